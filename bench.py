@@ -25,7 +25,16 @@ sequence (or problems); the only collective is the end-of-run gather of stats
 (RCCL when every rank has its own GPU, gloo when ranks share one).  Weak
 scaling: value = units of all ranks / the slowest rank's timed seconds.
 
-Prints ONE JSON line (rank 0) with roofline and cpu_baseline objects.
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up,
+times the N steps and prints ONE JSON line (rank 0): metric, value, unit,
+ms_per_step, and the dominant kernel's figures from the events inside the
+timed steps.  `--dump-outputs DIR` also writes the last timed step's outputs
+(the arrays a caller of the timed path receives) as DIR/<name>.npy, float32 /
+float64; the inputs are seeded, so two builds can be compared output for
+output.  `--full` adds everything else to the line: the serialised per-kernel
+pass and the headline roofline, the parity check of the last step against the
+oracle, the cpu_baseline objects (1 core and all cores), the host-fed (c2, c3)
+and host-array (c5) legs and the single-call legs (c2).
 """
 import argparse
 import ctypes
@@ -435,6 +444,9 @@ def run_pose(args, wl, rank, local, world, dist):
     arr, n_inl, st = ctx.pose_fetch()
     stats = np.array([elapsed, P * args.steps, int(n_inl[0]), st[0].rounds], dtype=np.float64)
     allst = odist.gather_stats(stats, dist, device=args.gather_device)   # before rank 0's CPU legs
+    if args.dump_outputs:
+        dump_outputs(args, rank, world, {"Tcw": np.stack([np.ctypeslib.as_array(a.Tcw) for a in arr]),
+                                         "n_inliers": n_inl, "outlier": np.stack([k[1]["outlier"] for k in keep])})
     ab = {"pose": n_edges * 25 + 80 + 160}
     units_per_step = {"pose": P}
     flops = float(np.mean([pose_flops(st[i], int(frames[i]["has_mp"].sum())) for i in range(len(uniq))]))
@@ -984,6 +996,8 @@ def run_frames(args, wl, rank, local, world, dist):
     _, nm = ctx.matches(B - 1)
     stats = np.array([elapsed, B * args.steps, len(k0), nm], dtype=np.float64)
     allst = odist.gather_stats(stats, dist, device=args.gather_device)   # before rank 0's CPU legs
+    if args.dump_outputs:
+        dump_outputs(args, rank, world, frames_outputs(ctx, last[0], B, nf))
     ab = algorithmic_bytes(w, h, nf, "bf" if bf else "init")
     units_per_step = {k: B for k in ab}
     cpu = None
@@ -1075,6 +1089,11 @@ def run_lba(args, wl, rank, local, world, dist):
     stats = np.array([elapsed, P * args.steps, st[0].iterations[0] + st[0].iterations[1], st[0].n_outliers[0]],
                      dtype=np.float64)
     allst = odist.gather_stats(stats, dist, device=args.gather_device)   # before rank 0's CPU legs
+    if args.dump_outputs:
+        def cat(key):   # the problems differ in size: one after the other, flat
+            return np.concatenate([c[1][key].reshape(-1) for c in work])
+        dump_outputs(args, rank, world, {"pose_q": cat("pose_q"), "pose_t": cat("pose_t"), "points": cat("points"),
+                                         "edge_status": np.concatenate(es), "point_bad": np.concatenate(pb)})
     # the last timed run's results against the oracle, before the host-array
     # leg below reuses these arrays (after the gather: the other ranks do
     # not wait in the collective while rank 0 runs the oracle)
@@ -1083,7 +1102,7 @@ def run_lba(args, wl, rank, local, world, dist):
     # both passes, D2H readback and unpacking), timed beside it on rank 0;
     # reported in `check`, never as `value`
     pcie = None
-    if rank == 0:
+    if rank == 0 and args.full:
         def host_step():
             for (_, a), pr in zip(work, probs):
                 np.copyto(a["pose_q"], pr["pose_q"])
@@ -1181,6 +1200,61 @@ def pmc_valu(key, name):
     return {"insts_per_launch": sum(hits) / len(hits), "source": src + " SQ_INSTS_VALU"}
 
 
+DUMP_BUDGET_BYTES = 60_000_000   # --dump-outputs writes at most this much (the option's limit is 64 MB)
+
+
+def dump_outputs(args, rank, world, arrays):
+    """--dump-outputs DIR: the last timed step's outputs as DIR/<name>.npy in
+    float32 / float64 (every rank its own files, <name>_rank<r>.npy, when
+    N > 1).  Called right after the timed region, before any other leg
+    touches the context or the host arrays."""
+    if not args.dump_outputs:
+        return
+    out = Path(args.dump_outputs)
+    out.mkdir(parents=True, exist_ok=True)
+    conv = {name: np.ascontiguousarray(a, dtype=np.float64 if np.asarray(a).dtype == np.float64 else np.float32)
+            for name, a in arrays.items()}
+    while sum(a.nbytes for a in conv.values()) > DUMP_BUDGET_BYTES:
+        # over the budget: the largest array gives way to a fixed, seeded sample of its elements (flat, in order)
+        name = max(conv, key=lambda k: conv[k].nbytes)
+        a = conv[name].reshape(-1)
+        over = sum(v.nbytes for v in conv.values()) - DUMP_BUDGET_BYTES
+        keep = max(1, a.size - (over + a.itemsize - 1) // a.itemsize)
+        conv[name] = a[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+    for name, a in conv.items():
+        np.save(out / (f"{name}_rank{rank}.npy" if world > 1 else f"{name}.npy"), a)
+
+
+def frames_outputs(ctx, first, B, nf):
+    """What a caller of extract_match receives for slots [first, first + B):
+    per frame the keypoint count, the keypoint records (7 fields, rows past
+    the count zero), the match vector against the predecessor (rows past the
+    predecessor's count zero) and the match count; the
+    descriptors of every frame, or of a fixed seeded sample of frames
+    (`descriptor_frames`) when all of them would not fit the budget."""
+    fields = ox.KEYPOINT.names
+    kps = np.zeros((B, nf, len(fields)), np.float32)
+    m12 = np.zeros((B, nf), np.float32)
+    n_kps, n_m = np.zeros(B, np.float32), np.zeros(B, np.float32)
+    fixed = kps.nbytes + m12.nbytes + 3 * 4 * B
+    n_desc = int(max(1, min(B, (DUMP_BUDGET_BYTES - fixed) // (nf * 32 * 4))))
+    picks = np.sort(np.random.default_rng(0).choice(B, n_desc, replace=False))
+    row = {int(f): i for i, f in enumerate(picks)}
+    desc = np.zeros((n_desc, nf, 32), np.float32)
+    for f in range(B):
+        gk, gd = ctx.features(first + f)
+        gm, gn = ctx.matches(first + f)
+        n_kps[f], n_m[f] = len(gk), gn
+        kps[f, :len(gk)] = np.stack([gk[name] for name in fields], 1)
+        m12[f, :len(gm)] = gm
+        if f in row:
+            desc[row[f], :len(gd)] = gd
+    for f in range(B):
+        m12[f, int(n_kps[(f - 1) % B]):] = 0
+    return {"n_keypoints": n_kps, "keypoints": kps, "matches": m12, "n_matches": n_m, "descriptors": desc,
+            "descriptor_frames": picks}
+
+
 def timed(args, ctx, step, dist, names, only=None):
     def barrier():
         if dist is not None:
@@ -1272,6 +1346,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=0, help="frames (or BA problems) per step per GPU")
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the serialised per-kernel pass (headline roofline), the parity "
+                         "check of the last step, the CPU baselines, the host-fed / host-array legs and the "
+                         "single-call legs (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last timed step's outputs as DIR/<name>.npy")
     ap.add_argument("--cpu-budget", type=float, default=12.0,
                     help="seconds of the all-cores CPU baseline x2 (the 1-core baseline follows CPU_PROTOCOL)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -1297,6 +1377,10 @@ def main():
     ap.add_argument("--no-kernel-timing", action="store_true",
                     help="diagnostic: no per-kernel hipEvents in the timed region (roofline then unavailable)")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run does what the headline figure needs: set-up, warm-up,
+        # the timed steps, --dump-outputs, the line
+        args.no_cpu_baseline = args.no_isolated = args.no_host_inclusive = args.no_single_call = True
     if args.cpu_protocol:
         CPU_PROTOCOL[args.workload] = tuple(int(v) for v in args.cpu_protocol.split(","))
 

@@ -15,18 +15,18 @@ out=gpurun_out/round
 mkdir -p "$out"
 export TMPDIR=/tmp
 if [ "$1" = bench ]; then   # the four bench lines only (after the profiles exist)
-timeout -k 10 300 python3 bench.py > "$out/bench_c2.json" 2> "$out/bench_c2.err"
-timeout -k 10 300 python3 bench.py --workload pose --cpu-budget 10 > "$out/bench_pose.json" 2> "$out/bench_pose.err"
-timeout -k 10 300 python3 bench.py --workload c3 --cpu-budget 10 > "$out/bench_c3.json" 2> "$out/bench_c3.err"
-timeout -k 10 300 python3 bench.py --workload c5 --cpu-budget 10 > "$out/bench_c5.json" 2> "$out/bench_c5.err"
+timeout -k 10 300 python3 bench.py --full > "$out/bench_c2.json" 2> "$out/bench_c2.err"
+timeout -k 10 300 python3 bench.py --full --workload pose --cpu-budget 10 > "$out/bench_pose.json" 2> "$out/bench_pose.err"
+timeout -k 10 300 python3 bench.py --full --workload c3 --cpu-budget 10 > "$out/bench_c3.json" 2> "$out/bench_c3.err"
+timeout -k 10 300 python3 bench.py --full --workload c5 --cpu-budget 10 > "$out/bench_c5.json" 2> "$out/bench_c5.err"
 elif [ "$1" = 1 ]; then
 timeout -k 10 600 python3 -u -m pytest tests -m gpu -q --timeout 120 --timeout-method thread > "$out/gpu_tests.log" 2>&1
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.log" 2>&1
-timeout -k 10 300 python3 bench.py > "$out/bench_c2.json" 2> "$out/bench_c2.err"
-timeout -k 10 300 python3 bench.py --workload pose --cpu-budget 10 > "$out/bench_pose.json" 2> "$out/bench_pose.err"
-timeout -k 10 300 python3 bench.py --workload c3 --cpu-budget 10 > "$out/bench_c3.json" 2> "$out/bench_c3.err"
-timeout -k 10 300 python3 bench.py --workload c5 --cpu-budget 10 > "$out/bench_c5.json" 2> "$out/bench_c5.err"
-timeout -k 10 300 python3 bench.py --gpus 2 --cpu-budget 4 > "$out/bench_c2_gpus2.json" 2> "$out/bench_c2_gpus2.err"
+timeout -k 10 300 python3 bench.py --full > "$out/bench_c2.json" 2> "$out/bench_c2.err"
+timeout -k 10 300 python3 bench.py --full --workload pose --cpu-budget 10 > "$out/bench_pose.json" 2> "$out/bench_pose.err"
+timeout -k 10 300 python3 bench.py --full --workload c3 --cpu-budget 10 > "$out/bench_c3.json" 2> "$out/bench_c3.err"
+timeout -k 10 300 python3 bench.py --full --workload c5 --cpu-budget 10 > "$out/bench_c5.json" 2> "$out/bench_c5.err"
+timeout -k 10 300 python3 bench.py --full --gpus 2 --cpu-budget 4 > "$out/bench_c2_gpus2.json" 2> "$out/bench_c2_gpus2.err"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/c2_serial" -o run -- \
     python3 tools/extract_serial.py > "$out/c2_serial.log" 2>&1
 elif [ "$1" = serial ]; then   # PMC of the serialised bench (the headline roofline's launch)
