@@ -262,7 +262,10 @@ int orbx_dev_kernel_time_enable(orbx_ctx* ctx, int enable);
 int orbx_dev_kernel_time_select(orbx_ctx* ctx, const char* name);
 
 /* Debug / parity taps: padded pyramid level (raw or blurred) of a slot.
- * Writes (w_l+32)*(h_l+32) bytes; *pw, *ph receive the padded size. */
+ * Writes (w_l+32)*(h_l+32) bytes; *pw, *ph receive the padded size.  The
+ * extraction keeps only the raw pyramid (the describe kernel blurs each
+ * keypoint's patch): a blurred level is computed by this call, from the raw
+ * pyramid the slot holds now. */
 int orbx_dev_read_level(orbx_ctx* ctx, int slot, int level, int blurred,
                         uint8_t* out, int cap, int* pw, int* ph);
 

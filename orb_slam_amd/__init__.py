@@ -138,6 +138,7 @@ def _declare(L):
         "orbx_lba_get_workgroups": ([vp], i),
         "orbx_lba_last_workgroups": ([vp], i),
         "orbx_debug_lba_split": ([vp, i, i, i, i], i),
+        "orbx_debug_describe_patch": ([vp, i, i, i, i, vp], i),
         "orbx_pose_set_exact": ([vp, i], i),
         "orbx_pose_get_exact": ([vp], i),
         "orbx_dev_set_image_bounds": ([vp, vp], i),
@@ -353,6 +354,13 @@ class Context:
         _check(lib().orbx_dev_read_level(self._h, slot, level, int(blurred), _ptr(buf), cap,
                                          ctypes.byref(pw), ctypes.byref(ph)), "orbx_dev_read_level")
         return buf[:pw.value * ph.value].reshape(ph.value, pw.value).copy()
+
+    def describe_patch(self, slot, level, x, y):
+        """The blurred 37x37 patch that the describe kernel builds around
+        level position (x, y) of the slot's pyramid (orbx_debug_describe_patch)."""
+        out = np.zeros((37, 37), np.uint8)
+        _check(lib().orbx_debug_describe_patch(self._h, slot, level, x, y, _ptr(out)), "orbx_debug_describe_patch")
+        return out
 
     def timing(self, enable=True, only=None):
         """Kernel timing with hipEvents around every launch, or only around

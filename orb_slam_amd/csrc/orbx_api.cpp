@@ -105,7 +105,8 @@ static int set_geometry(orbx_ctx* ctx, int w, int h)
     }
     if (g.frame_pyr_bytes > ctx->cap_pyr_bytes) {
         if ((r = realloc_dev(ctx->pyr_raw, (size_t)S * g.frame_pyr_bytes)) != ORBX_OK) return r;
-        if ((r = realloc_dev(ctx->pyr_blur, (size_t)S * g.frame_pyr_bytes)) != ORBX_OK) return r;
+        // one frame: orbx_dev_read_level's blurred levels, computed on demand
+        if ((r = realloc_dev(ctx->pyr_blur, (size_t)g.frame_pyr_bytes)) != ORBX_OK) return r;
         ctx->cap_pyr_bytes = g.frame_pyr_bytes;
     }
     if (g.list_entries + 4LL * (long long)g.cells.size() > ctx->cap_list_entries) {
@@ -597,7 +598,15 @@ int orbx_dev_read_level(orbx_ctx* ctx, int slot, int level, int blurred, uint8_t
     *pw = L.pw;
     *ph = L.ph;
     if (cap < L.pw * L.ph) return ORBX_ERR_CAPACITY;
-    const uint8_t* src = (blurred ? ctx->pyr_blur : ctx->pyr_raw) + (size_t)f * ctx->geom.frame_pyr_bytes + L.off;
+    // The extraction path keeps no blurred pyramid (k_describe blurs its own
+    // patches): the slot's raw pyramid is blurred now, by the whole-level
+    // k_blur, into the one-frame pyr_blur.
+    if (blurred) {
+        const int r = launch_blur_slot(ctx, f);
+        if (r != ORBX_OK) return r;
+        ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    }
+    const uint8_t* src = blurred ? ctx->pyr_blur + L.off : ctx->pyr_raw + (size_t)f * ctx->geom.frame_pyr_bytes + L.off;
     ORBX_HIP_CHECK(hipMemcpy2D(out, L.pw, src, L.stride, L.pw, L.ph, hipMemcpyDeviceToHost));
     return ORBX_OK;
 }

@@ -11,10 +11,12 @@
 //   k_retain_cells per-level quota redistribution + cell retainBest,
 //                  one wave per cell (libstdc++ introselect)  (:622-694)
 //   k_retain_levels level retainBest, one wave per level      (:697-701)
-//   k_blur         GaussianBlur 7x7 sigma 2 on each level     (:760)
-//   k_describe     IC_Angle + rBRIEF + coordinate scaling,
-//                  one wave per keypoint                      (:124-194, :705,
-//                                                              :764-777)
+//   k_blur         GaussianBlur 7x7 sigma 2 on each level     (:760); only for
+//                  orbx_dev_read_level's blurred levels
+//   k_describe     IC_Angle, the GaussianBlur of the keypoint's
+//                  patch, rBRIEF + coordinate scaling,
+//                  two keypoints per wave                     (:124-194, :705,
+//                                                              :760, :764-777)
 //
 // All integer / byte work; the bounds are HBM or latency, never MFMA.
 #include <algorithm>
@@ -82,7 +84,6 @@ struct ExtractArgs {
     // after nfeatures records), in place of a pack launch; else null
     uint8_t* host_out;
     int32_t* retain_scratch;        // slots x (list_entries + 4 ncells): global nth_element scratch
-    const int4* blur_tiles;         // k_blur work blocks (also the blur tail of k_fast_cells<..., true>)
     uint64_t* cell_keys64;          // HARRIS_SCORE: Harris-keyed cell lists (as cell_lists)
     uint64_t* level_keys64;         // HARRIS_SCORE: Harris-keyed level lists (as level_keys)
     int harris;                     // scoreType == HARRIS_SCORE
@@ -847,9 +848,10 @@ __host__ __device__ constexpr int fast_static_lds(bool u32_entries) { return 4 *
 #define ORBX_FAST_LDS_TARGET (40 * 1024)   // 4 workgroups per CU
 #endif
 constexpr int kFastLdsTarget = ORBX_FAST_LDS_TARGET;
-// Diagnostic builds only (-DORBX_DIAG_REPEAT=r,b,d,f): launch resize, blur,
+// Diagnostic builds only (-DORBX_DIAG_REPEAT=r,b,d,f): launch resize,
 // describe or FAST that many times (idempotent kernels) to price each
-// stage's marginal cost inside the pipelined bench.
+// stage's marginal cost inside the pipelined bench (b, once the whole-level
+// blur's count, is unused).
 #ifndef ORBX_DIAG_REPEAT
 #define ORBX_DIAG_REPEAT 1, 1, 1, 1
 #endif
@@ -860,22 +862,10 @@ constexpr int kDiagRepeat[4] = {ORBX_DIAG_REPEAT};
 // kThreads: 256 for cells up to 208-byte rows; the wide tiles of large
 // frames (1920x1080: 336-byte rows, 75 KB of LDS, two workgroups per CU)
 // get more waves per workgroup instead.
-__device__ __forceinline__ void blur_block(const ExtractArgs& a, const int4* tiles, int bx, int f);
-
-// kBlurTail (orbx_extract's single-frame graph): the grid carries the blur's
-// work blocks after the cells (blockIdx.x >= ncells), so FAST and the blur,
-// which both read only the raw pyramid, are one launch.
-template <int kP, int kThreads = 256, bool kBanded = false, bool kBlurTail = false>
+template <int kP, int kThreads = 256, bool kBanded = false>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(kThreads > 256 ? 6 : 4))) void k_fast_cells(
     ExtractArgs a, int tile_bytes, int band_rows)
 {
-    static_assert(!kBlurTail || kThreads == kBlurItems, "the blur tail runs 256-thread blur blocks");
-    if constexpr (kBlurTail) {
-        if ((int)blockIdx.x >= a.ncells) {
-            blur_block(a, a.blur_tiles, (int)blockIdx.x - a.ncells, (int)blockIdx.y);
-            return;
-        }
-    }
     constexpr int kBlock = kThreads, kWaves = kThreads / 64;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     __shared__ BlockScratchN<kWaves> bs;
@@ -1539,10 +1529,52 @@ __global__ __launch_bounds__(256) void k_retain_levels(ExtractArgs a, int waves_
 // slides a 7-row window of horizontal sums down it in registers: one pass
 // over the input rows it needs, one dword store per output row, no LDS.
 // ---------------------------------------------------------------------------
-__device__ inline void blur_hsum(const uint8_t* row, int x, int hs[4])
+typedef float orbx_f2 __attribute__((ext_vector_type(2)));
+
+// Horizontal pass of one dword (4 pixels; wl / wr: its left / right
+// neighbours): the four row sums as two packed float pairs.
+__device__ __forceinline__ void blur_hrow(uint32_t wl, uint32_t wc, uint32_t wr, orbx_f2 (&o)[2])
 {
-    const uint32_t* w = reinterpret_cast<const uint32_t*>(row + x);
-    blur_hsum_w(w[-1], w[0], w[1], hs);
+    int hs[4];
+    blur_hsum_w(wl, wc, wr, hs);
+    o[0] = orbx_f2{(float)hs[0], (float)hs[1]};
+    o[1] = orbx_f2{(float)hs[2], (float)hs[3]};
+}
+
+// Vertical pass of one dword over the 7 rows of horizontal sums R, in packed
+// FP32 (two pixels per v_pk_fma_f32): the row sums are integers <= 255 * 257
+// and N <= 255 * 257^2; every partial sum below 2^24 is exact, and an N beyond
+// 2^24 saturates to 255 either way.  Rounding and saturation by
+// v_cvt_pk_u8_f32 (round half to even = cvtps2dq of SymmColumnVec_32s8u); the
+// scalar tail columns (FixedPtCastEx, +2^15 >> 16) pass
+// floor((N + 2^15) / 2^16).  The taps carry the 1/65536: a power of two, so
+// every product and partial sum is the integer form's times 2^-16, still
+// exact.  Bytes that are not `inside` keep `raw`'s.
+__device__ __forceinline__ uint32_t blur_vstep(const orbx_f2 (&R)[7][2], uint32_t raw, const bool (&inside)[4],
+                                               const bool (&tail_col)[4], bool any_tail)
+{
+    constexpr float kInv = 1.0f / 65536.0f;
+    constexpr float k0 = 55.0f * kInv, k1 = 49.0f * kInv, k2 = 34.0f * kInv, k3 = 18.0f * kInv;
+    float sv[4];
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        orbx_f2 N = R[3][h] * k0;
+        N = __builtin_elementwise_fma(R[2][h] + R[4][h], orbx_f2{k1, k1}, N);
+        N = __builtin_elementwise_fma(R[1][h] + R[5][h], orbx_f2{k2, k2}, N);
+        N = __builtin_elementwise_fma(R[0][h] + R[6][h], orbx_f2{k3, k3}, N);
+        sv[2 * h] = N.x;
+        sv[2 * h + 1] = N.y;
+        if (any_tail) {
+            const orbx_f2 tl2 = N + 0.5f;
+            if (tail_col[2 * h]) sv[2 * h] = floorf(tl2.x);
+            if (tail_col[2 * h + 1]) sv[2 * h + 1] = floorf(tl2.y);
+        }
+    }
+    uint32_t word = raw;   // border columns keep the raw byte
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+        if (inside[j]) word = __builtin_amdgcn_cvt_pk_u8_f32(sv[j], j, word);
+    return word;
 }
 
 // One blur work block (bx) of frame f.
@@ -1606,27 +1638,14 @@ __device__ __forceinline__ void blur_block(const ExtractArgs& a, const int4* til
             inside[j] = xi >= 0 && xi < L.w;
             half_even[j] = xi < L.nvec_blur;
         }
-        // Vertical pass in packed FP32 (two pixels per v_pk_fma_f32): the row
-        // sums are integers <= 255 * 257 and N <= 255 * 257^2; every partial
-        // sum below 2^24 is exact, and an N beyond 2^24 saturates to 255 either
-        // way.  Rounding and saturation by v_cvt_pk_u8_f32 (round half to even
-        // = cvtps2dq of SymmColumnVec_32s8u); the scalar tail columns
-        // (FixedPtCastEx, +2^15 >> 16) pass floor((N + 2^15) / 2^16).
-        typedef float f2 __attribute__((ext_vector_type(2)));
-        constexpr float kInv = 1.0f / 65536.0f;
         bool tail_col[4], any_tail = false;
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             tail_col[j] = inside[j] && !half_even[j];
             any_tail = any_tail || tail_col[j];
         }
-        f2 R[7][2];
-        auto hrow = [&](uint32_t c, f2 (&o)[2]) {
-            int hs[4];
-            blur_hsum_w(left(c), c, right(c), hs);
-            o[0] = f2{(float)hs[0], (float)hs[1]};
-            o[1] = f2{(float)hs[2], (float)hs[3]};
-        };
+        orbx_f2 R[7][2];
+        auto hrow = [&](uint32_t c, orbx_f2 (&o)[2]) { blur_hrow(left(c), c, right(c), o); };
         uint32_t C[3];   // raw centre words of rows y, y+1, y+2 (loaded as rows y'+3 earlier)
         {
             uint32_t w0[6];
@@ -1652,26 +1671,7 @@ __device__ __forceinline__ void blur_block(const ExtractArgs& a, const int4* til
                 // no early exit, so the window rotation stays straight-line
                 const int y = yc + k;
                 hrow(wc[k], R[6]);
-                float sv[4];
-#pragma unroll
-                for (int h = 0; h < 2; h++) {
-                    f2 N = R[3][h] * 55.0f;
-                    N = __builtin_elementwise_fma(R[2][h] + R[4][h], f2{49.0f, 49.0f}, N);
-                    N = __builtin_elementwise_fma(R[1][h] + R[5][h], f2{34.0f, 34.0f}, N);
-                    N = __builtin_elementwise_fma(R[0][h] + R[6][h], f2{18.0f, 18.0f}, N);
-                    const f2 sc = N * kInv;
-                    sv[2 * h] = sc.x;
-                    sv[2 * h + 1] = sc.y;
-                    if (any_tail) {
-                        const f2 tl2 = (N + 32768.0f) * kInv;
-                        if (tail_col[2 * h]) sv[2 * h] = floorf(tl2.x);
-                        if (tail_col[2 * h + 1]) sv[2 * h + 1] = floorf(tl2.y);
-                    }
-                }
-                uint32_t word = C[0];   // border columns keep the raw byte
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-                    if (inside[j]) word = __builtin_amdgcn_cvt_pk_u8_f32(sv[j], j, word);
+                const uint32_t word = blur_vstep(R, C[0], inside, tail_col, any_tail);
                 if (y < yb) st(y, word & keep_mask);
 #pragma unroll
                 for (int kk = 0; kk < 6; kk++)
@@ -1693,17 +1693,156 @@ __global__ __launch_bounds__(256) void k_blur(ExtractArgs a, const int4* tiles)
 
 // ---------------------------------------------------------------------------
 // IC_Angle + computeOrbDescriptor + output assembly, one wave per keypoint.
-// The wave first stages, with independent dword loads, the 31x31 unblurred
-// patch (IC_Angle reads radius 15) and the 37x37 blurred patch (rotated
-// pattern points reach cvRound(13*sqrt(2)) = 18) in LDS, so the gathers
-// cost one memory round trip instead of a dependent chain.
+// The wave first stages, with independent dword loads, one unblurred window
+// per keypoint in LDS: rows Y - 21 .. Y + 21, 12 dwords per row from
+// (X - 21) & ~3.  It holds the 31x31 patch of IC_Angle (radius 15) and every
+// tap of the 37x37 blurred patch of the descriptor (rotated pattern points
+// reach cvRound(13*sqrt(2)) = 18, the 7x7 filter 3 more).  Keypoints lie in
+// [16, w - 16) x [16, h - 16) of the level and the padded border is 16, so
+// the window stays inside the padded level.  After IC_Angle the half-wave
+// blurs the 37x37 patch in place (describe_blur_window): the whole-level
+// blur pass and its second pyramid are not on the extraction path.
 // ---------------------------------------------------------------------------
 constexpr int kIcRows = 2 * kHalfPatch + 1;          // 31
-constexpr int kIcPitch = 36;                         // 9 dwords: 31 bytes + alignment
 constexpr int kBrR = 18;                             // pattern reach
 constexpr int kBrRows = 2 * kBrR + 1;                // 37
-constexpr int kBrPitch = 40;                         // 10 dwords: 37 bytes + alignment
-constexpr int kDescWaveBytes = kIcRows * kIcPitch + kBrRows * kBrPitch;
+constexpr int kWinR = kBrR + 3;                      // + the filter's reach
+constexpr int kWinRows = 2 * kWinR + 1;              // 43
+constexpr int kWinDw = 12;                           // dwords per window row
+constexpr int kBrPitch = 4 * kWinDw;                 // 48: window row pitch (raw and blurred)
+constexpr int kWinPad = 16;                          // in front: dword column 0's left neighbour reads into it
+constexpr int kDescWaveBytes = kWinPad + kWinRows * kBrPitch;   // 2080 per keypoint
+constexpr int kWinCols = 10;                         // dword columns that hold the 37 blurred bytes
+constexpr int kWinStrips = 3;                        // row strips per column; 30 of the 32 lanes work
+constexpr int kWinStripRows = 13;                    // rows 0..12, 12..24, 24..36 (rows 12 and 24 twice)
+static_assert(kWinCols * kWinStrips <= 32 && (kWinStrips - 1) * (kWinStripRows - 1) + kWinStripRows == kBrRows,
+              "the strips of one half-wave cover the blurred patch");
+
+// Orders a half-wave's LDS writes before the other lanes' reads (and the
+// reverse): one wave, so no hardware barrier.
+__device__ __forceinline__ void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Stages the raw window of the keypoint at padded level position (X, Y) into
+// win (kWinRows * kBrPitch bytes behind the keypoint's kWinPad), lane hl of
+// 32; lev: the padded level.  All loads in flight together; 32-bit offsets
+// from the window's first row, (row, dword) stepped per load.  Returns the
+// window centre's byte offset in win.
+__device__ __forceinline__ int describe_stage_window(const uint8_t* lev, uint32_t stride, int X, int Y, uint8_t* win,
+                                                     int hl)
+{
+    constexpr int n = kWinRows * kWinDw, nld = (n + 31) / 32;
+    const int x0 = (X - kWinR) & ~3;
+    const uint8_t* r0 = lev + (long long)(Y - kWinR) * stride + x0;
+    uint32_t* w32 = reinterpret_cast<uint32_t*>(win);
+    uint32_t v[nld];
+    int r = hl / kWinDw, q = hl - (hl / kWinDw) * kWinDw;
+#pragma unroll
+    for (int k = 0; k < nld; k++) {
+        const bool in = hl + 32 * k < n;
+        // lanes past the window re-load (and below re-store) its last dword
+        v[k] = *reinterpret_cast<const uint32_t*>(
+            r0 + (in ? (uint32_t)r * stride + 4u * (uint32_t)q : (uint32_t)(kWinRows - 1) * stride + 4u * (kWinDw - 1)));
+        r += 32 / kWinDw;
+        q += 32 % kWinDw;
+        if (q >= kWinDw) {
+            q -= kWinDw;
+            r++;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < nld; k++) w32[min(hl + 32 * k, n - 1)] = v[k];
+    return kWinR * kBrPitch + (X - x0);
+}
+
+// GaussianBlur 7x7 of the 37x37 patch around (X, Y) inside the staged raw
+// window, in place: k_blur's filter (blur_hrow, blur_vstep) and its rules per
+// byte at level position (xi, yi): outside [0, w) x [0, h) the raw border
+// byte, inside the 7x7 result over the raw padded pixels, with the float
+// rounding for xi < nvec and the tail rounding beyond.  Lane hl owns one
+// dword column and one strip of kWinStripRows rows; it slides a 7-row window
+// of horizontal sums down the strip in registers and keeps its output words
+// there until every lane has read its raw rows.  Bytes of the 10 dword
+// columns outside the 37x37 patch are undefined.
+__device__ __forceinline__ void describe_blur_window(uint8_t* win, int X, int Y, int lw, int lh, int nvec, int hl)
+{
+    const int x0 = (X - kWinR) & ~3;
+    const int d0 = (X - x0 - kBrR) >> 2;   // first dword column with patch bytes: 0 or 1
+    const bool act = hl < kWinCols * kWinStrips;
+    const int strip = min(hl / kWinCols, kWinStrips - 1), d = d0 + (hl - (hl / kWinCols) * kWinCols);
+    const int j0 = strip * (kWinStripRows - 1);   // first patch row of the strip = its first input row of the window
+    // dword column 0 has no left neighbour (the read falls into the previous
+    // row or kWinPad): only its byte 3 can be a patch byte (d0 = 0: the patch
+    // starts at byte 3), and that sum does not read the left word
+    uint32_t* wp = reinterpret_cast<uint32_t*>(win) + j0 * kWinDw + d;
+    const bool all[4] = {true, true, true, true};
+    bool tail_col[4], any_tail = false;
+    uint32_t in_mask = 0;   // bytes inside the level's columns
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int xi = x0 + 4 * d + j - kEdge;
+        const bool inside = xi >= 0 && xi < lw;
+        if (inside) in_mask |= 0xFFu << (8 * j);
+        tail_col[j] = inside && xi >= nvec;
+        any_tail = any_tail || tail_col[j];
+    }
+    const int yi0 = Y - kBrR + j0 - kEdge;   // level row of the strip's first output row
+    uint32_t outw[kWinStripRows];
+    // tail: some lane of the wave has a tail column (rare: a keypoint within
+    // 18 columns of the right edge of a level whose width is not vectorised
+    // to the end); the common instance carries no tail arithmetic
+    auto strip_rows = [&](auto tail) {
+        orbx_f2 R[7][2];
+        uint32_t C[3];   // raw centre words of the next three output rows
+        uint32_t w[3];   // the next input row's left, centre and right words
+        auto ldrow = [&](int r) {
+#pragma unroll
+            for (int i = 0; i < 3; i++) w[i] = wp[r * kWinDw - 1 + i];
+        };
+        // one row's words are read ahead of the row being filtered, no more
+        // (the scheduler would otherwise hoist every read and spill)
+        auto hrow = [&](int r, orbx_f2 (&o)[2]) {
+            const uint32_t l = w[0], c = w[1], rr = w[2];
+            if (r + 1 <= kWinStripRows + 5) ldrow(r + 1);
+            blur_hrow(l, c, rr, o);
+            __builtin_amdgcn_sched_barrier(0);
+            return c;
+        };
+        ldrow(0);
+#pragma unroll
+        for (int k = 0; k < 6; k++) {
+            const uint32_t c = hrow(k, R[k]);
+            if (k >= 3) C[k - 3] = c;
+        }
+#pragma unroll
+        for (int k = 0; k < kWinStripRows; k++) {
+            const uint32_t c = hrow(k + 6, R[6]);
+            // border rows and columns keep the raw bytes
+            const uint32_t word = blur_vstep(R, 0u, all, tail_col, decltype(tail)::value);
+            const uint32_t m = (unsigned)(yi0 + k) < (unsigned)lh ? in_mask : 0u;
+            outw[k] = (word & m) | (C[0] & ~m);
+#pragma unroll
+            for (int kk = 0; kk < 6; kk++)
+#pragma unroll
+                for (int h = 0; h < 2; h++) R[kk][h] = R[kk + 1][h];
+            C[0] = C[1];
+            C[1] = C[2];
+            C[2] = c;
+        }
+    };
+    if (__any(any_tail)) strip_rows(std::true_type{});
+    else strip_rows(std::false_type{});
+    wave_lds_sync();
+    if (act) {
+#pragma unroll
+        for (int k = 0; k < kWinStripRows; k++) wp[(k + 3) * kWinDw] = outw[k];
+    }
+    wave_lds_sync();
+}
 
 // Half-wave (32-lane) sums: DPP row shifts inside each 16-lane row, then
 // row_bcast:15 folds row 0 into row 1 and row 2 into row 3; lane 31 holds the
@@ -1742,7 +1881,6 @@ __device__ inline int orb_sample_offset(float px, float py, float sa, float ca)
 // offset row * kBrPitch + col (+ base, folded into the column's round trip)
 // is then an exact float fma on integers below 2^24.  Returns the two LDS
 // byte addresses.
-typedef float orbx_f2 __attribute__((ext_vector_type(2)));
 template <bool kFma>
 __device__ inline void orb_sample_addr2(orbx_f2 px, orbx_f2 py, float sa, float ca, float base, uint32_t& a1,
                                         uint32_t& a2)
@@ -1764,8 +1902,10 @@ __device__ inline void orb_sample_addr2(orbx_f2 px, orbx_f2 py, float sa, float 
     a2 = (uint32_t)ad.y;
 }
 
+// 5 waves per SIMD: the register allocator otherwise spends past 128 VGPRs
+// on hoisted window reads (the kernel is VALU-bound; 90 VGPRs, no spills)
 template <bool kFma>
-__global__ __launch_bounds__(256) void k_describe(ExtractArgs a, int nframes)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k_describe(ExtractArgs a, int nframes)
 {
     __shared__ __attribute__((aligned(16))) uint8_t s_patch[2 * kWaves][kDescWaveBytes];
     // XCD-aware order (xcd_block): a frame's keypoint patches, which overlap,
@@ -1788,6 +1928,7 @@ __global__ __launch_bounds__(256) void k_describe(ExtractArgs a, int nframes)
     const int cnt_l = lane < a.nlevels ? a.level_count[(size_t)f * a.nlevels + lane] : 0;
     const long long off_l = a.levels[ll].off;
     const int stride_l = a.levels[ll].stride, loff_l = a.levels[ll].level_off;
+    const int w_l = a.levels[ll].w, h_l = a.levels[ll].h, nvec_l = a.levels[ll].nvec_blur;
     const float scale_l = a.levels[ll].scale, psize_l = a.levels[ll].patch_size;
     int total = 0, level = -1, local = 0;
     for (int l = 0; l < a.nlevels; l++) {
@@ -1822,6 +1963,7 @@ __global__ __launch_bounds__(256) void k_describe(ExtractArgs a, int nframes)
     const long long lev_off = (long long)(((unsigned long long)(uint32_t)pick((int)(off_l >> 32)) << 32) |
                                           (uint32_t)pick((int)off_l));
     const int lev_stride = pick(stride_l), lev_loff = pick(loff_l);
+    const int lev_w = pick(w_l), lev_h = pick(h_l), lev_nvec = pick(nvec_l);
     const float lev_scale = __int_as_float(pick(__float_as_int(scale_l)));
     const float lev_psize = __int_as_float(pick(__float_as_int(psize_l)));
     uint32_t e;
@@ -1836,63 +1978,13 @@ __global__ __launch_bounds__(256) void k_describe(ExtractArgs a, int nframes)
     }
     const int y = (int)((e >> 12) & 0xFFF), x = (int)(e & 0xFFF);
     const int X = kEdge + (valid ? x : kHalfPatch + 8), Y = kEdge + (valid ? y : kHalfPatch + 8);
-    uint8_t* ic = s_patch[slot];
-    uint8_t* br = ic + kIcRows * kIcPitch;
-    {
-        const uint8_t* raw = a.pyr_raw + (size_t)f * a.frame_pyr_bytes + lev_off;
-        const uint8_t* blr = a.pyr_blur + (size_t)f * a.frame_pyr_bytes + lev_off;
-        const int ix0 = (X - kHalfPatch) & ~3, bx0 = (X - kBrR) & ~3;
-        uint32_t* ic32 = reinterpret_cast<uint32_t*>(ic);
-        uint32_t* br32 = reinterpret_cast<uint32_t*>(br);
-        // both patches' loads (9 + 12 per lane) in flight together; 32-bit
-        // offsets from the patches' first rows, (row, dword) stepped per load
-        constexpr int nic = kIcRows * (kIcPitch / 4), nbr = kBrRows * (kBrPitch / 4);
-        constexpr int qi = kIcPitch / 4, qb = kBrPitch / 4;
-        const uint8_t* ri = raw + (long long)(Y - kHalfPatch) * lev_stride + ix0;
-        const uint8_t* rb = blr + (long long)(Y - kBrR) * lev_stride + bx0;
-        const uint32_t stride = (uint32_t)lev_stride;
-        uint32_t vi[(nic + 31) / 32], vb[(nbr + 31) / 32];
-        {
-            int r = hl / qi, q = hl - (hl / qi) * qi;
-#pragma unroll
-            for (int k = 0; k < (nic + 31) / 32; k++) {
-                const bool in = hl + 32 * k < nic;
-                // lanes past the patch re-load (and below re-store) its last dword
-                vi[k] = *reinterpret_cast<const uint32_t*>(
-                    ri + (in ? (uint32_t)r * stride + 4u * (uint32_t)q : (uint32_t)(kIcRows - 1) * stride + 4u * (qi - 1)));
-                r += 32 / qi;
-                q += 32 % qi;
-                if (q >= qi) {
-                    q -= qi;
-                    r++;
-                }
-            }
-        }
-        {
-            int r = hl / qb, q = hl - (hl / qb) * qb;
-#pragma unroll
-            for (int k = 0; k < (nbr + 31) / 32; k++) {
-                const bool in = hl + 32 * k < nbr;
-                vb[k] = *reinterpret_cast<const uint32_t*>(
-                    rb + (in ? (uint32_t)r * stride + 4u * (uint32_t)q : (uint32_t)(kBrRows - 1) * stride + 4u * (qb - 1)));
-                r += 32 / qb;
-                q += 32 % qb;
-                if (q >= qb) {
-                    q -= qb;
-                    r++;
-                }
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < (nic + 31) / 32; k++) ic32[min(hl + 32 * k, nic - 1)] = vi[k];
-#pragma unroll
-        for (int k = 0; k < (nbr + 31) / 32; k++) br32[min(hl + 32 * k, nbr - 1)] = vb[k];
-        ic += (X - kHalfPatch) - ix0 + kHalfPatch * kIcPitch + kHalfPatch;   // -> patch center
-        br += (X - kBrR) - bx0 + kBrR * kBrPitch + kBrR;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    // the raw window; ic / br: its centre, the patch centre of IC_Angle now
+    // and of the blurred patch after describe_blur_window
+    uint8_t* win = s_patch[slot] + kWinPad;
+    const uint8_t* ic =
+        win + describe_stage_window(a.pyr_raw + (size_t)f * a.frame_pyr_bytes + lev_off, (uint32_t)lev_stride, X, Y, win, hl);
+    const uint8_t* br = ic;
+    wave_lds_sync();
     // IC_Angle on the unblurred level (src/ORBextractor.cc:124-151): lane u
     // of the half takes column u - 15 over all rows of the circular patch
     int m01 = 0, m10 = 0;
@@ -1904,7 +1996,7 @@ __global__ __launch_bounds__(256) void k_describe(ExtractArgs a, int nframes)
         for (int v = 1; v <= kHalfPatch; v++) {
             const int d = __builtin_amdgcn_readlane(umax_l, v);
             if (u >= -d && u <= d) {
-                const int vp = ic[u + v * kIcPitch], vm = ic[u - v * kIcPitch];
+                const int vp = ic[u + v * kBrPitch], vm = ic[u - v * kBrPitch];
                 m01 += v * (vp - vm);
                 m10 += u * (vp + vm);
             }
@@ -1913,7 +2005,10 @@ __global__ __launch_bounds__(256) void k_describe(ExtractArgs a, int nframes)
     m01 = half_wave_sum(m01);
     m10 = half_wave_sum(m10);
     const float angle = fast_atan2_deg((float)m01, (float)m10);
-    // computeOrbDescriptor on the blurred level (src/ORBextractor.cc:155-194)
+    // the blurred patch overwrites the raw window, behind a wave_lds_sync
+    // that follows every lane's IC_Angle reads
+    describe_blur_window(win, X, Y, lev_w, lev_h, lev_nvec, hl);
+    // computeOrbDescriptor on the blurred patch (src/ORBextractor.cc:155-194)
     const float factorPI = (float)(M_PI / 180.f);
     float sa, ca;
     cr_sincosf(__fmul_rn(angle, factorPI), &sa, &ca);
@@ -2006,6 +2101,65 @@ extern "C" int orbx_debug_nth(const uint32_t* entries, int n, int nth, uint32_t*
 
 namespace orbx {
 
+// Test hook: k_describe's window staging and patch blur for one position of
+// one level, both halves of the wave on the same keypoint; the blurred 37x37
+// patch goes to out, row-major.
+__global__ __launch_bounds__(64) void k_debug_describe_patch(const uint8_t* lev, LevelGeom L, int X, int Y, uint8_t* out)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t s_patch[2][kDescWaveBytes];
+    const int lane = threadIdx.x, half = lane >> 5, hl = lane & 31;
+    uint8_t* win = s_patch[half] + kWinPad;
+    const int centre = describe_stage_window(lev, (uint32_t)L.stride, X, Y, win, hl);
+    wave_lds_sync();
+    describe_blur_window(win, X, Y, L.w, L.h, L.nvec_blur, hl);
+    if (half == 0)
+        for (int i = hl; i < kBrRows * kBrRows; i += 32) {
+            const int r = i / kBrRows, c = i - r * kBrRows;
+            out[i] = win[centre + (r - kBrR) * kBrPitch + (c - kBrR)];
+        }
+}
+
+// The whole-level blur of one slot's raw pyramid into the one-frame
+// ctx->pyr_blur, on the context stream (orbx_dev_read_level's blurred levels).
+int launch_blur_slot(orbx_ctx* ctx, int slot)
+{
+    ExtractArgs a = {};
+    a.levels = ctx->dgeom.levels;
+    a.pyr_raw = ctx->pyr_raw + (size_t)slot * ctx->geom.frame_pyr_bytes;
+    a.pyr_blur = ctx->pyr_blur;
+    a.frame_pyr_bytes = ctx->geom.frame_pyr_bytes;
+    hipLaunchKernelGGL(k_blur, dim3(ctx->blur_tiles_n, 1), dim3(kBlurItems), 0, ctx->stream, a, ctx->blur_tiles);
+    if (hipGetLastError() != hipSuccess) return ORBX_ERR_HIP;
+    return ORBX_OK;
+}
+
+}  // namespace orbx
+
+/* Diagnostics (not in include/orbx.h): the blurred 37x37 descriptor patch
+ * that k_describe builds for a keypoint at level position (x, y) of slot
+ * `slot`'s raw pyramid, 16 <= x < w - 16, 16 <= y < h - 16, row-major. */
+extern "C" int orbx_debug_describe_patch(orbx_ctx* ctx, int slot, int level, int x, int y, uint8_t* out)
+{
+    using namespace orbx;
+    if (!ctx || !out || slot < 0 || slot >= ctx->slots || level < 0 || level >= ctx->geom.nlevels) return ORBX_ERR_ARG;
+    const LevelGeom& L = ctx->geom.levels[level];
+    if (x < kEdge || x >= L.w - kEdge || y < kEdge || y >= L.h - kEdge) return ORBX_ERR_ARG;
+    ctx_enter(ctx);
+    uint8_t* d = nullptr;
+    if (hipDeviceSynchronize() != hipSuccess) return ORBX_ERR_HIP;   // every part stream's pyramid
+    if (hipMalloc(&d, kBrRows * kBrRows) != hipSuccess) return ORBX_ERR_NOMEM;
+    const uint8_t* lev = ctx->pyr_raw + (size_t)slot * ctx->geom.frame_pyr_bytes + L.off;
+    hipLaunchKernelGGL(k_debug_describe_patch, dim3(1), dim3(64), 0, ctx->stream, lev, L, kEdge + x, kEdge + y, d);
+    int r = ORBX_OK;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess ||
+        hipMemcpy(out, d, kBrRows * kBrRows, hipMemcpyDeviceToHost) != hipSuccess)
+        r = ORBX_ERR_HIP;
+    (void)hipFree(d);
+    return r;
+}
+
+namespace orbx {
+
 // ---------------------------------------------------------------------------
 // Host launcher
 // ---------------------------------------------------------------------------
@@ -2030,7 +2184,7 @@ int launch_extract(orbx_ctx* ctx, int first, int count, const MatchSpec* m)
     // work buffers are per slot (frame f of this pass uses slot first + f):
     // batches on disjoint slots can be in flight at the same time
     a.pyr_raw = ctx->pyr_raw + (size_t)first * g.frame_pyr_bytes;
-    a.pyr_blur = ctx->pyr_blur + (size_t)first * g.frame_pyr_bytes;
+    a.pyr_blur = nullptr;   // off the extraction path (launch_blur_slot fills the one-frame buffer)
     a.cell_lists = ctx->cell_lists + (size_t)first * g.list_entries;
     a.cell_count = ctx->cell_count + (size_t)first * g.cells.size();
     a.level_keys = ctx->level_keys + (size_t)first * g.level_entries;
@@ -2041,7 +2195,6 @@ int launch_extract(orbx_ctx* ctx, int first, int count, const MatchSpec* m)
     a.error_flags = ctx->error_flags;
     a.host_out = ctx->single_frame ? ctx->single_out : nullptr;
     a.retain_scratch = ctx->retain_scratch + (size_t)first * (g.list_entries + 4 * g.cells.size());
-    a.blur_tiles = ctx->blur_tiles;
     a.harris = ctx->harris;
     a.fp_contract = ctx->fp_contract;
     a.nth_pivot = ctx->nth_pivot;
@@ -2126,13 +2279,10 @@ int launch_extract(orbx_ctx* ctx, int first, int count, const MatchSpec* m)
         }
     };
     // FAST .. describe over nb frames on stream st (after their pyramid).
-    // parts: 1 = FAST, 2 = retain, 4 = blur, 8 = describe
-    // 16 = FAST with the blur's blocks in the same launch where the FAST
-    // instance takes them (whole cells at a template pitch), else FAST then blur
+    // parts: 1 = FAST, 2 = retain, 8 = describe (4 was the whole-level blur:
+    // k_describe blurs its own patches)
     auto run_rest = [&](const ExtractArgs& x, int nb, hipStream_t st, int parts) {
-        const bool tail = (parts & 16) != 0;
-        bool tail_done = false;
-        if (parts & (1 | 16)) {
+        if (parts & 1) {
         timer_begin(ctx, "fast", st);
         {
             // widest aligned cell row and tallest cell pick the tile pitch
@@ -2162,12 +2312,6 @@ int launch_extract(orbx_ctx* ctx, int first, int count, const MatchSpec* m)
                 const int lds = fast_lds_bytes(bytes);
                 hipLaunchKernelGGL(kern, grid, dim3(threads), lds, st, x, bytes, band_rows);
             };
-            auto fast_tail = [&](auto kern, int bytes) {
-                const int lds = fast_lds_bytes(bytes);
-                hipLaunchKernelGGL(kern, dim3((int)g.cells.size() + ctx->blur_tiles_n, nb), dim3(256), lds, st, x, bytes,
-                                   0);
-                tail_done = true;
-            };
             // the templated instances queue u16 tile positions: windows of up
             // to 64 KB (larger ones take the runtime-pitch instance)
             // whole cells at the 96 / 144 / 208 pitches (their tiles fit four
@@ -2184,17 +2328,10 @@ int launch_extract(orbx_ctx* ctx, int first, int count, const MatchSpec* m)
                 bytes = plan(P, fast_static_lds(false), br);
                 return bytes <= 65536;
             };
-            if (fits(96)) {
-                if (tail) fast_tail(k_fast_cells<96, 256, false, true>, bytes);
-                else fast(k_fast_cells<96>, bytes, 0, 256);
-            } else if (fits(144)) {
-                if (tail) fast_tail(k_fast_cells<144, 256, false, true>, bytes);
-                else
+            if (fits(96)) fast(k_fast_cells<96>, bytes, 0, 256);
+            else if (fits(144)) {
                 for (int rep = 0; rep < kDiagRepeat[3]; rep++) fast(k_fast_cells<144>, bytes, 0, 256);
-            } else if (fits(208)) {
-                if (tail) fast_tail(k_fast_cells<208, 256, false, true>, bytes);
-                else fast(k_fast_cells<208>, bytes, 0, 256);
-            }
+            } else if (fits(208)) fast(k_fast_cells<208>, bytes, 0, 256);
             else if (fits_banded(336)) fast(k_fast_cells<336, kFastWideThreads, true>, bytes, br, kFastWideThreads);
             else {
                 bytes = plan(wmax, fast_static_lds(true), br);
@@ -2228,12 +2365,6 @@ int launch_extract(orbx_ctx* ctx, int first, int count, const MatchSpec* m)
             }
         }
         timer_end(ctx, "retain", st);
-        }
-        if (parts & 4 || (tail && !tail_done)) {
-            timer_begin(ctx, "blur", st);
-            for (int rep = 0; rep < kDiagRepeat[1]; rep++)
-                hipLaunchKernelGGL(k_blur, dim3(ctx->blur_tiles_n, nb), dim3(kBlurItems), 0, st, x, ctx->blur_tiles);
-            timer_end(ctx, "blur", st);
         }
         if (!(parts & 8)) return;
         timer_begin(ctx, "describe", st);
@@ -2317,7 +2448,6 @@ int launch_extract(orbx_ctx* ctx, int first, int count, const MatchSpec* m)
                 ExtractArgs b = a;
                 b.first_slot = first + lo;
                 b.pyr_raw += (size_t)lo * a.frame_pyr_bytes;
-                b.pyr_blur += (size_t)lo * a.frame_pyr_bytes;
                 b.cell_lists += (size_t)lo * a.list_entries;
                 b.retain_scratch += (size_t)lo * (a.list_entries + 4 * a.ncells);
                 b.cell_count += (size_t)lo * a.ncells;
@@ -2356,7 +2486,6 @@ int launch_extract(orbx_ctx* ctx, int first, int count, const MatchSpec* m)
         ExtractArgs b = a;
         b.first_slot = first + n0;
         b.pyr_raw += (size_t)n0 * a.frame_pyr_bytes;
-        b.pyr_blur += (size_t)n0 * a.frame_pyr_bytes;
         b.cell_lists += (size_t)n0 * a.list_entries;
         b.retain_scratch += (size_t)n0 * (a.list_entries + 4 * a.ncells);
         b.cell_count += (size_t)n0 * a.ncells;
@@ -2382,11 +2511,9 @@ int launch_extract(orbx_ctx* ctx, int first, int count, const MatchSpec* m)
         match_runs(first + n0, first + count, -0x7fffffff, first, ctx->stream);
     } else if (ctx->single_frame && count == 1) {
         // one frame (orbx_extract's captured graph), for latency: the raw
-        // pyramid as one cascade launch, FAST with the blur's blocks in its
-        // grid (a branch for the blur measured slower: the cross-queue join
-        // cost more than the blur), then retain and describe
+        // pyramid as one cascade launch, then FAST, retain and describe
         run_pyramid(a, 1, ctx->stream);
-        run_rest(a, 1, ctx->stream, 16 | 2 | 8);
+        run_rest(a, 1, ctx->stream, 1 | 2 | 8);
         match_runs(first, first + count, 0, -1, ctx->stream);
     } else {
         run(a, count, ctx->stream);

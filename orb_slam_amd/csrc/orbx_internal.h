@@ -5,8 +5,11 @@
 //   pyr_raw     slots x frame_pyr_bytes        padded levels (w_l+32)x(h_l+32),
 //                                              rows padded to 64 B; level l at
 //                                              LevelGeom::off.  Unblurred.
-//   pyr_blur    slots x frame_pyr_bytes        same layout; interior blurred,
-//                                              border = unblurred border
+//   pyr_blur    1 x frame_pyr_bytes            same layout, one frame; interior
+//                                              blurred, border = unblurred border.
+//                                              Not on the extraction path (k_describe
+//                                              blurs each keypoint's patch in LDS):
+//                                              written by orbx_dev_read_level(blurred)
 //   cell_lists  slots x list_entries  u32      FAST corners per cell, raster
 //                                              order, packed score<<24|y<<12|x
 //                                              (level coordinates)
@@ -352,6 +355,7 @@ struct MatchSpec {
     float nnratio;
 };
 int launch_extract(orbx_ctx* ctx, int first, int count, const MatchSpec* m = nullptr);
+int launch_blur_slot(orbx_ctx* ctx, int slot);   // k_blur of one slot's raw pyramid into the one-frame pyr_blur
 // timing helpers (orbx_api.cpp)
 void timer_begin(orbx_ctx* ctx, const char* name, hipStream_t st = nullptr);
 void timer_end(orbx_ctx* ctx, const char* name, hipStream_t st = nullptr);
