@@ -139,6 +139,7 @@ def _declare(L):
         "orbx_lba_last_workgroups": ([vp], i),
         "orbx_debug_lba_split": ([vp, i, i, i, i], i),
         "orbx_debug_describe_patch": ([vp, i, i, i, i, vp], i),
+        "orbx_debug_level0_direct": ([vp], i),
         "orbx_pose_set_exact": ([vp, i], i),
         "orbx_pose_get_exact": ([vp], i),
         "orbx_dev_set_image_bounds": ([vp, vp], i),
@@ -361,6 +362,14 @@ class Context:
         out = np.zeros((37, 37), np.uint8)
         _check(lib().orbx_debug_describe_patch(self._h, slot, level, x, y, _ptr(out)), "orbx_debug_describe_patch")
         return out
+
+    def level0_direct(self):
+        """Whether the last extraction read pyramid level 0 from the frame
+        store, without the padded copy (orbx_debug_level0_direct)."""
+        r = lib().orbx_debug_level0_direct(self._h)
+        if r < 0:
+            raise OrbxError(r, "orbx_debug_level0_direct")
+        return bool(r)
 
     def timing(self, enable=True, only=None):
         """Kernel timing with hipEvents around every launch, or only around

@@ -601,8 +601,15 @@ int orbx_dev_read_level(orbx_ctx* ctx, int slot, int level, int blurred, uint8_t
     // The extraction path keeps no blurred pyramid (k_describe blurs its own
     // patches): the slot's raw pyramid is blurred now, by the whole-level
     // k_blur, into the one-frame pyr_blur.
+    // Level 0's padded copy is not on the extraction path either (direct
+    // mode reads the frame store): it is rebuilt now from the slot's current
+    // frame, here for the raw level and inside launch_blur_slot.
     if (blurred) {
         const int r = launch_blur_slot(ctx, f);
+        if (r != ORBX_OK) return r;
+        ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    } else if (level == 0) {
+        const int r = launch_level0_slot(ctx, f);
         if (r != ORBX_OK) return r;
         ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     }

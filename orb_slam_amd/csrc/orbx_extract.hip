@@ -1,7 +1,9 @@
 // ORB extraction on MI355X (gfx950): ORBextractor::operator()
 // (src/ORBextractor.cc:718-779) for a batch of frames, one launch per stage:
 //
-//   k_pyr_level0   copyMakeBorder(REFLECT_101) of the input   (:814)
+//   k_pyr_level0   copyMakeBorder(REFLECT_101) of the input   (:814); not
+//                  launched for frames of w % 16 == 0, whose level 0 the
+//                  kernels below read from the frame store (level_src)
 //   k_pyr_resize   resize INTER_LINEAR + border, level l      (:800, :806)
 //   k_fast_cells   FAST-9/16 + cell-local NMS + threshold-7
 //                  fallback + raster-order compaction, one
@@ -95,7 +97,30 @@ struct ExtractArgs {
     int nlevels, ncells, list_entries, level_entries, nfeatures;
     int fast_th, fast_th_low;       // FAST thresholds (fastTh, 7), clamped
     int max_list_cap, max_level_cap;
+    // level 0 is read from the frame store (no k_pyr_level0 copy): frame width
+    // a multiple of 16, not the single-frame cascade (launch_extract)
+    int l0_direct;
 };
+
+// A level's padded origin and row stride for frame f of the pass (off and
+// stride: the level's LevelGeom entries).  Level 0 in direct mode is the
+// frame itself: its virtual padded origin, kEdge rows and columns in front of
+// the frame's first pixel, with row stride w.  Only addresses inside the
+// image may be read through it -- the border does not exist there.  With
+// kEdge == 16 and w % 16 == 0 the origin keeps the 16-byte alignment of the
+// padded level, and interior addressing (kEdge + y) * stride + kEdge + x is
+// unchanged.
+struct LevelSrc {
+    const uint8_t* base;
+    int stride;
+};
+static_assert(kEdge % 16 == 0, "the direct level 0 keeps the padded level's 16-byte alignment");
+__device__ __forceinline__ LevelSrc level_src(const ExtractArgs& a, int f, int level, long long off, int stride)
+{
+    if (a.l0_direct && level == 0)
+        return {a.frames + ((long long)(a.first_slot + f) * a.w * a.h - (long long)kEdge * a.w - kEdge), a.w};
+    return {a.pyr_raw + (size_t)f * a.frame_pyr_bytes + off, stride};
+}
 
 // The geometry tables (cells, levels, ...) are never written by a kernel:
 // read through the constant address space, a wave-uniform read is a scalar
@@ -275,7 +300,9 @@ __global__ __launch_bounds__(256) void k_pyr_resize(ExtractArgs a, int level)
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= wpr * nstrips) return;
     const int strip = idx / wpr, q = idx - strip * wpr, px0 = 4 * q;
-    const uint8_t* prev = a.pyr_raw + (size_t)f * a.frame_pyr_bytes + P.off + (size_t)kEdge * P.stride + kEdge;
+    // interior sources only (the level's own border recomputes its source)
+    const LevelSrc ps = level_src(a, f, level - 1, P.off, P.stride);
+    const uint8_t* prev = ps.base + (size_t)kEdge * ps.stride + kEdge;
     uint8_t* dst = a.pyr_raw + (size_t)f * a.frame_pyr_bytes + L.off;
     ResizeCol c[4];
     bool vec[4], on[4];
@@ -293,7 +320,7 @@ __global__ __launch_bounds__(256) void k_pyr_resize(ExtractArgs a, int level)
         uint32_t word = 0;
 #pragma unroll
         for (int b = 0; b < 4; b++)
-            if (on[b]) word |= (uint32_t)resize_pixel(prev, P.stride, c[b], r, vec[b]) << (8 * b);
+            if (on[b]) word |= (uint32_t)resize_pixel(prev, ps.stride, c[b], r, vec[b]) << (8 * b);
         if (strip * kPyrRows + rr < L.ph) *reinterpret_cast<uint32_t*>(dst + (size_t)py * L.stride + px0) = word;
     }
 }
@@ -310,6 +337,10 @@ struct ResizeLevel {
     long long off, poff;                 // level / parent offsets in a frame's pyramid
     int stride, pstride, w, h, pw, ph, ph_parent_h, nvec, span, strip_off, row_off, col_off;
     int packed;                          // every interior word's taps lie within 8 bytes (the packed form applies)
+    // the parent's level index and the left pad of its staged rows: kEdge
+    // (padded columns 0 .. kEdge + P.w), or 0 where the parent is the frame
+    // itself (level 0 in direct mode: columns 0 .. P.w of the image)
+    int plevel, ppad;
 };
 
 __global__ __launch_bounds__(256) void k_pyr_resize_lds(ExtractArgs a, ResizeLevel L, int pitch)
@@ -327,7 +358,11 @@ __global__ __launch_bounds__(256) void k_pyr_resize_lds(ExtractArgs a, ResizeLev
     if (tid < nrows) s_rows[tid] = a.res_rows[L.row_off + reflect101(py0 + tid - kEdge, L.h)];
     stage_to_lds<4>(s_cols, L.w, tid, (int)blockDim.x, [&](int x) { return a.res_cols[L.col_off + x]; });
     const int nsrc = min(L.span, L.ph_parent_h - lo);
-    const uint8_t* pbase = a.pyr_raw + (size_t)f * a.frame_pyr_bytes + L.poff + (size_t)(lo + kEdge) * L.pstride;
+    // parent row lo from its column kEdge - ppad on: the padded row's first
+    // byte, or the frame row's (there every staged byte lies inside the
+    // frame: rows lo .. lo + nsrc - 1 < P.h, columns 0 .. pitch - 1 = P.w - 1)
+    const LevelSrc ps = level_src(a, f, L.plevel, L.poff, L.pstride);
+    const uint8_t* pbase = ps.base + (size_t)(lo + kEdge) * ps.stride + (kEdge - L.ppad);
 #ifndef RES_NO_STAGE
     {
         // u / nch as a float product: (u + 1/2) / nch lies at least 1/(2 nch)
@@ -336,7 +371,7 @@ __global__ __launch_bounds__(256) void k_pyr_resize_lds(ExtractArgs a, ResizeLev
         const float inv = 1.0f / (float)nch;
         stage_to_lds<8>(s_dyn, nsrc * nch, tid, (int)blockDim.x, [&](int u) {
             const int r = (int)(((float)u + 0.5f) * inv), c = u - r * nch;
-            return *reinterpret_cast<const uint4*>(pbase + (size_t)r * L.pstride + 16 * c);
+            return *reinterpret_cast<const uint4*>(pbase + (size_t)r * ps.stride + 16 * c);
         });
     }
 #endif
@@ -380,7 +415,7 @@ __global__ __launch_bounds__(256) void k_pyr_resize_lds(ExtractArgs a, ResizeLev
 #pragma unroll
         for (int b = 0; b < 4; b++) {
             const ResizeCol c = s_cols[x0 + b];
-            ca[b] = kEdge + c.sx0;
+            ca[b] = L.ppad + c.sx0;
             wgt[b] = (uint32_t)(16 * c.a0) | (uint32_t)(16 * c.a1) << 16;
         }
         const int qa = ca[0] & ~3, sh = ca[0] & 3;
@@ -453,8 +488,8 @@ __global__ __launch_bounds__(256) void k_pyr_resize_lds(ExtractArgs a, ResizeLev
             if (px0 + b >= L.pw) continue;   // row padding: zero
             const int x = reflect101(px0 + b - kEdge, L.w);
             const ResizeCol c = s_cols[x];
-            const uint8_t* r0 = s_src + (R.sy0 - lo) * pitch + kEdge + c.sx0;
-            const uint8_t* r1 = s_src + (R.sy1 - lo) * pitch + kEdge + c.sx0;
+            const uint8_t* r0 = s_src + (R.sy0 - lo) * pitch + L.ppad + c.sx0;
+            const uint8_t* r1 = s_src + (R.sy1 - lo) * pitch + L.ppad + c.sx0;
             const int S0 = r0[0] * c.a0 + r0[1] * c.a1, S1 = r1[0] * c.a0 + r1[1] * c.a1;
             int v;
             if (x < L.nvec)
@@ -901,7 +936,18 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(kThrea
     const int hx = C.hx, hy = C.hy;
     const int nq16 = (sh + hx + 15) >> 4;               // 16-byte words loaded per row
     const int P = kP ? kP : 16 * nq16, nq = P >> 2;     // tile pitch, dwords per row
-    const uint8_t* src = a.pyr_raw + (size_t)f * a.frame_pyr_bytes + L.off + (size_t)(kEdge + C.ini_y) * L.stride + x_al;
+    // Level 0 may be the frame itself (level_src), where only image bytes
+    // exist.  A cell's ROI starts 13 pixels inside its level (ini_x, ini_y >=
+    // kEdge - 3) and ends at w - 13 (at most at w: ini_x + hx <= w and
+    // ini_y + hy <= h are checked with the geometry), so the first 16-byte
+    // word of a row starts at padded column x_al >= (kEdge + 13) & ~15 =
+    // kEdge, image column >= 0, and the last one ends at roundup16(kEdge +
+    // ini_x + hx) <= kEdge + w (w % 16 == 0), image column w; load_tile's
+    // rows lie in [ini_y, ini_y + hy).  The threshold-7 rescore reloads
+    // through the same load_tile.
+    const LevelSrc ls = level_src(a, f, C.level, L.off, L.stride);
+    const int lstride = ls.stride;
+    const uint8_t* src = ls.base + (size_t)(kEdge + C.ini_y) * lstride + x_al;
     uint32_t* tile32 = reinterpret_cast<uint32_t*>(tile);
     uint32_t* sm32 = reinterpret_cast<uint32_t*>(sm);
     uint32_t* kept = tile32;                                      // bit per tile byte (after scoring)
@@ -910,7 +956,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(kThrea
     // the cell's rows [w0, w0 + wh) into tile rows 0 .. wh - 1
     auto load_tile = [&](int w0, int wh) {
         uint4* t16 = reinterpret_cast<uint4*>(tile32);
-        const uint8_t* src_w = src + (size_t)w0 * L.stride;
+        const uint8_t* src_w = src + (size_t)w0 * lstride;
         const int n = wh * nq16;
         // i / nq16 as a float product: (i + 1/2) / nq16 is at least 1/(2 nq16)
         // from an integer and the product's error is < 2^-21 (i + 1) for
@@ -925,10 +971,10 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(kThrea
             const int r0 = row_of(i0), r1 = row_of(i1), r2 = row_of(i2), r3 = row_of(i3);
             const int c0 = i0 - r0 * nq16, c1 = i1 - r1 * nq16, c2 = i2 - r2 * nq16, c3 = i3 - r3 * nq16;
             // 32-bit offsets from the uniform tile origin (saddr loads)
-            const uint4 v0 = *reinterpret_cast<const uint4*>(src_w + (uint32_t)(r0 * L.stride + 16 * c0));
-            const uint4 v1 = *reinterpret_cast<const uint4*>(src_w + (uint32_t)(r1 * L.stride + 16 * c1));
-            const uint4 v2 = *reinterpret_cast<const uint4*>(src_w + (uint32_t)(r2 * L.stride + 16 * c2));
-            const uint4 v3 = *reinterpret_cast<const uint4*>(src_w + (uint32_t)(r3 * L.stride + 16 * c3));
+            const uint4 v0 = *reinterpret_cast<const uint4*>(src_w + (uint32_t)(r0 * lstride + 16 * c0));
+            const uint4 v1 = *reinterpret_cast<const uint4*>(src_w + (uint32_t)(r1 * lstride + 16 * c1));
+            const uint4 v2 = *reinterpret_cast<const uint4*>(src_w + (uint32_t)(r2 * lstride + 16 * c2));
+            const uint4 v3 = *reinterpret_cast<const uint4*>(src_w + (uint32_t)(r3 * lstride + 16 * c3));
             t16[r0 * (P >> 4) + c0] = v0;
             t16[r1 * (P >> 4) + c1] = v1;
             t16[r2 * (P >> 4) + c2] = v2;
@@ -1397,8 +1443,11 @@ __global__ __launch_bounds__(256) void k_harris_cells(ExtractArgs a)
     if (!C.valid) return;
     const int n = min(a.cell_count[(size_t)f * a.ncells + cell], C.list_cap);
     const LevelGeom L = cget(a.levels, C.level);
-    const int stride = L.stride;
-    const uint8_t* img = a.pyr_raw + (size_t)f * a.frame_pyr_bytes + L.off + (size_t)kEdge * stride + kEdge;
+    // 9x9 windows around corners at least 16 pixels inside the level: image
+    // pixels only (level 0 may be the frame itself, level_src)
+    const LevelSrc ls = level_src(a, f, C.level, L.off, L.stride);
+    const int stride = ls.stride;
+    const uint8_t* img = ls.base + (size_t)kEdge * stride + kEdge;
     const uint32_t* src = a.cell_lists + (size_t)f * a.list_entries + C.list_off;
     uint64_t* dst = a.cell_keys64 + (size_t)f * a.list_entries + C.list_off;
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
@@ -1727,18 +1776,62 @@ __device__ __forceinline__ void wave_lds_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// The window of a level-0 keypoint near the image edge when level 0 is the
+// frame itself (level_src: no border exists there).  The window's first byte
+// is padded position (x0, y0); every byte is fetched from the image position
+// BORDER_REFLECT_101 maps it to, so the staged bytes equal the padded copy's
+// and every address lies inside the frame -- also for the window bytes that
+// the blur never uses.  Keypoints are at least kEdge inside the level, so the
+// window lies within the padded level's kEdge border and one reflection per
+// index is enough (the clamps only keep a degenerate tiny level in bounds).
+// x0, kEdge and lw are multiples of 4, so a window dword lies wholly inside
+// the image columns or wholly outside.  An outside dword at image columns
+// c .. c + 3 is the byte-reversed dword at columns -c - 3 .. -c (c < 0) or
+// 2 lw - 5 - c .. 2 lw - 2 - c (c >= lw): one (unaligned) dword load each,
+// no branch per item, all of a lane's loads in flight together as in the
+// common path.
+__device__ __forceinline__ void describe_stage_reflect(const uint8_t* lev, int stride, int lw, int lh, int x0, int y0,
+                                                       uint32_t* w32, int hl)
+{
+    constexpr int n = kWinRows * kWinDw, nld = (n + 31) / 32;
+    const uint8_t* img = lev + (long long)kEdge * stride + kEdge;   // the frame's first pixel
+    uint32_t v[nld];
+#pragma unroll
+    for (int k = 0; k < nld; k++) {
+        const int i = min(hl + 32 * k, n - 1), r = i / kWinDw, c = x0 - kEdge + 4 * (i - r * kWinDw);
+        int y = y0 - kEdge + r;
+        y = y < 0 ? -y : (y >= lh ? 2 * lh - 2 - y : y);
+        y = min(max(y, 0), lh - 1);
+        int col = c < 0 ? -c - 3 : (c >= lw ? 2 * lw - 5 - c : c);
+        col = min(max(col, 0), lw - 4);
+        uint32_t d;
+        __builtin_memcpy(&d, img + (long long)y * stride + col, 4);
+        v[k] = (c < 0 || c >= lw) ? __builtin_bswap32(d) : d;
+    }
+#pragma unroll
+    for (int k = 0; k < nld; k++) w32[min(hl + 32 * k, n - 1)] = v[k];
+}
+
 // Stages the raw window of the keypoint at padded level position (X, Y) into
 // win (kWinRows * kBrPitch bytes behind the keypoint's kWinPad), lane hl of
 // 32; lev: the padded level.  All loads in flight together; 32-bit offsets
 // from the window's first row, (row, dword) stepped per load.  Returns the
 // window centre's byte offset in win.
-__device__ __forceinline__ int describe_stage_window(const uint8_t* lev, uint32_t stride, int X, int Y, uint8_t* win,
-                                                     int hl)
+// direct: lev is a frame's virtual padded origin (level 0 read from the
+// frame store), lw x lh the level's size.  The loads below then apply when
+// the whole window (kWinRows rows x kBrPitch bytes) lies inside the image;
+// other windows go through describe_stage_reflect.
+__device__ __forceinline__ int describe_stage_window(const uint8_t* lev, uint32_t stride, bool direct, int lw, int lh,
+                                                     int X, int Y, uint8_t* win, int hl)
 {
     constexpr int n = kWinRows * kWinDw, nld = (n + 31) / 32;
     const int x0 = (X - kWinR) & ~3;
-    const uint8_t* r0 = lev + (long long)(Y - kWinR) * stride + x0;
     uint32_t* w32 = reinterpret_cast<uint32_t*>(win);
+    if (direct && (Y - kWinR < kEdge || Y + kWinR >= kEdge + lh || x0 < kEdge || x0 + kBrPitch > kEdge + lw)) {
+        describe_stage_reflect(lev, (int)stride, lw, lh, x0, Y - kWinR, w32, hl);
+        return kWinR * kBrPitch + (X - x0);
+    }
+    const uint8_t* r0 = lev + (long long)(Y - kWinR) * stride + x0;
     uint32_t v[nld];
     int r = hl / kWinDw, q = hl - (hl / kWinDw) * kWinDw;
 #pragma unroll
@@ -1981,8 +2074,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k
     // the raw window; ic / br: its centre, the patch centre of IC_Angle now
     // and of the blurred patch after describe_blur_window
     uint8_t* win = s_patch[slot] + kWinPad;
-    const uint8_t* ic =
-        win + describe_stage_window(a.pyr_raw + (size_t)f * a.frame_pyr_bytes + lev_off, (uint32_t)lev_stride, X, Y, win, hl);
+    const LevelSrc ls = level_src(a, f, level, lev_off, lev_stride);
+    const uint8_t* ic = win + describe_stage_window(ls.base, (uint32_t)ls.stride, a.l0_direct && level == 0, lev_w,
+                                                    lev_h, X, Y, win, hl);
     const uint8_t* br = ic;
     wave_lds_sync();
     // IC_Angle on the unblurred level (src/ORBextractor.cc:124-151): lane u
@@ -2103,13 +2197,15 @@ namespace orbx {
 
 // Test hook: k_describe's window staging and patch blur for one position of
 // one level, both halves of the wave on the same keypoint; the blurred 37x37
-// patch goes to out, row-major.
-__global__ __launch_bounds__(64) void k_debug_describe_patch(const uint8_t* lev, LevelGeom L, int X, int Y, uint8_t* out)
+// patch goes to out, row-major.  lev / stride / direct: the level as
+// k_describe sees it (level_src).
+__global__ __launch_bounds__(64) void k_debug_describe_patch(const uint8_t* lev, int stride, int direct, LevelGeom L,
+                                                             int X, int Y, uint8_t* out)
 {
     __shared__ __attribute__((aligned(16))) uint8_t s_patch[2][kDescWaveBytes];
     const int lane = threadIdx.x, half = lane >> 5, hl = lane & 31;
     uint8_t* win = s_patch[half] + kWinPad;
-    const int centre = describe_stage_window(lev, (uint32_t)L.stride, X, Y, win, hl);
+    const int centre = describe_stage_window(lev, (uint32_t)stride, direct != 0, L.w, L.h, X, Y, win, hl);
     wave_lds_sync();
     describe_blur_window(win, X, Y, L.w, L.h, L.nvec_blur, hl);
     if (half == 0)
@@ -2119,10 +2215,48 @@ __global__ __launch_bounds__(64) void k_debug_describe_patch(const uint8_t* lev,
         }
 }
 
+// k_pyr_level0 over nb frames on stream st (x: levels, frames, first_slot,
+// pyr_raw, w, h).
+static void launch_level0(const Geometry& g, const ExtractArgs& x, int nb, hipStream_t st)
+{
+    const LevelGeom& L = g.levels[0];
+    // interior 16-byte words: two aligned source loads cover them
+    // (frames rows are 16-byte aligned when w % 16 == 0)
+    const int qpr = L.stride / 16;
+    int q_lo = (kEdge + 15) / 16, q_hi = (L.w + kEdge + kPyr0Shift - 32) / 16;
+    q_hi = std::min(q_hi, qpr - 1);
+    const int nint = (g.w % 16 == 0 && q_hi >= q_lo) ? q_hi - q_lo + 1 : 0;
+    if (nint == 0) q_lo = 0;
+    const int items = nint * ((L.ph + kPyrRows - 1) / kPyrRows) + (qpr - nint) * L.ph;
+    hipLaunchKernelGGL(k_pyr_level0, dim3((items + 255) / 256, nb), dim3(256), 0, st, x, q_lo, nint);
+}
+
+// The padded level 0 of one slot, from the slot's current frame, on the
+// context stream.  Extraction in direct mode leaves the area unwritten, so
+// the readers of the padded level (orbx_dev_read_level, the whole-level blur)
+// call this first; the copy depends on the frame alone, so it is repeated
+// rather than tracked per slot.
+int launch_level0_slot(orbx_ctx* ctx, int slot)
+{
+    ExtractArgs a = {};
+    a.levels = ctx->dgeom.levels;
+    a.frames = ctx->frames;
+    a.first_slot = slot;
+    a.pyr_raw = ctx->pyr_raw + (size_t)slot * ctx->geom.frame_pyr_bytes;
+    a.frame_pyr_bytes = ctx->geom.frame_pyr_bytes;
+    a.w = ctx->geom.w;
+    a.h = ctx->geom.h;
+    launch_level0(ctx->geom, a, 1, ctx->stream);
+    if (hipGetLastError() != hipSuccess) return ORBX_ERR_HIP;
+    return ORBX_OK;
+}
+
 // The whole-level blur of one slot's raw pyramid into the one-frame
 // ctx->pyr_blur, on the context stream (orbx_dev_read_level's blurred levels).
 int launch_blur_slot(orbx_ctx* ctx, int slot)
 {
+    const int r0 = launch_level0_slot(ctx, slot);   // k_blur reads the padded level 0
+    if (r0 != ORBX_OK) return r0;
     ExtractArgs a = {};
     a.levels = ctx->dgeom.levels;
     a.pyr_raw = ctx->pyr_raw + (size_t)slot * ctx->geom.frame_pyr_bytes;
@@ -2148,14 +2282,30 @@ extern "C" int orbx_debug_describe_patch(orbx_ctx* ctx, int slot, int level, int
     uint8_t* d = nullptr;
     if (hipDeviceSynchronize() != hipSuccess) return ORBX_ERR_HIP;   // every part stream's pyramid
     if (hipMalloc(&d, kBrRows * kBrRows) != hipSuccess) return ORBX_ERR_NOMEM;
-    const uint8_t* lev = ctx->pyr_raw + (size_t)slot * ctx->geom.frame_pyr_bytes + L.off;
-    hipLaunchKernelGGL(k_debug_describe_patch, dim3(1), dim3(64), 0, ctx->stream, lev, L, kEdge + x, kEdge + y, d);
+    // the level as k_describe sees it: level 0 of frames that qualify for the
+    // direct mode is the slot's frame (its virtual padded origin, level_src);
+    // the padded level 0 of such a slot may never have been written, and
+    // where the cascade wrote it, it holds the same bytes
+    const bool direct = level == 0 && kEdge == 16 && ctx->geom.w % 16 == 0;
+    const long long fw = ctx->geom.w, fh = ctx->geom.h;
+    const uint8_t* lev = direct ? ctx->frames + ((long long)slot * fw * fh - (long long)kEdge * fw - kEdge)
+                                : ctx->pyr_raw + (size_t)slot * ctx->geom.frame_pyr_bytes + L.off;
+    hipLaunchKernelGGL(k_debug_describe_patch, dim3(1), dim3(64), 0, ctx->stream, lev, direct ? (int)fw : L.stride,
+                       direct ? 1 : 0, L, kEdge + x, kEdge + y, d);
     int r = ORBX_OK;
     if (hipStreamSynchronize(ctx->stream) != hipSuccess ||
         hipMemcpy(out, d, kBrRows * kBrRows, hipMemcpyDeviceToHost) != hipSuccess)
         r = ORBX_ERR_HIP;
     (void)hipFree(d);
     return r;
+}
+
+/* Diagnostics (not in include/orbx.h): 1 when the last extraction launched on
+ * the context read level 0 from the frame store (no k_pyr_level0 copy), else 0. */
+extern "C" int orbx_debug_level0_direct(orbx_ctx* ctx)
+{
+    if (!ctx) return ORBX_ERR_ARG;
+    return ctx->last_l0_direct ? 1 : 0;
 }
 
 namespace orbx {
@@ -2214,6 +2364,13 @@ int launch_extract(orbx_ctx* ctx, int first, int count, const MatchSpec* m)
     a.fast_th_low = 7;
     a.max_list_cap = g.max_list_cap;
     a.max_level_cap = g.max_level_cap;
+    // Level 0 straight from the frame store (level_src), without the padded
+    // copy: rows of w % 16 == 0 bytes keep the kernels' 16-byte loads
+    // aligned; the single-frame cascade writes level 0 itself.  A slot's frame
+    // is then read until its k_describe ends: whatever overwrites frames is
+    // ordered after the whole queued extraction.
+    a.l0_direct = (kEdge == 16 && g.w % 16 == 0 && !(ctx->single_frame && g.cascade_bands > 0)) ? 1 : 0;
+    ctx->last_l0_direct = a.l0_direct != 0;
 
     // The pyramid stages over nb frames on stream st.
     auto run_pyramid = [&](const ExtractArgs& x, int nb, hipStream_t st) {
@@ -2238,24 +2395,18 @@ int launch_extract(orbx_ctx* ctx, int first, int count, const MatchSpec* m)
             timer_end(ctx, "resize", st);
             return;
         }
-        timer_begin(ctx, "pyr0", st);
-        {
-            const LevelGeom& L = g.levels[0];
-            // interior 16-byte words: two aligned source loads cover them
-            // (frames rows are 16-byte aligned when w % 16 == 0)
-            const int qpr = L.stride / 16;
-            int q_lo = (kEdge + 15) / 16, q_hi = (L.w + kEdge + kPyr0Shift - 32) / 16;
-            q_hi = std::min(q_hi, qpr - 1);
-            const int nint = (g.w % 16 == 0 && q_hi >= q_lo) ? q_hi - q_lo + 1 : 0;
-            if (nint == 0) q_lo = 0;
-            const int items = nint * ((L.ph + kPyrRows - 1) / kPyrRows) + (qpr - nint) * L.ph;
-            hipLaunchKernelGGL(k_pyr_level0, dim3((items + 255) / 256, nb), dim3(256), 0, st, x, q_lo, nint);
+        if (!x.l0_direct) {   // direct mode: no launch, and the "pyr0" timer reports none
+            timer_begin(ctx, "pyr0", st);
+            launch_level0(g, x, nb, st);
+            timer_end(ctx, "pyr0", st);
         }
-        timer_end(ctx, "pyr0", st);
         for (int l = 1; l < g.nlevels; l++) {
             const LevelGeom& L = g.levels[l];
             const LevelGeom& P = g.levels[l - 1];
-            const int pitch = (kEdge + P.w + 15) & ~15;
+            // staged parent rows: the padded row from its first byte, or the
+            // frame's row (no left pad) when the parent is the direct level 0
+            const int ppad = (l == 1 && x.l0_direct) ? 0 : kEdge;
+            const int pitch = (ppad + P.w + 15) & ~15;
             const size_t lds = (size_t)L.res_span * pitch + (size_t)L.w * sizeof(ResizeCol);
             timer_begin(ctx, "resize", st);
             if (lds <= kResizeLds) {
@@ -2267,7 +2418,7 @@ int launch_extract(orbx_ctx* ctx, int first, int count, const MatchSpec* m)
                 for (int x0 = 0; x0 + 3 < L.w; x0 += 4)
                     if (g.res_cols[L.res_col_off + x0 + 3].sx0 - g.res_cols[L.res_col_off + x0].sx0 > 6) packed = 0;
                 const ResizeLevel rl{L.off, P.off, L.stride, P.stride, L.w, L.h, L.pw, L.ph, P.h, L.nvec_resize,
-                                     L.res_span, L.res_strip_off, L.res_row_off, L.res_col_off, packed};
+                                     L.res_span, L.res_strip_off, L.res_row_off, L.res_col_off, packed, l - 1, ppad};
                 for (int rep = 0; rep < kDiagRepeat[0]; rep++)
                     hipLaunchKernelGGL(k_pyr_resize_lds, dim3((L.ph + kResRows - 1) / kResRows, nb), dim3(threads), lds,
                                        st, x, rl, pitch);

@@ -4,7 +4,10 @@
 //   frames      slots x (w*h)                  input mono8, dense rows
 //   pyr_raw     slots x frame_pyr_bytes        padded levels (w_l+32)x(h_l+32),
 //                                              rows padded to 64 B; level l at
-//                                              LevelGeom::off.  Unblurred.
+//                                              LevelGeom::off.  Unblurred.  Level 0
+//                                              is written on demand only where the
+//                                              kernels read it from `frames`
+//                                              (w % 16 == 0; launch_level0_slot)
 //   pyr_blur    1 x frame_pyr_bytes            same layout, one frame; interior
 //                                              blurred, border = unblurred border.
 //                                              Not on the extraction path (k_describe
@@ -281,6 +284,7 @@ struct orbx_ctx {
     int cap_cascade = 0;
     int blur_tiles_n = 0;
     int last_first = 0, last_count = 0;   // batch of the most recent extract
+    bool last_l0_direct = false;          // the last launch_extract read level 0 from the frame store
     // Frame::ComputeImageBounds of the slots' keypoints (orbx_dev_set_image_bounds;
     // has_bounds 0: 0..w x 0..h, the undistorted case) for the device matchers
     int has_bounds = 0;
@@ -356,6 +360,10 @@ struct MatchSpec {
 };
 int launch_extract(orbx_ctx* ctx, int first, int count, const MatchSpec* m = nullptr);
 int launch_blur_slot(orbx_ctx* ctx, int slot);   // k_blur of one slot's raw pyramid into the one-frame pyr_blur
+// k_pyr_level0 of one slot's current frame into the slot's level-0 area, on
+// the context stream: the extraction path reads level 0 from the frame store
+// where it can, so whoever reads the padded level 0 builds it first
+int launch_level0_slot(orbx_ctx* ctx, int slot);
 // timing helpers (orbx_api.cpp)
 void timer_begin(orbx_ctx* ctx, const char* name, hipStream_t st = nullptr);
 void timer_end(orbx_ctx* ctx, const char* name, hipStream_t st = nullptr);
