@@ -1814,41 +1814,50 @@ __device__ __forceinline__ void describe_stage_reflect(const uint8_t* lev, int s
 
 // Stages the raw window of the keypoint at padded level position (X, Y) into
 // win (kWinRows * kBrPitch bytes behind the keypoint's kWinPad), lane hl of
-// 32; lev: the padded level.  All loads in flight together; 32-bit offsets
-// from the window's first row, (row, dword) stepped per load.  Returns the
-// window centre's byte offset in win.
+// 32; lev: the padded level.  A row is kWinPieces 16-byte pieces and win's
+// rows are contiguous, so piece p (row p / 3) goes to win + 16 p: lane hl
+// takes pieces hl, hl + 32, ... with 16-byte loads (the window origin is
+// 4-byte aligned only) and 16-byte LDS stores at a constant distance; the one
+// piece left over after kStageRounds rounds is loaded by every lane and
+// stored by lane 0.  All loads in flight together; 32-bit offsets from the
+// window's first row.  Returns the window centre's byte offset in win.
 // direct: lev is a frame's virtual padded origin (level 0 read from the
 // frame store), lw x lh the level's size.  The loads below then apply when
 // the whole window (kWinRows rows x kBrPitch bytes) lies inside the image;
 // other windows go through describe_stage_reflect.
+typedef uint32_t stage_piece_t __attribute__((ext_vector_type(4), aligned(4)));
+constexpr int kWinPieces = kBrPitch / 16;            // 3 per row
+constexpr int kStagePieces = kWinRows * kWinPieces;   // 129
+constexpr int kStageRounds = kStagePieces / 32;       // 4 full rounds of 32 lanes
+static_assert(kBrPitch % 16 == 0 && kWinPad % 16 == 0 && kDescWaveBytes % 16 == 0,
+              "every 16-byte piece of a window is 16-byte aligned in LDS");
+static_assert(kStagePieces - 32 * kStageRounds == 1, "one piece is left over after the full rounds");
+static_assert(kStagePieces < 512, "p / 3 == p * 171 >> 9 holds below 512");
 __device__ __forceinline__ int describe_stage_window(const uint8_t* lev, uint32_t stride, bool direct, int lw, int lh,
                                                      int X, int Y, uint8_t* win, int hl)
 {
-    constexpr int n = kWinRows * kWinDw, nld = (n + 31) / 32;
     const int x0 = (X - kWinR) & ~3;
-    uint32_t* w32 = reinterpret_cast<uint32_t*>(win);
     if (direct && (Y - kWinR < kEdge || Y + kWinR >= kEdge + lh || x0 < kEdge || x0 + kBrPitch > kEdge + lw)) {
-        describe_stage_reflect(lev, (int)stride, lw, lh, x0, Y - kWinR, w32, hl);
+        describe_stage_reflect(lev, (int)stride, lw, lh, x0, Y - kWinR, reinterpret_cast<uint32_t*>(win), hl);
         return kWinR * kBrPitch + (X - x0);
     }
     const uint8_t* r0 = lev + (long long)(Y - kWinR) * stride + x0;
-    uint32_t v[nld];
-    int r = hl / kWinDw, q = hl - (hl / kWinDw) * kWinDw;
+    // piece p at row r = p / 3 lies at r * stride + 16 (p - 3 r) = r * (stride - kBrPitch) + 16 p
+    const uint32_t skip = stride - kBrPitch;
+    stage_piece_t v[kStageRounds + 1];
 #pragma unroll
-    for (int k = 0; k < nld; k++) {
-        const bool in = hl + 32 * k < n;
-        // lanes past the window re-load (and below re-store) its last dword
-        v[k] = *reinterpret_cast<const uint32_t*>(
-            r0 + (in ? (uint32_t)r * stride + 4u * (uint32_t)q : (uint32_t)(kWinRows - 1) * stride + 4u * (kWinDw - 1)));
-        r += 32 / kWinDw;
-        q += 32 % kWinDw;
-        if (q >= kWinDw) {
-            q -= kWinDw;
-            r++;
-        }
+    for (int k = 0; k < kStageRounds; k++) {
+        const uint32_t p = (uint32_t)hl + 32u * k, r = (p * 171u) >> 9;
+        v[k] = *reinterpret_cast<const stage_piece_t*>(r0 + (__umul24(r, skip) + 16u * p));   // strides are < 2^24
     }
+    v[kStageRounds] = *reinterpret_cast<const stage_piece_t*>(
+        r0 + ((uint32_t)(kWinRows - 1) * stride + 16u * (kWinPieces - 1)));
+    uint4* w128 = reinterpret_cast<uint4*>(win);
 #pragma unroll
-    for (int k = 0; k < nld; k++) w32[min(hl + 32 * k, n - 1)] = v[k];
+    for (int k = 0; k < kStageRounds; k++) w128[hl + 32 * k] = uint4{v[k].x, v[k].y, v[k].z, v[k].w};
+    if (hl == 0)
+        w128[kStagePieces - 1] =
+            uint4{v[kStageRounds].x, v[kStageRounds].y, v[kStageRounds].z, v[kStageRounds].w};
     return kWinR * kBrPitch + (X - x0);
 }
 
@@ -1951,10 +1960,11 @@ __device__ inline int half_wave_sum(int v)
     return (threadIdx.x & 32) ? hi : lo;
 }
 
-// Two keypoints per wave, one per 32-lane half: every per-keypoint scalar
-// step (fastAtan2, the correctly rounded sin/cos) is shared by two
-// keypoints per instruction, and the pattern's 256 tests map onto 8 rounds
-// of 32 lanes (ballot halves = 32 descriptor bits each).
+// Two keypoints per wave, one per 32-lane half, eight per workgroup: the
+// per-keypoint scalar steps (fastAtan2, the correctly rounded sin/cos) run
+// once per workgroup, one keypoint per lane of one wave, and the pattern's
+// 256 tests map onto 8 rounds of 32 lanes (ballot halves = 32 descriptor
+// bits each).
 // GET_VALUE's sample coordinates (src/ORBextractor.cc:165-167): row
 // x*b + y*a and column x*a - y*b.  kFma: as GCC contracts them on an FMA host
 // (-O3 -march=native, CMakeLists.txt:12-13): fma(x, b, y*a), fma(x, a, -(y*b)).
@@ -1995,20 +2005,30 @@ __device__ inline void orb_sample_addr2(orbx_f2 px, orbx_f2 py, float sa, float 
     a2 = (uint32_t)ad.y;
 }
 
+// fastAtan2's angle and its correctly rounded sin / cos, one per keypoint
+struct DescTrig {
+    float angle, sa, ca;
+};
+
 // 5 waves per SIMD: the register allocator otherwise spends past 128 VGPRs
-// on hoisted window reads (the kernel is VALU-bound; 90 VGPRs, no spills)
+// on hoisted window reads (the kernel is VALU-bound; 88 VGPRs, no spills)
 template <bool kFma>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k_describe(ExtractArgs a, int nframes)
 {
     __shared__ __attribute__((aligned(16))) uint8_t s_patch[2 * kWaves][kDescWaveBytes];
+    __shared__ int2 s_mom[2 * kWaves];       // m01, m10 per keypoint of the workgroup
+    __shared__ DescTrig s_trig[2 * kWaves];
     // XCD-aware order (xcd_block): a frame's keypoint patches, which overlap,
     // are fetched into one XCD's L2
     const XcdBlock xb = xcd_block();
     const int f = xb.frame, chunk = xb.chunk;
     if (f >= nframes) return;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, half = lane >> 5, hl = lane & 31;
+    // wv is wave-uniform: with it in a scalar register the search for the two
+    // keypoints' levels below runs on the scalar unit
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & (kWaves - 1);
+    const int half = lane >> 5, hl = lane & 31;
     const int slot = wv * 2 + half;
-    const int k = chunk * (2 * kWaves) + slot;
+    const int k0 = chunk * (2 * kWaves) + wv * 2, k = k0 + half;
     // tables needed later, loaded up front (independent of the keypoint):
     // umax[0..15] one entry per lane, this lane's 8 pattern pairs
     const int umax_l = a.umax[min(lane, kHalfPatch)];
@@ -2023,15 +2043,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k
     const int stride_l = a.levels[ll].stride, loff_l = a.levels[ll].level_off;
     const int w_l = a.levels[ll].w, h_l = a.levels[ll].h, nvec_l = a.levels[ll].nvec_blur;
     const float scale_l = a.levels[ll].scale, psize_l = a.levels[ll].patch_size;
-    int total = 0, level = -1, local = 0;
+    // keypoints k0 (lower half) and k0 + 1 (upper half): level and index in it
+    int total = 0, level0 = -1, local0 = 0, level1 = -1, local1 = 0;
     for (int l = 0; l < a.nlevels; l++) {
         const int c = __builtin_amdgcn_readlane(cnt_l, l);
-        if (level < 0 && k < total + c) {
-            level = l;
-            local = k - total;
+        if (level0 < 0 && k0 < total + c) {
+            level0 = l;
+            local0 = k0 - total;
+        }
+        if (level1 < 0 && k0 + 1 < total + c) {
+            level1 = l;
+            local1 = k0 + 1 - total;
         }
         total += c;
     }
+    int level = half ? level1 : level0, local = half ? local1 : local0;
     if (k == 0 && lane == 0) {
         a.out_n[a.first_slot + f] = total;
         if (a.host_out) {   // every earlier kernel's error flags are final here
@@ -2039,73 +2065,97 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k
             reinterpret_cast<int32_t*>(a.host_out)[1] = *a.error_flags;
         }
     }
-    // a wave keeps running while either half has a keypoint (DPP/ballot need
-    // the whole wave); an empty half works on level 0 / key 0 and stores nothing
+    // no keypoint in the whole workgroup (block-uniform: every wave computes
+    // the same total): nothing to do, and no barrier is reached
+    if (chunk * (2 * kWaves) >= total) return;
+    // a wave works while either half has a keypoint (DPP/ballot need the
+    // whole wave); an empty half works on level 0 / key 0 and stores nothing.
+    // A wave without a keypoint only takes part in the block barriers.
     const bool valid = level >= 0;
-    if (!__any(valid)) return;
+    const bool wave_on = level0 >= 0;   // k0 + 1 has a keypoint only if k0 has
     if (!valid) {
         level = 0;
         local = 0;
     }
-    // this half's level data, read back from lane `level`
-    const int lv0 = __builtin_amdgcn_readlane(level, 0), lv1 = __builtin_amdgcn_readlane(level, 32);
-    auto pick = [&](int v) {
-        const int a0 = __builtin_amdgcn_readlane(v, lv0), a1 = __builtin_amdgcn_readlane(v, lv1);
-        return half ? a1 : a0;
-    };
-    const long long lev_off = (long long)(((unsigned long long)(uint32_t)pick((int)(off_l >> 32)) << 32) |
-                                          (uint32_t)pick((int)off_l));
-    const int lev_stride = pick(stride_l), lev_loff = pick(loff_l);
-    const int lev_w = pick(w_l), lev_h = pick(h_l), lev_nvec = pick(nvec_l);
-    const float lev_scale = __int_as_float(pick(__float_as_int(scale_l)));
-    const float lev_psize = __int_as_float(pick(__float_as_int(psize_l)));
-    uint32_t e;
-    float response;
-    if (a.harris) {
-        const uint64_t e64 = a.level_keys64[(size_t)f * a.level_entries + lev_loff + local];
-        e = (uint32_t)e64;
-        response = harris_response((uint32_t)(e64 >> 32));
-    } else {
-        e = a.level_keys[(size_t)f * a.level_entries + lev_loff + local];
-        response = (float)(e >> 24);   // FAST score
-    }
-    const int y = (int)((e >> 12) & 0xFFF), x = (int)(e & 0xFFF);
-    const int X = kEdge + (valid ? x : kHalfPatch + 8), Y = kEdge + (valid ? y : kHalfPatch + 8);
-    // the raw window; ic / br: its centre, the patch centre of IC_Angle now
-    // and of the blurred patch after describe_blur_window
+    int x = 0, y = 0, X = 0, Y = 0, lev_w = 0, lev_h = 0, lev_nvec = 0;
+    float lev_scale = 0.f, lev_psize = 0.f, response = 0.f;
     uint8_t* win = s_patch[slot] + kWinPad;
-    const LevelSrc ls = level_src(a, f, level, lev_off, lev_stride);
-    const uint8_t* ic = win + describe_stage_window(ls.base, (uint32_t)ls.stride, a.l0_direct && level == 0, lev_w,
-                                                    lev_h, X, Y, win, hl);
-    const uint8_t* br = ic;
-    wave_lds_sync();
-    // IC_Angle on the unblurred level (src/ORBextractor.cc:124-151): lane u
-    // of the half takes column u - 15 over all rows of the circular patch
+    const uint8_t* br = win;
     int m01 = 0, m10 = 0;
-    // umax read back from the lanes with readlane: no table loads in the loop
-    if (hl < kIcRows) {
-        const int u = hl - kHalfPatch;
-        m10 = u * ic[u];
+    if (wave_on) {
+        // this half's level data, read back from lane `level` (one
+        // ds_bpermute_b32 per value, no LDS memory involved)
+        auto pick = [&](int v) { return __builtin_amdgcn_ds_bpermute(level << 2, v); };
+        const long long lev_off = (long long)(((unsigned long long)(uint32_t)pick((int)(off_l >> 32)) << 32) |
+                                              (uint32_t)pick((int)off_l));
+        const int lev_stride = pick(stride_l), lev_loff = pick(loff_l);
+        lev_w = pick(w_l);
+        lev_h = pick(h_l);
+        lev_nvec = pick(nvec_l);
+        lev_scale = __int_as_float(pick(__float_as_int(scale_l)));
+        lev_psize = __int_as_float(pick(__float_as_int(psize_l)));
+        uint32_t e;
+        if (a.harris) {
+            const uint64_t e64 = a.level_keys64[(size_t)f * a.level_entries + lev_loff + local];
+            e = (uint32_t)e64;
+            response = harris_response((uint32_t)(e64 >> 32));
+        } else {
+            e = a.level_keys[(size_t)f * a.level_entries + lev_loff + local];
+            response = (float)(e >> 24);   // FAST score
+        }
+        y = (int)((e >> 12) & 0xFFF);
+        x = (int)(e & 0xFFF);
+        X = kEdge + (valid ? x : kHalfPatch + 8);
+        Y = kEdge + (valid ? y : kHalfPatch + 8);
+        // the raw window; ic / br: its centre, the patch centre of IC_Angle now
+        // and of the blurred patch after describe_blur_window
+        const LevelSrc ls = level_src(a, f, level, lev_off, lev_stride);
+        const uint8_t* ic = win + describe_stage_window(ls.base, (uint32_t)ls.stride, a.l0_direct && level == 0, lev_w,
+                                                        lev_h, X, Y, win, hl);
+        br = ic;
+        wave_lds_sync();
+        // IC_Angle on the unblurred level (src/ORBextractor.cc:124-151): lane u
+        // of the half takes column u - 15 over all rows of the circular patch
+        // umax read back from the lanes with readlane: no table loads in the loop
+        if (hl < kIcRows) {
+            const int u = hl - kHalfPatch;
+            m10 = u * ic[u];
 #pragma unroll
-        for (int v = 1; v <= kHalfPatch; v++) {
-            const int d = __builtin_amdgcn_readlane(umax_l, v);
-            if (u >= -d && u <= d) {
-                const int vp = ic[u + v * kBrPitch], vm = ic[u - v * kBrPitch];
-                m01 += v * (vp - vm);
-                m10 += u * (vp + vm);
+            for (int v = 1; v <= kHalfPatch; v++) {
+                const int d = __builtin_amdgcn_readlane(umax_l, v);
+                if (u >= -d && u <= d) {
+                    const int vp = ic[u + v * kBrPitch], vm = ic[u - v * kBrPitch];
+                    m01 += v * (vp - vm);
+                    m10 += u * (vp + vm);
+                }
             }
         }
+        m01 = half_wave_sum(m01);
+        m10 = half_wave_sum(m10);
     }
-    m01 = half_wave_sum(m01);
-    m10 = half_wave_sum(m10);
-    const float angle = fast_atan2_deg((float)m01, (float)m10);
+    // fastAtan2 and the correctly rounded sin/cos are one value per keypoint:
+    // one wave of the workgroup (a different one from block to block, so the
+    // work is spread over the SIMDs) computes them for all eight keypoints,
+    // one per lane, between two block barriers.  The blur does not depend on
+    // the angle and runs between the barriers too: the other waves blur while
+    // the chosen wave does the trigonometry first.
+    if (hl == 0) s_mom[slot] = int2{m01, m10};
+    __syncthreads();
+    if (wv == ((chunk + f) & (kWaves - 1)) && lane < 2 * kWaves) {
+        const int2 m = s_mom[lane];
+        const float ang = fast_atan2_deg((float)m.x, (float)m.y);
+        const float factorPI = (float)(M_PI / 180.f);
+        float s, c;
+        cr_sincosf(__fmul_rn(ang, factorPI), &s, &c);
+        s_trig[lane] = DescTrig{ang, s, c};
+    }
     // the blurred patch overwrites the raw window, behind a wave_lds_sync
     // that follows every lane's IC_Angle reads
-    describe_blur_window(win, X, Y, lev_w, lev_h, lev_nvec, hl);
+    if (wave_on) describe_blur_window(win, X, Y, lev_w, lev_h, lev_nvec, hl);
+    __syncthreads();
+    if (!wave_on) return;
+    const float angle = s_trig[slot].angle, sa = s_trig[slot].sa, ca = s_trig[slot].ca;
     // computeOrbDescriptor on the blurred patch (src/ORBextractor.cc:155-194)
-    const float factorPI = (float)(M_PI / 180.f);
-    float sa, ca;
-    cr_sincosf(__fmul_rn(angle, factorPI), &sa, &ca);
     uint8_t* desc = a.out_desc + ((size_t)(a.first_slot + f) * a.nfeatures + k) * 32;
     // the blurred patch centre as an offset into the block's LDS (exact in float)
     const uint8_t* lds_bytes = &s_patch[0][0];
