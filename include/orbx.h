@@ -44,8 +44,10 @@ extern "C" {
  *      orbx_dev_pyramid_fused / _kind, orbx_dev_set_fast_chunk / get, launch
  *      modes 2 and 3); orbx_lba_last_workgroups, orbx_debug_lba_split;
  *      orbx_track_frame (one Tracking frame on the device); PoseOptimization
- *      sums sequentially in g2o's order by default (orbx_pose_set_exact). */
-#define ORBX_ABI_VERSION 5
+ *      sums sequentially in g2o's order by default (orbx_pose_set_exact).
+ *   6: initialisation models (orbx_init_models, orbx_init_models_batch,
+ *      orbx_dev_init_models, orbx_dev_read_init_models); additions only. */
+#define ORBX_ABI_VERSION 6
 int orbx_abi_version(void);
 
 #define ORBX_OK               0
@@ -252,7 +254,8 @@ int orbx_dev_read_matches(orbx_ctx* ctx, int slot, int32_t* matches12, int cap,
                           int* n_matches, int* n1);
 /* Timing of the dominant kernels over the launches issued since the last
  * reset, measured with hipEvents on the context stream.  name: "pyr0",
- * "resize", "fast", "retain", "blur", "describe", "match".  Returns the number of
+ * "resize", "fast", "retain", "blur", "describe", "match", "init" (the three kernels of
+ * orbx_init_models / orbx_dev_init_models, one timed region per call).  Returns the number of
  * timed launches; *avg_ms receives the mean duration. */
 int orbx_dev_kernel_time(orbx_ctx* ctx, const char* name, double* avg_ms,
                          double* total_ms);
@@ -307,6 +310,65 @@ int orbx_search_for_initialization(orbx_ctx* ctx, const orbx_frame_view* F1,
                                    const orbx_frame_view* F2, float* prev_matched,
                                    int32_t* matches12, int window, float nnratio,
                                    int check_ori, int* n_matches);
+
+/* Initializer::Initialize up to the score ratio (src/Initializer.cc:44-113):
+ * the matches compacted in i1 order, the RANSAC sets drawn from the caller's
+ * rand() values as DUtils::Random::RandomInt maps them (:80-95), Normalize
+ * over all keypoints of each frame (:747-793), and for every iteration
+ * ComputeH21 / ComputeF21, H21i = T2inv*Hn*T1 with its inverse, F21i =
+ * T2t*Fn*T1, CheckHomography / CheckFundamental (:303-466) and the selection
+ * of the first strictly greater score (FindHomography :122-170,
+ * FindFundamental :173-221), all on the device.  The caller goes on with
+ * `if(RH>0.40)` (:113) and ReconstructH / ReconstructF on the host.
+ * Everything is the reference's float arithmetic operation by operation but
+ * the two cv::SVDecomp null vectors, the 3x3 inverses and the denormalising
+ * products, which are FP64 rounded once to float; the
+ * sign of Hn / Fn is unspecified (no score or inlier depends on it).
+ * Arguments are checked before any device work: a null context or query,
+ * max_iter outside 1..1024, a draw below 0, sigma <= 0, or a match index >=
+ * n2 is ORBX_ERR_ARG; cap < N is ORBX_ERR_CAPACITY; a frame of more than 4096
+ * keypoints ORBX_ERR_UNSUPPORTED.  A pair with N < 8 (the reference would
+ * index an empty vector; Tracking calls with N >= 100) returns ORBX_OK with
+ * n_matches set, best_h = best_f = -1, SH = SF = 0 and RH = 0/0. */
+typedef struct {
+    /* in */
+    const orbx_keypoint* keys1; int n1;   /* Initializer::mvKeys1 = ReferenceFrame.mvKeysUn */
+    const orbx_keypoint* keys2; int n2;   /* CurrentFrame.mvKeysUn                          */
+    const int32_t* matches12;             /* n1: vMatches12 (index into keys2, or < 0)      */
+    float sigma;                          /* 1.0 (src/Tracking.cc:341)                      */
+    int max_iter;                         /* 200                                            */
+    const int32_t* draws;                 /* max_iter x 8 successive rand() values, 0..RAND_MAX (2^31-1) */
+    /* out */
+    int n_matches;                        /* N = mvMatches12.size()                         */
+    int best_h, best_f;                   /* winning iteration, -1 if no score exceeded 0   */
+    float SH, SF, RH;                     /* scores; RH = SH / (SH + SF) in float           */
+    float H21[9], F21[9];                 /* row-major; untouched when best_* is -1         */
+    uint8_t* inliers_h; uint8_t* inliers_f; int cap;   /* vbMatchesInliersH / F, by match index i */
+    /* optional taps (may be NULL), all [max_iter] leading dimension */
+    int32_t* sets;                        /* x 8: mvSets                                    */
+    float* Hn; float* Fn;                 /* x 9: ComputeH21 / ComputeF21 results           */
+    float* H21_all; float* H12_all; float* F21_all;    /* x 9: what the Check* functions read */
+    float* score_h; float* score_f;       /* currentScore of every iteration                */
+    float* T1; float* T2;                 /* 9 each: Normalize's matrices                   */
+} orbx_init_query;
+
+int orbx_init_models(orbx_ctx* ctx, orbx_init_query* q);
+int orbx_init_models_batch(orbx_ctx* ctx, int B, orbx_init_query* qs);   /* one upload, one read-back */
+
+/* Device-resident: pair (slot s-1, slot s) for every s in [first, first+count)
+ * with s % seq_len != 0, keypoints as the slots hold them (after
+ * orbx_dev_undistort if used), matches12 as orbx_dev_match_prev /
+ * orbx_dev_extract_match left them in slot s.  draws: count x max_iter x 8
+ * (slot s reads block s - first).  The kernels run asynchronously on the
+ * context stream, ordered after a pending async match of these slots (the
+ * call returns once the draws are uploaded).  Results stay in HBM until read
+ * or until the next run.  orbx_dev_read_init_models fills the out fields and
+ * taps of `out` (inliers / cap and the tap pointers are read from it; the in
+ * fields are ignored); before a run, on a slot outside the run or on a
+ * sequence-start slot it is ORBX_ERR_ARG. */
+int orbx_dev_init_models(orbx_ctx* ctx, int first, int count, int seq_len,
+                         float sigma, int max_iter, const int32_t* draws);
+int orbx_dev_read_init_models(orbx_ctx* ctx, int slot, orbx_init_query* out);
 
 /* ORBmatcher::WindowSearch (src/ORBmatcher.cc:409-516).
  * f1_mp: per F1 keypoint, 1 if F1.mvpMapPoints[i1] is set and not bad.

@@ -39,6 +39,70 @@ class FrameView(ctypes.Structure):
                 ("nlevels", ctypes.c_int), ("scale_factor", ctypes.c_float)]
 
 
+class InitQuery(ctypes.Structure):
+    """orbx_init_query (include/orbx.h)."""
+    _fields_ = [("keys1", ctypes.c_void_p), ("n1", ctypes.c_int), ("keys2", ctypes.c_void_p), ("n2", ctypes.c_int),
+                ("matches12", ctypes.c_void_p), ("sigma", ctypes.c_float), ("max_iter", ctypes.c_int),
+                ("draws", ctypes.c_void_p),
+                ("n_matches", ctypes.c_int), ("best_h", ctypes.c_int), ("best_f", ctypes.c_int),
+                ("SH", ctypes.c_float), ("SF", ctypes.c_float), ("RH", ctypes.c_float),
+                ("H21", ctypes.c_float * 9), ("F21", ctypes.c_float * 9),
+                ("inliers_h", ctypes.c_void_p), ("inliers_f", ctypes.c_void_p), ("cap", ctypes.c_int),
+                ("sets", ctypes.c_void_p), ("Hn", ctypes.c_void_p), ("Fn", ctypes.c_void_p),
+                ("H21_all", ctypes.c_void_p), ("H12_all", ctypes.c_void_p), ("F21_all", ctypes.c_void_p),
+                ("score_h", ctypes.c_void_p), ("score_f", ctypes.c_void_p),
+                ("T1", ctypes.c_void_p), ("T2", ctypes.c_void_p)]
+
+
+_INIT_TAPS = (("sets", np.int32, 8), ("Hn", np.float32, 9), ("Fn", np.float32, 9), ("H21_all", np.float32, 9),
+              ("H12_all", np.float32, 9), ("F21_all", np.float32, 9), ("score_h", np.float32, 0),
+              ("score_f", np.float32, 0))
+
+
+def init_query(keys1, keys2, matches12, draws, sigma=1.0, max_iter=200, taps=False, cap=None):
+    """An InitQuery over numpy arrays and the arrays it points to (keep both
+    alive while the query is used): (query, keep)."""
+    keep = {}
+    q = InitQuery()
+    if keys1 is not None:
+        keep["keys1"] = np.ascontiguousarray(keys1, KEYPOINT)
+        keep["keys2"] = np.ascontiguousarray(keys2, KEYPOINT)
+        keep["matches12"] = np.ascontiguousarray(matches12, np.int32)
+        keep["draws"] = np.ascontiguousarray(draws, np.int32)
+        q.keys1, q.n1 = keep["keys1"].ctypes.data, len(keep["keys1"])
+        q.keys2, q.n2 = keep["keys2"].ctypes.data, len(keep["keys2"])
+        q.matches12, q.draws = keep["matches12"].ctypes.data, keep["draws"].ctypes.data
+        if cap is None:
+            cap = len(keep["keys1"])
+    q.sigma, q.max_iter = sigma, max_iter
+    q.cap = max(int(cap), 0)
+    keep["inliers_h"], keep["inliers_f"] = np.zeros(max(q.cap, 1), np.uint8), np.zeros(max(q.cap, 1), np.uint8)
+    q.inliers_h, q.inliers_f = keep["inliers_h"].ctypes.data, keep["inliers_f"].ctypes.data
+    if taps:
+        m = max(int(max_iter), 1)
+        for name, dt, k in _INIT_TAPS:
+            keep[name] = np.zeros((m, k) if k else m, dt)
+            setattr(q, name, keep[name].ctypes.data)
+        for name in ("T1", "T2"):
+            keep[name] = np.zeros(9, np.float32)
+            setattr(q, name, keep[name].ctypes.data)
+    return q, keep
+
+
+def init_result(q, keep, taps=False):
+    """The out fields (and taps) of a filled InitQuery as a dict."""
+    n = q.n_matches
+    r = dict(n_matches=n, best_h=q.best_h, best_f=q.best_f, SH=np.float32(q.SH), SF=np.float32(q.SF),
+             RH=np.float32(q.RH), H21=np.array(q.H21, np.float32) if q.best_h >= 0 else None,
+             F21=np.array(q.F21, np.float32) if q.best_f >= 0 else None,
+             inliers_h=keep["inliers_h"][:n].copy(), inliers_f=keep["inliers_f"][:n].copy())
+    if taps:
+        for name, _, _ in _INIT_TAPS:
+            r[name] = keep[name]
+        r["T1"], r["T2"] = keep["T1"], keep["T2"]
+    return r
+
+
 _lib = None
 
 
@@ -150,6 +214,10 @@ def _declare(L):
         "orbx_dev_upload_async": ([vp, i, i, vp, i, i, sz], i),
         "orbx_dev_download_async": ([vp, i, i, vp, vp, vp, vp, vp], i),
         "orbx_describe_levels": ([i, f, i, i, i, i, vp, i], i),
+        "orbx_init_models": ([vp, vp], i),
+        "orbx_init_models_batch": ([vp, i, vp], i),
+        "orbx_dev_init_models": ([vp, i, i, i, f, i, vp], i),
+        "orbx_dev_read_init_models": ([vp, i, vp], i),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(L, name)
@@ -449,6 +517,43 @@ class Context:
         _check(lib().orbx_dev_search_by_bow(self._h, slot, n, arr, nnratio, int(check_ori), ptrs, self.nfeatures,
                                             _ptr(nm)), "orbx_dev_search_by_bow")
         return outs, nm[:n]
+
+    # --- Initializer: homography / fundamental models ----------------------
+    def init_models(self, keys1, keys2, matches12, draws, sigma=1.0, max_iter=200, taps=False):
+        """Initializer::FindHomography + FindFundamental and the score ratio
+        (orbx_init_models): a dict of n_matches, best_h / best_f, SH, SF, RH,
+        H21 / F21 (None without a winner), inliers_h / inliers_f and, with
+        taps, the per-iteration arrays of orbx_init_query."""
+        q, keep = init_query(keys1, keys2, matches12, draws, sigma, max_iter, taps)
+        _check(lib().orbx_init_models(self._h, ctypes.byref(q)), "orbx_init_models")
+        return init_result(q, keep, taps)
+
+    def init_models_batch(self, queries, taps=False):
+        """orbx_init_models_batch over (keys1, keys2, matches12, draws, sigma,
+        max_iter) tuples: one upload, one read-back; a list of dicts."""
+        built = [init_query(*a, taps=taps) for a in queries]
+        arr = (InitQuery * len(built))(*[b[0] for b in built])
+        _check(lib().orbx_init_models_batch(self._h, len(built), arr), "orbx_init_models_batch")
+        return [init_result(arr[k], built[k][1], taps) for k in range(len(built))]
+
+    def dev_init_models(self, first, count, seq_len, draws, sigma=1.0, max_iter=200):
+        """orbx_dev_init_models: the models of every pair (s - 1, s) of slots
+        [first, first + count) from the slots' keypoints and matches; draws
+        (count, max_iter, 8) int32."""
+        d = np.ascontiguousarray(draws, np.int32)
+        if d.size != count * max_iter * 8:
+            raise ValueError(f"draws: {d.size} values, expected count x max_iter x 8 = {count * max_iter * 8}")
+        _check(lib().orbx_dev_init_models(self._h, first, count, seq_len, sigma, max_iter, _ptr(d)),
+               "orbx_dev_init_models")
+        self._init_iter = max_iter
+
+    def read_init_models(self, slot, taps=False):
+        """orbx_dev_read_init_models: the dict of init_models for the pair
+        (slot - 1, slot) of the last dev_init_models run."""
+        q, keep = init_query(None, None, None, None, max_iter=getattr(self, "_init_iter", 1), taps=taps,
+                             cap=self.nfeatures)
+        _check(lib().orbx_dev_read_init_models(self._h, slot, ctypes.byref(q)), "orbx_dev_read_init_models")
+        return init_result(q, keep, taps)
 
     @property
     def handle(self):

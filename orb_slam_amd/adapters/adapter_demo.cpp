@@ -1,11 +1,13 @@
 // Exercises the C++ adapter (orbx_adapters.hpp) the way ORB-SLAM's Tracking
 // and LocalMapping would: extract two frames of a shifted synthetic image,
-// SearchForInitialization between them, brute-force matching, and one local
-// BA on a tiny synthetic problem.  Prints one JSON line.  Exit codes: 0 ok,
+// SearchForInitialization between them, the initialisation models of those
+// matches (Initializer::FindModels beside the plain C call fed the same rand()
+// sequence), brute-force matching, and one local BA on a tiny synthetic problem.  Prints one JSON line.  Exit codes: 0 ok,
 // 3 device path unavailable (orbx_error), 1 other failure.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "orbx_adapters.hpp"
@@ -66,6 +68,43 @@ int main()
         for (size_t i = 0; i < prev.size(); i++) prev[i] = {F1.keys_un[i].x, F1.keys_un[i].y};
         std::vector<int> m12;
         const int n_init = matcher.SearchForInitialization(F1, F2, prev, m12, 100);
+        // Initializer::Initialize's model searches on the matches just found
+        Initializer initializer(F1.keys_un, 1.0f, 200, ex.context());
+        std::vector<bool> inH, inF;
+        float SH = 0.f, SF = 0.f, H[9] = {0}, Fm[9] = {0};
+        std::srand(1);
+        const float RH = initializer.FindModels(F2.keys_un, m12, inH, SH, H, inF, SF, Fm);
+        // the C call, fed the rand() values the adapter drew
+        std::srand(1);
+        std::vector<int32_t> draws(200 * 8);
+        for (auto& d : draws) d = (int32_t)std::rand();
+        std::vector<int32_t> m12c(m12.begin(), m12.end());
+        std::vector<uint8_t> cH(m12.size() + 1), cF(m12.size() + 1);
+        orbx_init_query q;
+        std::memset(&q, 0, sizeof(q));
+        q.keys1 = F1.keys_un.data();
+        q.n1 = (int)F1.keys_un.size();
+        q.keys2 = F2.keys_un.data();
+        q.n2 = (int)F2.keys_un.size();
+        q.matches12 = m12c.data();
+        q.sigma = 1.0f;
+        q.max_iter = 200;
+        q.draws = draws.data();
+        q.inliers_h = cH.data();
+        q.inliers_f = cF.data();
+        q.cap = (int)m12.size();
+        check(orbx_init_models(ex.context(), &q), "orbx_init_models");
+        bool init_same = q.n_matches == n_init && q.best_h == initializer.mBestH && q.best_f == initializer.mBestF &&
+                         std::memcmp(&q.SH, &SH, 4) == 0 && std::memcmp(&q.SF, &SF, 4) == 0 &&
+                         std::memcmp(&q.RH, &RH, 4) == 0 && (int)inH.size() == q.n_matches;
+        if (q.best_h >= 0) init_same = init_same && std::memcmp(q.H21, H, sizeof(H)) == 0;
+        if (q.best_f >= 0) init_same = init_same && std::memcmp(q.F21, Fm, sizeof(Fm)) == 0;
+        int n_in_h = 0, n_in_f = 0;
+        for (int i = 0; i < q.n_matches && init_same; i++) {
+            init_same = inH[i] == (cH[i] != 0) && inF[i] == (cF[i] != 0);
+            n_in_h += cH[i];
+            n_in_f += cF[i];
+        }
         std::vector<int> mbf;
         const int n_bf = matcher.MatchBruteForce(F1.desc, F2.desc, mbf);
         // tiny BA: 3 keyframes (first fixed) observing 60 points
@@ -120,10 +159,12 @@ int main()
         for (uint8_t m : PF.has_mp) n_mp += m;
         std::printf("{\"n1\": %zu, \"n2\": %zu, \"levels\": %d, \"scale\": %.3f, \"init_matches\": %d, "
                     "\"bf_matches\": %d, \"ba_iterations\": [%d, %d], \"ba_chi2\": [%.6g, %.6g], "
-                    "\"pose_inliers\": %d, \"pose_edges\": %d, \"pose_tx\": %.6g}\n",
+                    "\"pose_inliers\": %d, \"pose_edges\": %d, \"pose_tx\": %.6g, \"init_same\": %d, "
+                    "\"init_n\": %d, \"init_best\": [%d, %d], \"init_rh\": %.6g, \"init_inliers\": [%d, %d]}\n",
                     F1.keys_un.size(), F2.keys_un.size(), ex.GetLevels(), ex.GetScaleFactor(), n_init, n_bf,
                     P.stats.iterations[0], P.stats.iterations[1], P.stats.chi2_initial[0], P.stats.chi2_final[1],
-                    n_pose_inliers, n_mp, PF.Tcw[3]);
+                    n_pose_inliers, n_mp, PF.Tcw[3], init_same ? 1 : 0, q.n_matches, q.best_h, q.best_f, (double)q.RH,
+                    n_in_h, n_in_f);
         return 0;
     } catch (const orbx_error& e) {
         std::fprintf(stderr, "%s\n", e.what());

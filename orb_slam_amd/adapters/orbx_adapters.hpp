@@ -8,6 +8,8 @@
 //   ORB_SLAM_AMD::ORBmatcher     <- ORB_SLAM::ORBmatcher     include/ORBmatcher.h:37-107
 //   ORB_SLAM_AMD::Optimizer      <- ORB_SLAM::Optimizer::LocalBundleAdjustment
 //                                                           include/Optimizer.h:42
+//   ORB_SLAM_AMD::Initializer    <- ORB_SLAM::Initializer    include/Initializer.h:33-96
+//                                   (FindHomography + FindFundamental)
 //
 // Error behaviour: the reference has no error codes.  Like the reference, an
 // empty image returns without touching the outputs (src/ORBextractor.cc:
@@ -17,6 +19,7 @@
 
 #include <cstdint>
 #include <climits>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <stdexcept>
@@ -393,6 +396,79 @@ public:
                              prob.edge_status.data(), prob.point_bad.data(), &prob.stats),
               "Optimizer::LocalBundleAdjustment");
     }
+};
+
+// ---------------------------------------------------------------------------
+// Initializer (src/Initializer.cc:32-221): the constructor's reference
+// keypoints, sigma and iterations, and the two model searches Initialize runs
+// on two boost::threads (:97-107) as one device call.  The caller goes on
+// with `if(RH>0.40)` and ReconstructH / ReconstructF (:113-116), which take
+// exactly these outputs.
+// ---------------------------------------------------------------------------
+class Initializer {
+public:
+    // Initializer(const Frame& ReferenceFrame, float sigma = 1.0, int iterations = 200) (:32-42),
+    // with ReferenceFrame.mvKeysUn passed as such.
+    Initializer(const std::vector<KeyPoint>& keys1, float sigma = 1.0f, int iterations = 200, orbx_ctx* ctx = nullptr)
+        : mvKeys1(keys1), mSigma(sigma), mMaxIterations(iterations), ctx_(ctx)
+    {
+        if (!ctx_) {
+            own_.reset(new Context(1000, 1.2f, 8, 1, 20, 64, 64));
+            ctx_ = own_->get();
+        }
+    }
+
+    // The part of Initialize before the ratio test (:49-110).  rand() is
+    // called as the reference's set loop calls it (:80-95): 8 times per
+    // iteration through DUtils::Random::RandomInt, and not at all when there
+    // are fewer than 8 matches (where the reference would fail).  H and F are
+    // 3x3 row-major and keep their content when no iteration scored above 0.
+    // Returns RH = SH / (SH + SF).
+    float FindModels(const std::vector<KeyPoint>& keys2, const std::vector<int>& vMatches12,
+                     std::vector<bool>& vbMatchesInliersH, float& SH, float H[9],
+                     std::vector<bool>& vbMatchesInliersF, float& SF, float F[9])
+    {
+        int N = 0;
+        for (int m : vMatches12) N += m >= 0;
+        std::vector<int32_t> draws((size_t)mMaxIterations * 8, 0);
+        if (N >= 8)
+            for (auto& d : draws) d = (int32_t)std::rand();
+        std::vector<uint8_t> inH(N > 0 ? N : 1), inF(N > 0 ? N : 1);
+        std::vector<int32_t> m12(vMatches12.begin(), vMatches12.end());
+        orbx_init_query q;
+        std::memset(&q, 0, sizeof(q));
+        q.keys1 = mvKeys1.data();
+        q.n1 = (int)mvKeys1.size();
+        q.keys2 = keys2.data();
+        q.n2 = (int)keys2.size();
+        q.matches12 = m12.data();
+        q.sigma = mSigma;
+        q.max_iter = mMaxIterations;
+        q.draws = draws.data();
+        q.inliers_h = inH.data();
+        q.inliers_f = inF.data();
+        q.cap = N;
+        if ((int)m12.size() != q.n1) throw orbx_error(ORBX_ERR_ARG, "Initializer::FindModels");
+        check(orbx_init_models(ctx_, &q), "Initializer::FindModels");
+        SH = q.SH;
+        SF = q.SF;
+        if (q.best_h >= 0) std::memcpy(H, q.H21, sizeof(q.H21));
+        if (q.best_f >= 0) std::memcpy(F, q.F21, sizeof(q.F21));
+        vbMatchesInliersH.assign(inH.begin(), inH.begin() + N);
+        vbMatchesInliersF.assign(inF.begin(), inF.begin() + N);
+        mBestH = q.best_h;
+        mBestF = q.best_f;
+        return q.RH;
+    }
+
+    int mBestH = -1, mBestF = -1;   // winning iterations of the last call (-1: none)
+
+private:
+    std::vector<KeyPoint> mvKeys1;
+    float mSigma;
+    int mMaxIterations;
+    orbx_ctx* ctx_;
+    std::unique_ptr<Context> own_;
 };
 
 }  // namespace ORB_SLAM_AMD

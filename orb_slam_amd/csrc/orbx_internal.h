@@ -337,6 +337,14 @@ struct orbx_ctx {
     int bow_nf = 0;
     orbx::SlotBowDev bow = {};
     std::vector<uint8_t> bow_ready;
+    // initialisation models of device-resident pairs (orbx_init.hip): the
+    // result blocks of the last orbx_dev_init_models run, one per pair, and
+    // the run they belong to (init_pair[s - init_first]: block of slot s, -1
+    // for a sequence start)
+    void* init_res = nullptr;
+    size_t init_res_bytes = 0;
+    int init_first = 0, init_count = 0, init_iter = 0;   // init_count 0: no run yet
+    std::vector<int> init_pair;
     // timing
     bool timing = false;
     std::string timing_only;   // non-empty: only this timer records (orbx_dev_kernel_time_select)
