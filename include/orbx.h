@@ -46,8 +46,11 @@ extern "C" {
  *      orbx_track_frame (one Tracking frame on the device); PoseOptimization
  *      sums sequentially in g2o's order by default (orbx_pose_set_exact).
  *   6: initialisation models (orbx_init_models, orbx_init_models_batch,
- *      orbx_dev_init_models, orbx_dev_read_init_models); additions only. */
-#define ORBX_ABI_VERSION 6
+ *      orbx_dev_init_models, orbx_dev_read_init_models); additions only.
+ *   7: new map points (orbx_kf_geom, orbx_triangulate_matches,
+ *      orbx_create_new_map_points, orbx_dev_create_new_map_points);
+ *      additions only. */
+#define ORBX_ABI_VERSION 7
 int orbx_abi_version(void);
 
 #define ORBX_OK               0
@@ -163,7 +166,12 @@ int orbx_dev_extract(orbx_ctx* ctx, int first, int count);
  * (-O3 -march=native, CMakeLists.txt:12-13) on an FMA host, where GCC's
  * default -ffp-contract=fast fuses them: fma(x, b, y*a), fma(x, a, -(y*b));
  * fma(-(k*(a+b)), a+b, fma(a, b, -(c*c))).  Applies to extractions launched
- * after the call (DESIGN.md section 4 has the measured effect). */
+ * after the call (DESIGN.md section 4 has the measured effect).
+ * The triangulation gates (orbx_triangulate_matches and the two
+ * create_new_map_points forms) follow the mode too, for the two expressions
+ * of src/LocalMapping.cc:335-351 that are the reference's own source:
+ * fx*x*invz+cx and errX*errX+errY*errY as written (0), or fma(fx*x, invz, cx)
+ * and fma(errX, errX, errY*errY) (1); they read the mode at the call. */
 int orbx_set_fp_contract(orbx_ctx* ctx, int enable);
 int orbx_get_fp_contract(const orbx_ctx* ctx);
 /* libstdc++ era of retainBest's std::nth_element (KeyPointsFilter::retainBest,
@@ -255,7 +263,9 @@ int orbx_dev_read_matches(orbx_ctx* ctx, int slot, int32_t* matches12, int cap,
 /* Timing of the dominant kernels over the launches issued since the last
  * reset, measured with hipEvents on the context stream.  name: "pyr0",
  * "resize", "fast", "retain", "blur", "describe", "match", "init" (the three kernels of
- * orbx_init_models / orbx_dev_init_models, one timed region per call).  Returns the number of
+ * orbx_init_models / orbx_dev_init_models, one timed region per call),
+ * "triangulate" (k_triangulate: one launch per orbx_triangulate_matches or
+ * unchained create_new_map_points call, one per neighbour when chained).  Returns the number of
  * timed launches; *avg_ms receives the mean duration. */
 int orbx_dev_kernel_time(orbx_ctx* ctx, const char* name, double* avg_ms,
                          double* total_ms);
@@ -789,6 +799,76 @@ int orbx_dev_search_for_triangulation(orbx_ctx* ctx, int slot1, const uint8_t* m
                                       const uint8_t* const* mp2s, const float* F12s, const float* sigma2_2s,
                                       int nlevels, int check_ori, int32_t* const* matches12, int cap,
                                       int* n_matches);
+
+/* New map points: LocalMapping::CreateNewMapPoints' neighbour loop
+ * (src/LocalMapping.cc:245-385) behind its SearchForTriangulation call.  The
+ * baseline test (:249-258), ComputeF12 and `new MapPoint ...
+ * UpdateNormalAndDepth` (:370-383) stay with the caller. */
+typedef struct {                 /* a keyframe as CreateNewMapPoints reads it */
+    const float* Rcw;            /* 9  GetRotation(), row-major   */
+    const float* tcw;            /* 3  GetTranslation()           */
+    const float* Ow;             /* 3  GetCameraCenter()          */
+    const float* cam;            /* fx, fy, cx, cy                */
+    const float* scale_factors;  /* nlevels: mvScaleFactors       */
+    const float* level_sigma2;   /* nlevels: mvLevelSigma2        */
+    int nlevels;                 /* >= 2 (ratioFactor reads [1])  */
+} orbx_kf_geom;
+
+/* The per-match half of the loop (:283-368) for the matches of KF1 against
+ * n neighbours: matches12[k] holds per KF1 keypoint a keys2[k] index or < 0.
+ * One upload, one launch over all (k, i1), one read-back.  Per neighbour:
+ * status[k] (n1 bytes, all written):
+ *   0 no match for this keypoint      5 z2 <= 0 (:327)
+ *   1 point created, xyz holds x3D    6 reprojection error in KF1 (:339)
+ *   2 parallax gate (:299)            7 reprojection error in KF2 (:351)
+ *   3 x3D(3) == 0 (:314)              8 dist1 == 0 || dist2 == 0 (:361)
+ *   4 z1 <= 0 (:323)                  9 scale consistency (:366)
+ * xyz[k] (n1 x 3, written where status is 1), n_created[k], and the optional
+ * tap v4[k] (n1 x 4, v4 or v4[k] may be NULL): the null vector of A, written
+ * where the solve ran (status neither 0 nor 2).
+ * The gates are the reference's float arithmetic operation by operation;
+ * OpenCV's double accumulations and the cv::SVD null vector -- FP64 from the
+ * float entries of A, rounded once, sign unspecified (the division by x3D(3)
+ * is sign-invariant) -- are the defined parts of DESIGN.md section 4.
+ * ORBX_ERR_ARG (before any device work): a null context or required pointer,
+ * nlevels outside 2..16, an octave >= its keyframe's nlevels, a match index
+ * >= n2s[k].  n == 0 or n1 == 0 returns ORBX_OK and touches nothing. */
+int orbx_triangulate_matches(orbx_ctx* ctx, const orbx_keypoint* keys1, int n1, const orbx_kf_geom* g1, int n,
+                             const orbx_keypoint* const* keys2, const int* n2s, const orbx_kf_geom* g2s,
+                             const int32_t* const* matches12, float* const* xyz, uint8_t* const* status,
+                             int* n_created, float* const* v4);
+/* The loop: SearchForTriangulation of KF1 against KF2s[0, n) (views, F12s
+ * and check_ori as orbx_search_for_triangulation_batch; KF2's mvLevelSigma2
+ * from g2s) and the triangulation of its matches, in one call.  matches12[k]
+ * (KF1->n entries) and n_matches[k] as the search returns them, the rest as
+ * orbx_triangulate_matches.
+ * chain = 0: every neighbour is searched with the caller's map-point states:
+ *   the batch search followed by orbx_triangulate_matches, bit for bit.
+ * chain = 1: the reference's loop.  A point created for a KF1 keypoint
+ *   against neighbour k gives it a map point (:375), so the searches of the
+ *   neighbours after k skip it (src/ORBmatcher.cc:894-896) and its candidate
+ *   there stays free for other keypoints.  The n searches and triangulations
+ *   are queued on the context stream, neighbour after neighbour, without a
+ *   host synchronisation in between.  A created point changes KF2's states
+ *   as well (:376): a KF2 listed twice (the same keys or mp array) is
+ *   ORBX_ERR_ARG. */
+int orbx_create_new_map_points(orbx_ctx* ctx, const orbx_bow_view* KF1, const orbx_kf_geom* g1, int n,
+                               const orbx_bow_view* KF2s, const orbx_kf_geom* g2s, const float* F12s,
+                               int check_ori, int chain, int32_t* const* matches12, int* n_matches,
+                               float* const* xyz, uint8_t* const* status, int* n_created, float* const* v4);
+/* The same between device-resident frames, with the inputs of
+ * orbx_dev_search_for_triangulation: only the map-point states, F12s and the
+ * geometries travel.  Every geometry must have the extractor's nlevels
+ * (ORBX_ERR_ARG otherwise).  Every output array holds cap >= nfeatures
+ * entries (ORBX_ERR_CAPACITY below): matches12[k] cap, status[k] cap (0 past
+ * the slot's keypoints), xyz[k] cap x 3, v4[k] cap x 4.  A match whose index
+ * or octave is out of range is dropped as status 0.  A slot listed twice in
+ * slots2 under chain = 1 is ORBX_ERR_ARG. */
+int orbx_dev_create_new_map_points(orbx_ctx* ctx, int slot1, const uint8_t* mp1, const orbx_kf_geom* g1, int n,
+                                   const int* slots2, const uint8_t* const* mp2s, const orbx_kf_geom* g2s,
+                                   const float* F12s, int check_ori, int chain, int32_t* const* matches12,
+                                   int* n_matches, float* const* xyz, uint8_t* const* status, int* n_created,
+                                   float* const* v4, int cap);
 
 /* ------------------------------------------------------------------------ */
 /* C. Local bundle adjustment                                                */

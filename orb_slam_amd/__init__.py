@@ -103,6 +103,48 @@ def init_result(q, keep, taps=False):
     return r
 
 
+class KfGeom(ctypes.Structure):
+    """orbx_kf_geom (include/orbx.h)."""
+    _fields_ = [("Rcw", ctypes.c_void_p), ("tcw", ctypes.c_void_p), ("Ow", ctypes.c_void_p), ("cam", ctypes.c_void_p),
+                ("scale_factors", ctypes.c_void_p), ("level_sigma2", ctypes.c_void_p), ("nlevels", ctypes.c_int)]
+
+
+class BowView(ctypes.Structure):
+    """orbx_bow_view (include/orbx.h)."""
+    _fields_ = [("keys", ctypes.c_void_p), ("desc", ctypes.c_void_p), ("n", ctypes.c_int), ("mp", ctypes.c_void_p),
+                ("n_nodes", ctypes.c_int), ("node_id", ctypes.c_void_p), ("node_ptr", ctypes.c_void_p),
+                ("feat_idx", ctypes.c_void_p)]
+
+
+def kf_geom(g):
+    """A KfGeom over a dict of Rcw (3x3), tcw, Ow, cam (fx, fy, cx, cy),
+    scale_factors and level_sigma2, and the float32 arrays it points to (keep
+    them alive while the struct is used): (struct, keep)."""
+    keep = {k: np.ascontiguousarray(g[k], np.float32).reshape(-1)
+            for k in ("Rcw", "tcw", "Ow", "cam", "scale_factors", "level_sigma2")}
+    q = KfGeom()
+    for k, a in keep.items():
+        setattr(q, k, a.ctypes.data)
+    q.nlevels = int(g.get("nlevels", len(keep["scale_factors"])))
+    return q, keep
+
+
+def _geoms(gs):
+    built = [kf_geom(g) for g in gs]
+    return (KfGeom * max(len(built), 1))(*[b[0] for b in built]), built
+
+
+def _ptr_array(arrays):
+    return (ctypes.c_void_p * max(len(arrays), 1))(*[a.ctypes.data for a in arrays])
+
+
+def _new_points_outputs(n, length, v4):
+    out = dict(xyz=[np.zeros((length, 3), np.float32) for _ in range(n)],
+               status=[np.zeros(length, np.uint8) for _ in range(n)], n_created=np.zeros(max(n, 1), np.int32),
+               v4=[np.zeros((length, 4), np.float32) for _ in range(n)] if v4 else None)
+    return out
+
+
 _lib = None
 
 
@@ -218,6 +260,9 @@ def _declare(L):
         "orbx_init_models_batch": ([vp, i, vp], i),
         "orbx_dev_init_models": ([vp, i, i, i, f, i, vp], i),
         "orbx_dev_read_init_models": ([vp, i, vp], i),
+        "orbx_triangulate_matches": ([vp, vp, i, vp, i, vp, vp, vp, vp, vp, vp, vp, vp], i),
+        "orbx_create_new_map_points": ([vp, vp, vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp], i),
+        "orbx_dev_create_new_map_points": ([vp, i, vp, vp, i, vp, vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp, i], i),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(L, name)
@@ -554,6 +599,83 @@ class Context:
                              cap=self.nfeatures)
         _check(lib().orbx_dev_read_init_models(self._h, slot, ctypes.byref(q)), "orbx_dev_read_init_models")
         return init_result(q, keep, taps)
+
+    # --- LocalMapping::CreateNewMapPoints ----------------------------------
+    def triangulate_matches(self, keys1, g1, keys2, g2s, matches12, v4=False):
+        """orbx_triangulate_matches: the gates and the triangulation of
+        src/LocalMapping.cc:283-368 for the matches of KF1 (keys1, geometry
+        dict g1: kf_geom) against n neighbours (lists keys2, g2s, matches12).
+        A dict of per-neighbour lists xyz (n1 x 3), status (n1) and, with
+        v4, the null-vector tap (n1 x 4), and the array n_created."""
+        n = len(keys2)
+        k1 = np.ascontiguousarray(keys1, KEYPOINT)
+        k2 = [np.ascontiguousarray(k, KEYPOINT) for k in keys2]
+        m = [np.ascontiguousarray(a, np.int32) for a in matches12]
+        if any(len(a) != len(k1) for a in m):
+            raise ValueError("matches12: one entry per KF1 keypoint")
+        G1, keep1 = kf_geom(g1)
+        G2, keep2 = _geoms(g2s)
+        n2 = np.array([len(k) for k in k2] + [0], np.int32)
+        out = _new_points_outputs(n, len(k1), v4)
+        _check(lib().orbx_triangulate_matches(self._h, _ptr(k1), len(k1), ctypes.byref(G1), n, _ptr_array(k2),
+                                              _ptr(n2), G2, _ptr_array(m), _ptr_array(out["xyz"]),
+                                              _ptr_array(out["status"]), _ptr(out["n_created"]),
+                                              _ptr_array(out["v4"]) if v4 else None), "orbx_triangulate_matches")
+        out["n_created"] = out["n_created"][:n]
+        return out
+
+    def create_new_map_points(self, KF1, g1, KF2s, g2s, F12s, check_ori=False, chain=True, v4=False):
+        """orbx_create_new_map_points: SearchForTriangulation of the
+        orbx_bow_view KF1 against the views KF2s and the triangulation of
+        its matches; chain: the reference's loop, a created point marking its
+        KF1 keypoint for the later neighbours.  The dict of
+        triangulate_matches plus matches12 (list) and n_matches."""
+        n = len(KF2s)
+        G1, keep1 = kf_geom(g1)
+        G2, keep2 = _geoms(g2s)
+        F = np.ascontiguousarray(F12s, np.float32)
+        if F.size != 9 * n:
+            raise ValueError(f"F12s: {F.size} values, expected n x 9 = {9 * n}")
+        arr = (type(KF1) * max(n, 1))(*KF2s)
+        out = _new_points_outputs(n, KF1.n, v4)
+        out["matches12"] = [np.full(KF1.n, -1, np.int32) for _ in range(n)]
+        out["n_matches"] = np.zeros(max(n, 1), np.int32)
+        _check(lib().orbx_create_new_map_points(self._h, ctypes.byref(KF1), ctypes.byref(G1), n, arr, G2, _ptr(F),
+                                                int(check_ori), int(chain), _ptr_array(out["matches12"]),
+                                                _ptr(out["n_matches"]), _ptr_array(out["xyz"]),
+                                                _ptr_array(out["status"]), _ptr(out["n_created"]),
+                                                _ptr_array(out["v4"]) if v4 else None),
+               "orbx_create_new_map_points")
+        out["n_created"], out["n_matches"] = out["n_created"][:n], out["n_matches"][:n]
+        return out
+
+    def dev_create_new_map_points(self, slot1, mp1, g1, slots2, mp2s, g2s, F12s, check_ori=False, chain=True,
+                                  v4=False, cap=None):
+        """orbx_dev_create_new_map_points: the same between device-resident
+        frames (after extract and compute_bow on every slot named); mp1 /
+        mp2s are the map-point states of the slots' keypoints.  Arrays of
+        `cap` (default nfeatures) entries."""
+        n = len(slots2)
+        cap = self.nfeatures if cap is None else int(cap)
+        G1, keep1 = kf_geom(g1)
+        G2, keep2 = _geoms(g2s)
+        F = np.ascontiguousarray(F12s, np.float32)
+        if F.size != 9 * n:
+            raise ValueError(f"F12s: {F.size} values, expected n x 9 = {9 * n}")
+        m1 = np.ascontiguousarray(mp1, np.uint8)
+        m2 = [np.ascontiguousarray(m, np.uint8) for m in mp2s]
+        s2 = np.ascontiguousarray(list(slots2) + [0], np.int32)
+        out = _new_points_outputs(n, max(cap, 1), v4)
+        out["matches12"] = [np.full(max(cap, 1), -1, np.int32) for _ in range(n)]
+        out["n_matches"] = np.zeros(max(n, 1), np.int32)
+        _check(lib().orbx_dev_create_new_map_points(self._h, slot1, _ptr(m1), ctypes.byref(G1), n, _ptr(s2),
+                                                    _ptr_array(m2), G2, _ptr(F), int(check_ori), int(chain),
+                                                    _ptr_array(out["matches12"]), _ptr(out["n_matches"]),
+                                                    _ptr_array(out["xyz"]), _ptr_array(out["status"]),
+                                                    _ptr(out["n_created"]), _ptr_array(out["v4"]) if v4 else None,
+                                                    cap), "orbx_dev_create_new_map_points")
+        out["n_created"], out["n_matches"] = out["n_created"][:n], out["n_matches"][:n]
+        return out
 
     @property
     def handle(self):

@@ -471,4 +471,106 @@ private:
     std::unique_ptr<Context> own_;
 };
 
+// ---------------------------------------------------------------------------
+// LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:220-386): what the
+// loop reads of a keyframe, and the loop behind the baseline test and
+// ComputeF12 (:249-261) as one device call.
+// ---------------------------------------------------------------------------
+// A keyframe's pose, camera and level tables, copied from the reference's
+// getters: GetRotation() / GetTranslation() / GetCameraCenter() as the
+// cv::Mat's float data (row-major 3x3, 3, 3), fx, fy, cx, cy and
+// GetScaleFactors() / GetVectorScaleSigma2().
+struct KeyFrameGeom {
+    float Rcw[9], tcw[3], Ow[3], cam[4];
+    std::vector<float> scale_factors, level_sigma2;
+
+    KeyFrameGeom(const float* rotation, const float* translation, const float* camera_center, float fx, float fy,
+                 float cx, float cy, const std::vector<float>& mvScaleFactors, const std::vector<float>& mvLevelSigma2)
+        : scale_factors(mvScaleFactors), level_sigma2(mvLevelSigma2)
+    {
+        std::memcpy(Rcw, rotation, sizeof(Rcw));
+        std::memcpy(tcw, translation, sizeof(tcw));
+        std::memcpy(Ow, camera_center, sizeof(Ow));
+        cam[0] = fx;
+        cam[1] = fy;
+        cam[2] = cx;
+        cam[3] = cy;
+        if (scale_factors.size() != level_sigma2.size()) throw orbx_error(ORBX_ERR_ARG, "KeyFrameGeom");
+    }
+
+    // The view the C calls take; valid while this object lives unchanged.
+    orbx_kf_geom view() const
+    {
+        orbx_kf_geom g;
+        g.Rcw = Rcw;
+        g.tcw = tcw;
+        g.Ow = Ow;
+        g.cam = cam;
+        g.scale_factors = scale_factors.data();
+        g.level_sigma2 = level_sigma2.data();
+        g.nlevels = (int)scale_factors.size();
+        return g;
+    }
+};
+
+struct NewPoint {
+    int idx1, idx2;     // vMatchedIndices[ikp]
+    float x3D[3];       // the MapPoint's position (:370)
+};
+
+class LocalMapping {
+public:
+    explicit LocalMapping(orbx_ctx* ctx) : ctx_(ctx) {}
+
+    // The neighbour loop for the neighbours that passed the baseline test:
+    // per neighbour the (idx1, idx2, x3D) of every created point in idx1
+    // order.  KF1 / KF2s are the keyframes as the vocabulary-node searches
+    // read them, F12s the n ComputeF12 results (3x3 row-major each).  The
+    // caller creates the MapPoints from the triples (:370-383); the search
+    // of each neighbour skips the keypoints that got a point against an
+    // earlier one, as the reference's loop does.
+    std::vector<std::vector<NewPoint>> CreateNewMapPoints(const orbx_bow_view& KF1, const KeyFrameGeom& geom1,
+                                                          const std::vector<orbx_bow_view>& KF2s,
+                                                          const std::vector<KeyFrameGeom>& geom2s,
+                                                          const std::vector<float>& F12s, bool checkOri = false)
+    {
+        const int n = (int)KF2s.size(), n1 = KF1.n;
+        if ((int)geom2s.size() != n || (int)F12s.size() != 9 * n)
+            throw orbx_error(ORBX_ERR_ARG, "LocalMapping::CreateNewMapPoints");
+        std::vector<std::vector<NewPoint>> out(n);
+        if (n == 0 || n1 <= 0) return out;
+        const orbx_kf_geom g1 = geom1.view();
+        std::vector<orbx_kf_geom> g2s;
+        for (const KeyFrameGeom& g : geom2s) g2s.push_back(g.view());
+        std::vector<std::vector<int32_t>> m12(n, std::vector<int32_t>(n1, -1));
+        std::vector<std::vector<float>> xyz(n, std::vector<float>((size_t)n1 * 3, 0.f));
+        std::vector<std::vector<uint8_t>> status(n, std::vector<uint8_t>(n1, 0));
+        std::vector<int32_t*> pm(n);
+        std::vector<float*> px(n);
+        std::vector<uint8_t*> ps(n);
+        for (int k = 0; k < n; k++) {
+            pm[k] = m12[k].data();
+            px[k] = xyz[k].data();
+            ps[k] = status[k].data();
+        }
+        std::vector<int> n_matches(n, 0), n_created(n, 0);
+        check(orbx_create_new_map_points(ctx_, &KF1, &g1, n, KF2s.data(), g2s.data(), F12s.data(), checkOri ? 1 : 0, 1,
+                                         pm.data(), n_matches.data(), px.data(), ps.data(), n_created.data(), nullptr),
+              "LocalMapping::CreateNewMapPoints");
+        for (int k = 0; k < n; k++)
+            for (int i = 0; i < n1; i++)
+                if (status[k][i] == 1) {
+                    NewPoint p;
+                    p.idx1 = i;
+                    p.idx2 = m12[k][i];
+                    std::memcpy(p.x3D, &xyz[k][(size_t)i * 3], sizeof(p.x3D));
+                    out[k].push_back(p);
+                }
+        return out;
+    }
+
+private:
+    orbx_ctx* ctx_;
+};
+
 }  // namespace ORB_SLAM_AMD

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "orbx_device.h"
+#include "orbx_bow_queue.h"
 #include "orbx_internal.h"
 #include "orbx_match_common.h"
 
@@ -368,17 +369,19 @@ int run_bow(orbx_ctx* ctx, const orbx_bow_view* V1, const orbx_bow_view* V2, int
     return ORBX_OK;
 }
 
+}  // namespace
+
 // One keyframe against n others (modes 1, 2): KF1 uploaded once, each pair's
-// common nodes, one launch of n workgroups, one readback.
-int run_bow_batch(orbx_ctx* ctx, const orbx_bow_view* V1, int n, const orbx_bow_view* V2s, int mode, float nnratio,
-                  int check_ori, const float* F12s, const float* sigma2s, int nlevels, int32_t* const* outs,
-                  int* n_outs)
+// common nodes, one launch of n workgroups (orbx_bow_queue.h).
+int queue_bow_batch(orbx_ctx* ctx, const orbx_bow_view* V1, int n, const orbx_bow_view* V2s, int mode, float nnratio,
+                    int check_ori, const float* F12s, const float* sigma2s, int nlevels, size_t extra_bytes,
+                    const BowAfter* after, BowQueued* q)
 {
-    if (!ctx || n < 0 || (n > 0 && (!V2s || !outs || !n_outs))) return ORBX_ERR_ARG;
+    if (!ctx || n < 0 || (n > 0 && !V2s)) return ORBX_ERR_ARG;
     if (mode == 2 && n > 0 && (!F12s || !sigma2s || nlevels <= 0 || nlevels > kMaxLevels)) return ORBX_ERR_ARG;
     if (!valid_bow(V1, 0)) return ORBX_ERR_ARG;
     for (int k = 0; k < n; k++)
-        if (!valid_bow(&V2s[k], mode == 2 ? nlevels : 0) || (V1->n > 0 && !outs[k])) return ORBX_ERR_ARG;
+        if (!valid_bow(&V2s[k], mode == 2 ? nlevels : 0)) return ORBX_ERR_ARG;
     if (n == 0) return ORBX_OK;
     std::vector<std::vector<int4>> nodes(n);
     for (int k = 0; k < n; k++) {
@@ -414,6 +417,7 @@ int run_bow_batch(orbx_ctx* ctx, const orbx_bow_view* V1, int n, const orbx_bow_
         o[k].n = res(4);
     }
     const size_t o_jobs = res(sizeof(BowArgs) * (size_t)n);
+    const size_t o_extra = res(extra_bytes);
     int r = ensure_scratch(ctx, at);
     if (r != ORBX_OK) return r;
     uint8_t* d = static_cast<uint8_t*>(ctx->scratch);
@@ -458,14 +462,62 @@ int run_bow_batch(orbx_ctx* ctx, const orbx_bow_view* V1, int n, const orbx_bow_
         a.out_n = reinterpret_cast<int32_t*>(d + o[k].n);
     }
     if ((r = put(o_jobs, jobs.data(), sizeof(BowArgs) * (size_t)n))) return r;
-    hipLaunchKernelGGL(k_bow_match_jobs, dim3(n), dim3(kBlock), 0, ctx->stream,
-                       reinterpret_cast<const BowArgs*>(d + o_jobs));
-    ORBX_HIP_CHECK(hipGetLastError());
-    for (int k = 0; k < n; k++) {
-        if (out_len)
-            ORBX_HIP_CHECK(hipMemcpyAsync(outs[k], d + o[k].out, (size_t)out_len * 4, hipMemcpyDeviceToHost, ctx->stream));
-        ORBX_HIP_CHECK(hipMemcpyAsync(&n_outs[k], d + o[k].n, 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (q) {
+        q->k1 = reinterpret_cast<const orbx_keypoint*>(d + o_k1);
+        q->mp1 = d + o_m1;
+        q->n1 = V1->n;
+        q->out_len = out_len;
+        q->extra = d + o_extra;
+        q->k2.resize(n);
+        q->n2.resize(n);
+        q->out.resize(n);
+        q->out_n.resize(n);
+        for (int k = 0; k < n; k++) {
+            q->k2[k] = reinterpret_cast<const orbx_keypoint*>(d + o[k].k2);
+            q->n2[k] = V2s[k].n;
+            q->out[k] = reinterpret_cast<int32_t*>(d + o[k].out);
+            q->out_n[k] = reinterpret_cast<int32_t*>(d + o[k].n);
+        }
     }
+    const BowArgs* djobs = reinterpret_cast<const BowArgs*>(d + o_jobs);
+    if (!after) {
+        hipLaunchKernelGGL(k_bow_match_jobs, dim3(n), dim3(kBlock), 0, ctx->stream, djobs);
+        ORBX_HIP_CHECK(hipGetLastError());
+        return ORBX_OK;
+    }
+    for (int k = 0; k < n; k++) {
+        hipLaunchKernelGGL(k_bow_match_jobs, dim3(1), dim3(kBlock), 0, ctx->stream, djobs + k);
+        ORBX_HIP_CHECK(hipGetLastError());
+        if ((r = (*after)(k)) != ORBX_OK) return r;
+    }
+    return ORBX_OK;
+}
+
+int read_bow_queued(orbx_ctx* ctx, const BowQueued& q, int len, int32_t* const* outs, int* n_outs)
+{
+    for (size_t k = 0; k < q.out.size(); k++) {
+        if (len)
+            ORBX_HIP_CHECK(hipMemcpyAsync(outs[k], q.out[k], (size_t)len * 4, hipMemcpyDeviceToHost, ctx->stream));
+        ORBX_HIP_CHECK(hipMemcpyAsync(&n_outs[k], q.out_n[k], 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return ORBX_OK;
+}
+
+namespace {
+
+// queue_bow_batch and one readback.
+int run_bow_batch(orbx_ctx* ctx, const orbx_bow_view* V1, int n, const orbx_bow_view* V2s, int mode, float nnratio,
+                  int check_ori, const float* F12s, const float* sigma2s, int nlevels, int32_t* const* outs,
+                  int* n_outs)
+{
+    if (n > 0 && (!outs || !n_outs)) return ORBX_ERR_ARG;
+    if (V1 && V1->n > 0)
+        for (int k = 0; k < n; k++)
+            if (!outs[k]) return ORBX_ERR_ARG;
+    BowQueued q;
+    int r = queue_bow_batch(ctx, V1, n, V2s, mode, nnratio, check_ori, F12s, sigma2s, nlevels, 0, nullptr, &q);
+    if (r != ORBX_OK || n <= 0) return r;
+    if ((r = read_bow_queued(ctx, q, q.out_len, outs, n_outs)) != ORBX_OK) return r;
     ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return ORBX_OK;
 }
@@ -609,24 +661,25 @@ extern "C" int orbx_dev_search_by_bow(orbx_ctx* ctx, int slot, int n, const orbx
     return ORBX_OK;
 }
 
-namespace {
+namespace orbx {
 
 // SearchByBoW(KF1, KF2) (mode 1) / SearchForTriangulation (mode 2) of the
 // frame in slot1 against the frames in slots2[0, n): keypoints, descriptors
 // and FeatureVectors where orbx_dev_extract / orbx_dev_undistort /
-// orbx_dev_compute_bow left them; only the map-point states travel.
-int run_bow_slots(orbx_ctx* ctx, int mode, int slot1, const uint8_t* mp1, int n, const int* slots2,
-                  const uint8_t* const* mp2s, float nnratio, int check_ori, const float* F12s, const float* sigma2s,
-                  int nlevels, int32_t* const* outs, int cap, int* n_outs)
+// orbx_dev_compute_bow left them; only the map-point states travel
+// (orbx_bow_queue.h).
+int queue_bow_slots(orbx_ctx* ctx, int mode, int slot1, const uint8_t* mp1, int n, const int* slots2,
+                    const uint8_t* const* mp2s, float nnratio, int check_ori, const float* F12s, const float* sigma2s,
+                    int nlevels, int cap, size_t extra_bytes, const BowAfter* after, BowQueued* q)
 {
     auto ready = [&](int s) {
         return s >= 0 && s < ctx->slots && ctx->bow_dev && s < (int)ctx->bow_ready.size() && ctx->bow_ready[s];
     };
-    if (n < 0 || (n > 0 && (!slots2 || !mp2s || !outs || !n_outs || !mp1))) return ORBX_ERR_ARG;
+    if (n < 0 || (n > 0 && (!slots2 || !mp2s || !mp1))) return ORBX_ERR_ARG;
     if (mode == 2 && n > 0 && (!F12s || !sigma2s || nlevels <= 0 || nlevels > kMaxLevels)) return ORBX_ERR_ARG;
     if (!ready(slot1)) return ORBX_ERR_ARG;
     for (int k = 0; k < n; k++)
-        if (!ready(slots2[k]) || !mp2s[k] || !outs[k]) return ORBX_ERR_ARG;
+        if (!ready(slots2[k]) || !mp2s[k]) return ORBX_ERR_ARG;
     const int nf = ctx->bow_nf;
     if (n > 0 && cap < nf) return ORBX_ERR_CAPACITY;
     if (n == 0) return ORBX_OK;
@@ -656,6 +709,7 @@ int run_bow_slots(orbx_ctx* ctx, int mode, int slot1, const uint8_t* mp1, int n,
         o[k].n = res(4);
     }
     const size_t o_jobs = res(sizeof(BowSlotJob) * (size_t)n);
+    const size_t o_extra = res(extra_bytes);
     int r = ensure_scratch(ctx, at);
     if (r != ORBX_OK) return r;
     uint8_t* d = static_cast<uint8_t*>(ctx->scratch);
@@ -698,15 +752,58 @@ int run_bow_slots(orbx_ctx* ctx, int mode, int slot1, const uint8_t* mp1, int n,
     }
     ORBX_HIP_CHECK(hipMemcpyAsync(d + o_jobs, jobs.data(), sizeof(BowSlotJob) * (size_t)n, hipMemcpyHostToDevice,
                                   ctx->stream));
-    timer_begin(ctx, "bow_match_slot");
-    hipLaunchKernelGGL(k_bow_match_slot, dim3(n), dim3(kBlock), 0, ctx->stream,
-                       reinterpret_cast<const BowSlotJob*>(d + o_jobs));
-    timer_end(ctx, "bow_match_slot");
-    ORBX_HIP_CHECK(hipGetLastError());
-    for (int k = 0; k < n; k++) {
-        ORBX_HIP_CHECK(hipMemcpyAsync(outs[k], d + o[k].out, (size_t)nf * 4, hipMemcpyDeviceToHost, ctx->stream));
-        ORBX_HIP_CHECK(hipMemcpyAsync(&n_outs[k], d + o[k].n, 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (q) {
+        q->k1 = ctx->out_kps + (size_t)slot1 * nf;
+        q->mp1 = d + o_m1;
+        q->n1 = count(slot1);
+        q->out_len = nf;
+        q->extra = d + o_extra;
+        q->k2.resize(n);
+        q->n2.resize(n);
+        q->out.resize(n);
+        q->out_n.resize(n);
+        for (int k = 0; k < n; k++) {
+            q->k2[k] = ctx->out_kps + (size_t)slots2[k] * nf;
+            q->n2[k] = count(slots2[k]);
+            q->out[k] = reinterpret_cast<int32_t*>(d + o[k].out);
+            q->out_n[k] = reinterpret_cast<int32_t*>(d + o[k].n);
+        }
     }
+    const BowSlotJob* djobs = reinterpret_cast<const BowSlotJob*>(d + o_jobs);
+    if (!after) {
+        timer_begin(ctx, "bow_match_slot");
+        hipLaunchKernelGGL(k_bow_match_slot, dim3(n), dim3(kBlock), 0, ctx->stream, djobs);
+        timer_end(ctx, "bow_match_slot");
+        ORBX_HIP_CHECK(hipGetLastError());
+        return ORBX_OK;
+    }
+    for (int k = 0; k < n; k++) {
+        timer_begin(ctx, "bow_match_slot");
+        hipLaunchKernelGGL(k_bow_match_slot, dim3(1), dim3(kBlock), 0, ctx->stream, djobs + k);
+        timer_end(ctx, "bow_match_slot");
+        ORBX_HIP_CHECK(hipGetLastError());
+        if ((r = (*after)(k)) != ORBX_OK) return r;
+    }
+    return ORBX_OK;
+}
+
+}  // namespace orbx
+
+namespace {
+
+// queue_bow_slots and one readback.
+int run_bow_slots(orbx_ctx* ctx, int mode, int slot1, const uint8_t* mp1, int n, const int* slots2,
+                  const uint8_t* const* mp2s, float nnratio, int check_ori, const float* F12s, const float* sigma2s,
+                  int nlevels, int32_t* const* outs, int cap, int* n_outs)
+{
+    if (n > 0 && (!outs || !n_outs)) return ORBX_ERR_ARG;
+    for (int k = 0; k < n; k++)
+        if (!outs[k]) return ORBX_ERR_ARG;
+    BowQueued q;
+    int r = queue_bow_slots(ctx, mode, slot1, mp1, n, slots2, mp2s, nnratio, check_ori, F12s, sigma2s, nlevels, cap, 0,
+                            nullptr, &q);
+    if (r != ORBX_OK || n <= 0) return r;
+    if ((r = read_bow_queued(ctx, q, q.out_len, outs, n_outs)) != ORBX_OK) return r;
     ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     for (int k = 0; k < n; k++)
         if (n_outs[k] < 0) return ORBX_ERR_UNSUPPORTED;

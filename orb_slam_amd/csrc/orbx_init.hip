@@ -30,12 +30,11 @@
 
 #include "orbx_device.h"
 #include "orbx_internal.h"
+#include "orbx_jacobi.h"
 
 namespace orbx {
 
 constexpr int kInitMaxIter = 1024;
-constexpr int kInitSweeps = 40;            // Jacobi sweep cap (convergence takes 6-9)
-constexpr double kInitTol = 8.9e-16;       // 4 eps: rotation threshold on |a_p . a_q| / (|a_p| |a_q|)
 
 struct InitHdr {
     int32_t n, best_h, best_f, pad0;
@@ -265,52 +264,6 @@ __device__ inline double row_sum16(double x)
     x += row_dpp<0x141>(x);   // row_half_mirror: the other quad of the half row
     x += row_dpp<0x140>(x);   // row_mirror: the other half row
     return x;
-}
-
-// Reciprocal and reciprocal square root from the hardware estimates and two
-// Newton steps: a few units of FP64 round-off, which is all a Jacobi rotation
-// needs (c^2 + s^2 = 1 to round-off keeps V orthogonal; the angle's error
-// only leaves a smaller off-diagonal for the next sweep).  With the IEEE
-// divide and square root sequences in their place the solve took 1.5 times
-// as long.
-__device__ inline double fast_rcp(double x)
-{
-    double y = __builtin_amdgcn_rcp(x);
-    y = fma(fma(-x, y, 1.0), y, y);
-    y = fma(fma(-x, y, 1.0), y, y);
-    return y;
-}
-
-__device__ inline double fast_rsq(double x)
-{
-    double y = __builtin_amdgcn_rsq(x);
-    const double h = 0.5 * x;
-    y = fma(fma(-(h * y), y, 0.5), y, y);
-    y = fma(fma(-(h * y), y, 0.5), y, y);
-    return y;
-}
-
-// Whether columns with Gram entries al, be, ga still want a rotation:
-// |ga| > kInitTol sqrt(al be), and neither column is below round-off of the
-// whole matrix (floor = (eps |A|_F)^2).  A column that small is a null vector
-// to FP64 backward error already; its products with the others are noise that
-// never settles, and without the floor every 8x9 system -- which always has
-// such a column -- ran to the sweep cap (40 sweeps where 7 converge).
-__device__ inline bool jacobi_wants(double al, double be, double ga, double floor)
-{
-    return ga != 0.0 && ga * ga > (kInitTol * kInitTol) * (al * be) && al >= floor && be >= floor;
-}
-constexpr double kInitFloor = 4.93e-32;   // eps^2
-
-// Hestenes rotation of columns p, q with Gram entries al, be, ga.
-__device__ inline void jacobi_cs(double al, double be, double ga, double& c, double& s)
-{
-    double zeta = (be - al) * fast_rcp(2.0 * ga);
-    zeta = fmin(fmax(zeta, -1e100), 1e100);   // a negligible ga: the identity, without inf - inf
-    const double w = 1.0 + zeta * zeta;
-    const double t = copysign(fast_rcp(fabs(zeta) + w * fast_rsq(w)), zeta);
-    c = fast_rsq(1.0 + t * t);
-    s = c * t;
 }
 
 // Fn = U diag(s1, s2, 0) V^T of the 3x3 Fpre: one-sided Jacobi on its columns
