@@ -49,8 +49,12 @@ extern "C" {
  *      orbx_dev_init_models, orbx_dev_read_init_models); additions only.
  *   7: new map points (orbx_kf_geom, orbx_triangulate_matches,
  *      orbx_create_new_map_points, orbx_dev_create_new_map_points);
+ *      additions only.
+ *   8: the end of map initialisation (orbx_reconstruct_query,
+ *      orbx_init_reconstruct, orbx_init_reconstruct_batch,
+ *      orbx_dev_init_reconstruct, orbx_dev_read_init_reconstruct);
  *      additions only. */
-#define ORBX_ABI_VERSION 7
+#define ORBX_ABI_VERSION 8
 int orbx_abi_version(void);
 
 #define ORBX_OK               0
@@ -329,7 +333,7 @@ int orbx_search_for_initialization(orbx_ctx* ctx, const orbx_frame_view* F1,
  * T2t*Fn*T1, CheckHomography / CheckFundamental (:303-466) and the selection
  * of the first strictly greater score (FindHomography :122-170,
  * FindFundamental :173-221), all on the device.  The caller goes on with
- * `if(RH>0.40)` (:113) and ReconstructH / ReconstructF on the host.
+ * `if(RH>0.40)` (:113) and orbx_init_reconstruct below.
  * Everything is the reference's float arithmetic operation by operation but
  * the two cv::SVDecomp null vectors, the 3x3 inverses and the denormalising
  * products, which are FP64 rounded once to float; the
@@ -379,6 +383,71 @@ int orbx_init_models_batch(orbx_ctx* ctx, int B, orbx_init_query* qs);   /* one 
 int orbx_dev_init_models(orbx_ctx* ctx, int first, int count, int seq_len,
                          float sigma, int max_iter, const int32_t* draws);
 int orbx_dev_read_init_models(orbx_ctx* ctx, int slot, orbx_init_query* out);
+
+/* The end of Initializer::Initialize (src/Initializer.cc:113-119):
+ * ReconstructH (:570-730) or ReconstructF (:468-568) with CheckRT (:796-905),
+ * Triangulate (:732-745) and DecomposeE (:907-927), all on the device: the
+ * motion hypotheses (8 of Faugeras' decomposition of invK*H21*K, or 4 of
+ * DecomposeE on K.t()*F21*K), CheckRT of every hypothesis over every inlier
+ * match, and the reference's decision.  Everything is the reference's float
+ * arithmetic operation by operation but what goes through OpenCV -- the 3x3
+ * SVD, the 4x4 null vector of Triangulate, the float matrix products, norm,
+ * dot and determinant -- which DESIGN.md section 4 defines (FP64, rounded
+ * once).  The signs and, inside a pair of equal singular values, the columns
+ * of the SVD are unspecified; they permute the hypothesis list and nothing
+ * else, so n_good, parallax, R_all, t_all and best are in the order the
+ * device's own decomposition gives.  The reference's own float expressions
+ * (:606-614, :649-651, :867-881) follow orbx_set_fp_contract, read at the call.
+ * Arguments are checked before any device work: a null context, query or
+ * required pointer, a model outside 0..1, sigma <= 0 or a match index >= n2
+ * is ORBX_ERR_ARG; cap < n1 is ORBX_ERR_CAPACITY; a frame of more than 4096
+ * keypoints ORBX_ERR_UNSUPPORTED.  N == 0 returns ORBX_OK with ok = 0. */
+typedef struct {
+    /* in */
+    const orbx_keypoint* keys1; int n1;     /* mvKeys1 */
+    const orbx_keypoint* keys2; int n2;     /* mvKeys2 */
+    const int32_t* matches12;               /* n1, as orbx_init_query */
+    const uint8_t* inliers;                 /* N = number of matches12 >= 0: vbMatchesInliers by match index */
+    int model;                              /* 0: ReconstructH (M21 = H21), 1: ReconstructF (M21 = F21) */
+    const float* M21;                       /* 9, row-major */
+    const float* cam;                       /* fx, fy, cx, cy (mK) */
+    float sigma;                            /* mSigma: th2 = 4.0*sigma*sigma as the reference forms it */
+    float min_parallax; int min_triangulated;   /* 1.0, 50 (:114, :116) */
+    /* out */
+    int ok;                                 /* the function's return value */
+    int n_inliers;                          /* N of :471-474 / :573-576 */
+    int n_hyp;                              /* 4 (F), 8 (H), 0 when H returns at :595-598 */
+    int best;                               /* winning hypothesis, -1 when !ok */
+    float R21[9], t21[3];                   /* untouched when !ok */
+    int32_t n_good[8]; float parallax[8];   /* CheckRT's results per hypothesis */
+    float* p3d; uint8_t* triangulated; int cap;   /* n1 x 3, n1: vP3D / vbTriangulated of the winner; all zero when !ok */
+    /* optional taps (may be NULL) */
+    float* svd;                             /* 21: U (9), w (3), Vt (9) of the 3x3 decomposition */
+    float* R_all; float* t_all;             /* 8 x 9, 8 x 3 */
+    float* v4;                              /* n_hyp x N x 4: Triangulate's null vector, written where inliers[i] */
+    float* cos_parallax;                    /* n_hyp x N: NaN where the match did not reach :886 */
+} orbx_reconstruct_query;
+
+int orbx_init_reconstruct(orbx_ctx* ctx, orbx_reconstruct_query* q);
+int orbx_init_reconstruct_batch(orbx_ctx* ctx, int B, orbx_reconstruct_query* qs);   /* one upload, one read-back */
+
+/* Device-resident, after orbx_dev_init_models on the same slot range: per pair
+ * the compacted matches, RH, H21 or F21 and the matching inlier array are read
+ * where that run left them; the model is H where RH > rh_threshold in float
+ * (the reference compares the float RH with the double 0.40, which the float
+ * below 0.40f reproduces for every RH) and F otherwise; sigma is the models
+ * run's.  A pair whose models run had no winner (best_h or best_f -1, or
+ * N < 8) gives ok = 0 and n_hyp = 0.  The kernels run asynchronously on the
+ * context stream; results stay in HBM until read or until the next run (of
+ * either kind).  orbx_dev_read_init_reconstruct fills the out fields and taps
+ * of `out` (p3d / triangulated / cap and the tap pointers are read from it,
+ * the in fields are ignored; cap below the pair's n1 is ORBX_ERR_CAPACITY,
+ * the v4 and cos_parallax taps hold n_hyp x N entries with N <= n1) and the
+ * model that was chosen; before a run, on a slot outside the run or on a
+ * sequence-start slot it is ORBX_ERR_ARG. */
+int orbx_dev_init_reconstruct(orbx_ctx* ctx, int first, int count, int seq_len, const float* cam,
+                              float rh_threshold, float min_parallax, int min_triangulated);
+int orbx_dev_read_init_reconstruct(orbx_ctx* ctx, int slot, orbx_reconstruct_query* out, int* model);
 
 /* ORBmatcher::WindowSearch (src/ORBmatcher.cc:409-516).
  * f1_mp: per F1 keypoint, 1 if F1.mvpMapPoints[i1] is set and not bad.

@@ -103,6 +103,76 @@ def init_result(q, keep, taps=False):
     return r
 
 
+# The reference compares the float RH with the double 0.40 (src/Initializer.cc:113), which holds for RH >= 0.40f;
+# orbx_dev_init_reconstruct compares floats, so the float just below 0.40f reproduces it for every RH.
+RH_THRESHOLD = float(np.nextafter(np.float32(0.40), np.float32(0)))
+
+
+class ReconstructQuery(ctypes.Structure):
+    """orbx_reconstruct_query (include/orbx.h)."""
+    _fields_ = [("keys1", ctypes.c_void_p), ("n1", ctypes.c_int), ("keys2", ctypes.c_void_p), ("n2", ctypes.c_int),
+                ("matches12", ctypes.c_void_p), ("inliers", ctypes.c_void_p), ("model", ctypes.c_int),
+                ("M21", ctypes.c_void_p), ("cam", ctypes.c_void_p), ("sigma", ctypes.c_float),
+                ("min_parallax", ctypes.c_float), ("min_triangulated", ctypes.c_int),
+                ("ok", ctypes.c_int), ("n_inliers", ctypes.c_int), ("n_hyp", ctypes.c_int), ("best", ctypes.c_int),
+                ("R21", ctypes.c_float * 9), ("t21", ctypes.c_float * 3),
+                ("n_good", ctypes.c_int32 * 8), ("parallax", ctypes.c_float * 8),
+                ("p3d", ctypes.c_void_p), ("triangulated", ctypes.c_void_p), ("cap", ctypes.c_int),
+                ("svd", ctypes.c_void_p), ("R_all", ctypes.c_void_p), ("t_all", ctypes.c_void_p),
+                ("v4", ctypes.c_void_p), ("cos_parallax", ctypes.c_void_p)]
+
+
+def reconstruct_query(keys1, keys2, matches12, inliers, model, M21, cam, sigma=1.0, min_parallax=1.0,
+                      min_triangulated=50, taps=False, cap=None, n_max=None):
+    """A ReconstructQuery over numpy arrays and the arrays it points to (keep
+    both alive while the query is used): (query, keep).  keys1 None: an
+    output-only query of a device-resident pair (cap keypoints, n_max matches)."""
+    keep = {}
+    q = ReconstructQuery()
+    if keys1 is not None:
+        keep["keys1"] = np.ascontiguousarray(keys1, KEYPOINT)
+        keep["keys2"] = np.ascontiguousarray(keys2, KEYPOINT)
+        keep["matches12"] = np.ascontiguousarray(matches12, np.int32)
+        keep["inliers"] = np.ascontiguousarray(inliers, np.uint8)
+        keep["M21"] = np.ascontiguousarray(M21, np.float32).reshape(-1)
+        keep["cam"] = np.ascontiguousarray(cam, np.float32).reshape(-1)
+        q.keys1, q.n1 = keep["keys1"].ctypes.data, len(keep["keys1"])
+        q.keys2, q.n2 = keep["keys2"].ctypes.data, len(keep["keys2"])
+        q.matches12, q.inliers = keep["matches12"].ctypes.data, keep["inliers"].ctypes.data
+        q.M21, q.cam = keep["M21"].ctypes.data, keep["cam"].ctypes.data
+        q.model = int(model)
+        n_max = int(np.count_nonzero(keep["matches12"] >= 0))
+        if cap is None:
+            cap = len(keep["keys1"])
+    q.sigma, q.min_parallax, q.min_triangulated = sigma, min_parallax, min_triangulated
+    q.cap = max(int(cap), 0)
+    keep["p3d"], keep["triangulated"] = np.zeros((max(q.cap, 1), 3), np.float32), np.zeros(max(q.cap, 1), np.uint8)
+    q.p3d, q.triangulated = keep["p3d"].ctypes.data, keep["triangulated"].ctypes.data
+    keep["n_max"] = int(n_max)
+    if taps:
+        for name, shape in (("svd", 21), ("R_all", (8, 9)), ("t_all", (8, 3)), ("v4", (8 * max(n_max, 1), 4)),
+                            ("cos_parallax", 8 * max(n_max, 1))):
+            keep[name] = np.zeros(shape, np.float32)
+            setattr(q, name, keep[name].ctypes.data)
+    return q, keep
+
+
+def reconstruct_result(q, keep, taps=False, n1=None, n_matches=None):
+    """The out fields (and taps) of a filled ReconstructQuery as a dict; v4
+    and cos_parallax as (n_hyp, N, 4) and (n_hyp, N)."""
+    n1 = q.n1 if n1 is None else n1
+    r = dict(ok=q.ok, n_inliers=q.n_inliers, n_hyp=q.n_hyp, best=q.best,
+             R21=np.array(q.R21, np.float32) if q.ok else None, t21=np.array(q.t21, np.float32) if q.ok else None,
+             n_good=np.array(q.n_good, np.int32), parallax=np.array(q.parallax, np.float32),
+             p3d=keep["p3d"][:n1].copy(), triangulated=keep["triangulated"][:n1].copy())
+    if taps:
+        N = keep["n_max"] if n_matches is None else n_matches
+        r["svd"], r["R_all"], r["t_all"] = keep["svd"], keep["R_all"], keep["t_all"]
+        r["v4"] = keep["v4"][:q.n_hyp * N].reshape(q.n_hyp, N, 4)
+        r["cos_parallax"] = keep["cos_parallax"][:q.n_hyp * N].reshape(q.n_hyp, N)
+    return r
+
+
 class KfGeom(ctypes.Structure):
     """orbx_kf_geom (include/orbx.h)."""
     _fields_ = [("Rcw", ctypes.c_void_p), ("tcw", ctypes.c_void_p), ("Ow", ctypes.c_void_p), ("cam", ctypes.c_void_p),
@@ -260,6 +330,10 @@ def _declare(L):
         "orbx_init_models_batch": ([vp, i, vp], i),
         "orbx_dev_init_models": ([vp, i, i, i, f, i, vp], i),
         "orbx_dev_read_init_models": ([vp, i, vp], i),
+        "orbx_init_reconstruct": ([vp, vp], i),
+        "orbx_init_reconstruct_batch": ([vp, i, vp], i),
+        "orbx_dev_init_reconstruct": ([vp, i, i, i, vp, f, f, i], i),
+        "orbx_dev_read_init_reconstruct": ([vp, i, vp, ip], i),
         "orbx_triangulate_matches": ([vp, vp, i, vp, i, vp, vp, vp, vp, vp, vp, vp, vp], i),
         "orbx_create_new_map_points": ([vp, vp, vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp], i),
         "orbx_dev_create_new_map_points": ([vp, i, vp, vp, i, vp, vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp, i], i),
@@ -599,6 +673,59 @@ class Context:
                              cap=self.nfeatures)
         _check(lib().orbx_dev_read_init_models(self._h, slot, ctypes.byref(q)), "orbx_dev_read_init_models")
         return init_result(q, keep, taps)
+
+    # --- Initializer: ReconstructH / ReconstructF ---------------------------
+    def init_reconstruct(self, keys1, keys2, matches12, inliers, model, M21, cam, sigma=1.0, min_parallax=1.0,
+                         min_triangulated=50, taps=False):
+        """Initializer::ReconstructH (model 0) / ReconstructF (model 1)
+        (orbx_init_reconstruct): a dict of ok, n_inliers, n_hyp, best, R21 /
+        t21 (None when not ok), n_good, parallax, p3d, triangulated and, with
+        taps, svd, R_all, t_all, v4 and cos_parallax."""
+        q, keep = reconstruct_query(keys1, keys2, matches12, inliers, model, M21, cam, sigma, min_parallax,
+                                    min_triangulated, taps)
+        _check(lib().orbx_init_reconstruct(self._h, ctypes.byref(q)), "orbx_init_reconstruct")
+        return reconstruct_result(q, keep, taps)
+
+    def init_reconstruct_batch(self, queries, taps=False):
+        """orbx_init_reconstruct_batch over argument tuples of
+        init_reconstruct: one upload, one read-back; a list of dicts."""
+        built = [reconstruct_query(*a, taps=taps) for a in queries]
+        arr = (ReconstructQuery * len(built))(*[b[0] for b in built])
+        _check(lib().orbx_init_reconstruct_batch(self._h, len(built), arr), "orbx_init_reconstruct_batch")
+        return [reconstruct_result(arr[k], built[k][1], taps) for k in range(len(built))]
+
+    def dev_init_reconstruct(self, first, count, seq_len, cam, rh_threshold=None, min_parallax=1.0,
+                             min_triangulated=50):
+        """orbx_dev_init_reconstruct: the reconstruction of every pair of the
+        last dev_init_models run on the same slots, from what that run left
+        on the device.  rh_threshold None: RH_THRESHOLD, with which the
+        device's float RH > rh_threshold is the reference's RH > 0.40."""
+        if rh_threshold is None:
+            rh_threshold = RH_THRESHOLD
+        c = np.ascontiguousarray(cam, np.float32).reshape(-1)
+        _check(lib().orbx_dev_init_reconstruct(self._h, first, count, seq_len, _ptr(c), rh_threshold, min_parallax,
+                                               min_triangulated), "orbx_dev_init_reconstruct")
+
+    def read_init_reconstruct(self, slot, taps=False, n_matches=None):
+        """orbx_dev_read_init_reconstruct: the dict of init_reconstruct for
+        the pair (slot - 1, slot) of the last dev_init_reconstruct run, with
+        the chosen `model`.  The taps by match index are laid out by the
+        pair's number of matches, which is read from the models run
+        (read_init_models); a caller that passes n_matches must pass that
+        number.  p3d / triangulated have one entry per feature of the context."""
+        if taps:
+            n = self.read_init_models(slot)["n_matches"]
+            if n_matches is not None and n_matches != n:
+                raise ValueError(f"read_init_reconstruct: n_matches {n_matches}, the pair has {n}")
+            n_matches = n
+        q, keep = reconstruct_query(None, None, None, None, 0, None, None, taps=taps, cap=self.nfeatures,
+                                    n_max=self.nfeatures)
+        model = ctypes.c_int(-1)
+        _check(lib().orbx_dev_read_init_reconstruct(self._h, slot, ctypes.byref(q), ctypes.byref(model)),
+               "orbx_dev_read_init_reconstruct")
+        r = reconstruct_result(q, keep, taps, n1=self.nfeatures, n_matches=n_matches)
+        r["model"] = model.value
+        return r
 
     # --- LocalMapping::CreateNewMapPoints ----------------------------------
     def triangulate_matches(self, keys1, g1, keys2, g2s, matches12, v4=False):

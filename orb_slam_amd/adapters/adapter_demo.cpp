@@ -2,7 +2,7 @@
 // and LocalMapping would: extract two frames of a shifted synthetic image,
 // SearchForInitialization between them, the initialisation models of those
 // matches (Initializer::FindModels beside the plain C call fed the same rand()
-// sequence), brute-force matching, and one local BA on a tiny synthetic problem.  Prints one JSON line.  Exit codes: 0 ok,
+// sequence), the whole Initializer::Initialize beside orbx_init_reconstruct, brute-force matching, and one local BA on a tiny synthetic problem.  Prints one JSON line.  Exit codes: 0 ok,
 // 3 device path unavailable (orbx_error), 1 other failure.
 #include <cmath>
 #include <cstdio>
@@ -105,6 +105,89 @@ int main()
             n_in_h += cH[i];
             n_in_f += cF[i];
         }
+        // Initializer::Initialize beside the plain C reconstruction fed the models just read
+        const float K[9] = {500.f, 0.f, 320.f, 0.f, 500.f, 240.f, 0.f, 0.f, 1.f};
+        float R21[9] = {0}, t21[3] = {0};
+        std::vector<Point3f> vP3D;
+        std::vector<bool> vbTri;
+        std::srand(1);
+        const bool init_ok = initializer.Initialize(F2.keys_un, m12, K, R21, t21, vP3D, vbTri);
+        const float camK[4] = {K[0], K[4], K[2], K[5]};
+        std::vector<float> p3d(F1.keys_un.size() * 3 + 3);
+        std::vector<uint8_t> tri(F1.keys_un.size() + 1);
+        orbx_reconstruct_query rq;
+        std::memset(&rq, 0, sizeof(rq));
+        rq.keys1 = q.keys1;
+        rq.n1 = q.n1;
+        rq.keys2 = q.keys2;
+        rq.n2 = q.n2;
+        rq.matches12 = q.matches12;
+        rq.model = q.RH > 0.40 ? 0 : 1;
+        rq.inliers = rq.model ? cF.data() : cH.data();
+        rq.M21 = rq.model ? q.F21 : q.H21;
+        rq.cam = camK;
+        rq.sigma = 1.0f;
+        rq.min_parallax = 1.0f;
+        rq.min_triangulated = 50;
+        rq.p3d = p3d.data();
+        rq.triangulated = tri.data();
+        rq.cap = rq.n1;
+        bool rec_same = rq.model == initializer.mModel && vP3D.size() == F1.keys_un.size();
+        int n_tri = 0;
+        if ((rq.model ? q.best_f : q.best_h) >= 0) {
+            check(orbx_init_reconstruct(ex.context(), &rq), "orbx_init_reconstruct");
+            rec_same = rec_same && (rq.ok != 0) == init_ok && rq.best == initializer.mBestHypothesis;
+            if (rq.ok) rec_same = rec_same && std::memcmp(rq.R21, R21, sizeof(R21)) == 0 && std::memcmp(rq.t21, t21, sizeof(t21)) == 0;
+            for (int i = 0; i < rq.n1 && rec_same; i++) {
+                rec_same = std::memcmp(&p3d[3 * i], &vP3D[i], 12) == 0 && vbTri[i] == (tri[i] != 0);
+                n_tri += tri[i];
+            }
+        } else {
+            rec_same = rec_same && !init_ok;
+        }
+        // an accepted pair: 240 points of a cloud 3-12 m away, projected before and after a sideways motion
+        // (a rotation of 0.08 rad about y, t = (-0.6, 0.05, 0.1)), keypoint i matched with keypoint i
+        std::vector<KeyPoint> sk1, sk2;
+        std::vector<int> sm;
+        const double ang = 0.08, ca = std::cos(ang), sa = std::sin(ang), tt[3] = {-0.6, 0.05, 0.1};
+        uint32_t ls = 7;
+        auto rnd = [&ls]() {
+            ls = ls * 1664525u + 1013904223u;
+            return (double)(ls >> 8) / 16777216.0;
+        };
+        for (int i = 0; i < 240; i++) {
+            const double u = 20.0 + 600.0 * rnd(), v = 20.0 + 440.0 * rnd(), z = 3.0 + 9.0 * rnd();
+            const double X = (u - 320.0) / 500.0 * z, Y = (v - 240.0) / 500.0 * z;
+            const double xc = ca * X + sa * z + tt[0], yc = Y + tt[1], zc = -sa * X + ca * z + tt[2];
+            KeyPoint a;
+            std::memset(&a, 0, sizeof(a));
+            a.size = 31.f;
+            a.class_id = -1;
+            KeyPoint b = a;
+            a.x = (float)u;
+            a.y = (float)v;
+            b.x = (float)(500.0 * xc / zc + 320.0);
+            b.y = (float)(500.0 * yc / zc + 240.0);
+            sk1.push_back(a);
+            sk2.push_back(b);
+            sm.push_back(i);
+        }
+        Initializer scene_init(sk1, 1.0f, 200, ex.context());
+        float sR[9] = {0}, st[3] = {0};
+        std::vector<Point3f> sP3D;
+        std::vector<bool> sTri;
+        std::srand(2);
+        const bool scene_ok = scene_init.Initialize(sk2, sm, K, sR, st, sP3D, sTri);
+        int scene_tri = 0, scene_front = 0;
+        for (size_t i = 0; i < sTri.size(); i++)
+            if (sTri[i]) {
+                scene_tri++;
+                scene_front += sP3D[i].z > 0.f;
+            }
+        // the recovered translation is the true one up to scale, the rotation the true one
+        const double tn = std::sqrt(tt[0] * tt[0] + tt[1] * tt[1] + tt[2] * tt[2]);
+        const double t_cos = scene_ok ? (st[0] * tt[0] + st[1] * tt[1] + st[2] * tt[2]) / tn : 0.0;
+        const double r_trace = scene_ok ? (sR[0] * ca + sR[2] * sa + sR[4] - sR[6] * sa + sR[8] * ca) : 0.0;
         std::vector<int> mbf;
         const int n_bf = matcher.MatchBruteForce(F1.desc, F2.desc, mbf);
         // tiny BA: 3 keyframes (first fixed) observing 60 points
@@ -160,11 +243,16 @@ int main()
         std::printf("{\"n1\": %zu, \"n2\": %zu, \"levels\": %d, \"scale\": %.3f, \"init_matches\": %d, "
                     "\"bf_matches\": %d, \"ba_iterations\": [%d, %d], \"ba_chi2\": [%.6g, %.6g], "
                     "\"pose_inliers\": %d, \"pose_edges\": %d, \"pose_tx\": %.6g, \"init_same\": %d, "
-                    "\"init_n\": %d, \"init_best\": [%d, %d], \"init_rh\": %.6g, \"init_inliers\": [%d, %d]}\n",
+                    "\"init_n\": %d, \"init_best\": [%d, %d], \"init_rh\": %.6g, \"init_inliers\": [%d, %d], "
+                    "\"rec_same\": %d, \"rec_model\": %d, \"rec_ok\": %d, \"rec_hyp\": %d, \"rec_good\": %d, "
+                    "\"rec_triangulated\": %d, \"scene_ok\": %d, \"scene_model\": %d, \"scene_triangulated\": %d, "
+                    "\"scene_in_front\": %d, \"scene_t_cos\": %.6f, \"scene_r_trace\": %.6f}\n",
                     F1.keys_un.size(), F2.keys_un.size(), ex.GetLevels(), ex.GetScaleFactor(), n_init, n_bf,
                     P.stats.iterations[0], P.stats.iterations[1], P.stats.chi2_initial[0], P.stats.chi2_final[1],
                     n_pose_inliers, n_mp, PF.Tcw[3], init_same ? 1 : 0, q.n_matches, q.best_h, q.best_f, (double)q.RH,
-                    n_in_h, n_in_f);
+                    n_in_h, n_in_f, rec_same ? 1 : 0, rq.model, init_ok ? 1 : 0, rq.n_hyp,
+                    rq.n_hyp > 0 && rq.best >= 0 ? rq.n_good[rq.best] : 0, n_tri, scene_ok ? 1 : 0, scene_init.mModel,
+                    scene_tri, scene_front, t_cos, r_trace);
         return 0;
     } catch (const orbx_error& e) {
         std::fprintf(stderr, "%s\n", e.what());

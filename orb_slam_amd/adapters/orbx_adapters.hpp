@@ -401,10 +401,13 @@ public:
 // ---------------------------------------------------------------------------
 // Initializer (src/Initializer.cc:32-221): the constructor's reference
 // keypoints, sigma and iterations, and the two model searches Initialize runs
-// on two boost::threads (:97-107) as one device call.  The caller goes on
-// with `if(RH>0.40)` and ReconstructH / ReconstructF (:113-116), which take
-// exactly these outputs.
+// on two boost::threads (:97-107) as one device call; Initialize goes on with
+// `if(RH>0.40)` and ReconstructH / ReconstructF (:113-116) as a second one.
 // ---------------------------------------------------------------------------
+struct Point3f {
+    float x, y, z;
+};
+
 class Initializer {
 public:
     // Initializer(const Frame& ReferenceFrame, float sigma = 1.0, int iterations = 200) (:32-42),
@@ -461,7 +464,64 @@ public:
         return q.RH;
     }
 
+    // bool Initialize(const Frame& CurrentFrame, const vector<int>& vMatches12, cv::Mat& R21, cv::Mat& t21,
+    //                 vector<cv::Point3f>& vP3D, vector<bool>& vbTriangulated) (:44-119), with
+    // CurrentFrame.mvKeysUn and the calibration matrix mK (3x3 row-major) passed as such: FindModels, the ratio
+    // test, then ReconstructH or ReconstructF with minParallax 1.0 and minTriangulated 50 as one device call.
+    // R21 (3x3 row-major) and t21 keep their content when the function returns false.
+    bool Initialize(const std::vector<KeyPoint>& keys2, const std::vector<int>& vMatches12, const float K[9],
+                    float R21[9], float t21[3], std::vector<Point3f>& vP3D, std::vector<bool>& vbTriangulated)
+    {
+        mModel = -1;
+        mBestHypothesis = -1;
+        std::vector<bool> inH, inF;
+        float SH = 0.f, SF = 0.f, H[9] = {0}, F[9] = {0};
+        const float RH = FindModels(keys2, vMatches12, inH, SH, H, inF, SF, F);
+        mModel = RH > 0.40 ? 0 : 1;   // :113
+        const std::vector<bool>& in = mModel ? inF : inH;
+        std::vector<uint8_t> inliers(in.size() + 1);
+        for (size_t i = 0; i < in.size(); i++) inliers[i] = in[i];
+        std::vector<int32_t> m12(vMatches12.begin(), vMatches12.end());
+        const int n1 = (int)mvKeys1.size();
+        const float cam[4] = {K[0], K[4], K[2], K[5]};
+        std::vector<float> p3d((size_t)n1 * 3 + 3);
+        std::vector<uint8_t> tri((size_t)n1 + 1);
+        orbx_reconstruct_query q;
+        std::memset(&q, 0, sizeof(q));
+        q.keys1 = mvKeys1.data();
+        q.n1 = n1;
+        q.keys2 = keys2.data();
+        q.n2 = (int)keys2.size();
+        q.matches12 = m12.data();
+        q.inliers = inliers.data();
+        q.model = mModel;
+        q.M21 = mModel ? F : H;
+        q.cam = cam;
+        q.sigma = mSigma;
+        q.min_parallax = 1.0f;
+        q.min_triangulated = 50;
+        q.p3d = p3d.data();
+        q.triangulated = tri.data();
+        q.cap = n1;
+        vP3D.assign(n1, Point3f{0.f, 0.f, 0.f});
+        vbTriangulated.assign(n1, false);
+        // without a winning model of the chosen kind there is nothing to decompose
+        if ((mModel ? mBestF : mBestH) < 0) return false;
+        check(orbx_init_reconstruct(ctx_, &q), "Initializer::Initialize");
+        mBestHypothesis = q.best;
+        if (!q.ok) return false;
+        std::memcpy(R21, q.R21, sizeof(q.R21));
+        std::memcpy(t21, q.t21, sizeof(q.t21));
+        for (int i = 0; i < n1; i++) {
+            vP3D[i] = Point3f{p3d[3 * i], p3d[3 * i + 1], p3d[3 * i + 2]};
+            vbTriangulated[i] = tri[i] != 0;
+        }
+        return true;
+    }
+
     int mBestH = -1, mBestF = -1;   // winning iterations of the last call (-1: none)
+    int mModel = -1;                // 0: ReconstructH, 1: ReconstructF ran in the last Initialize
+    int mBestHypothesis = -1;       // its winning motion hypothesis (-1: none)
 
 private:
     std::vector<KeyPoint> mvKeys1;

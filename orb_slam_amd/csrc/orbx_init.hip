@@ -30,100 +30,11 @@
 
 #include "orbx_device.h"
 #include "orbx_internal.h"
+#include "orbx_init_layout.h"
 #include "orbx_jacobi.h"
+#include "orbx_linalg.h"
 
 namespace orbx {
-
-constexpr int kInitMaxIter = 1024;
-
-struct InitHdr {
-    int32_t n, best_h, best_f, pad0;
-    float SH, SF, RH, pad1;
-    float H21[9], F21[9], T1[9], T2[9];
-    float norm[8];   // mean x, mean y, sX, sY of frame 1, then of frame 2
-};
-
-// One pair's inputs, as element offsets into the call's keypoint / match /
-// count / draw arrays (device-resident form: the context's slot buffers).
-struct InitPair {
-    long long k1_off, k2_off, m_off, draw_off;
-    int32_t n1, n2;       // used when cnt1 / cnt2 < 0
-    int32_t cnt1, cnt2;   // index into the count array (slot), or -1
-    int32_t max_iter;
-    float sigma;
-};
-
-// Byte offsets inside one pair's result block.
-struct InitLayout {
-    long long stride;
-    int o_pairs, o_xy, o_sets, o_Hn, o_Fn, o_H21, o_H12, o_F21, o_sh, o_sf, o_inh, o_inf;
-    int M, cap;   // iterations and matches the block is sized for
-};
-
-static InitLayout make_layout(int M, int cap)
-{
-    InitLayout L;
-    long long o = 0;
-    auto take = [&](long long bytes) {
-        const long long r = o;
-        o += (bytes + 15) & ~15ll;
-        return (int)r;
-    };
-    take(sizeof(InitHdr));
-    L.o_pairs = take((long long)cap * 8);
-    L.o_xy = take((long long)cap * 16);
-    L.o_sets = take((long long)M * 32);
-    L.o_Hn = take((long long)M * 36);
-    L.o_Fn = take((long long)M * 36);
-    L.o_H21 = take((long long)M * 36);
-    L.o_H12 = take((long long)M * 36);
-    L.o_F21 = take((long long)M * 36);
-    L.o_sh = take((long long)M * 4);
-    L.o_sf = take((long long)M * 4);
-    L.o_inh = take(cap);
-    L.o_inf = take(cap);
-    L.stride = o;
-    L.M = M;
-    L.cap = cap;
-    return L;
-}
-
-// ---------------------------------------------------------------------------
-// Defined 3x3 arithmetic: FP64 from the float entries,
-// rounded once.  tests/init_numpy.py restates both in the same order.
-// ---------------------------------------------------------------------------
-__device__ inline void mul3(const float* a, const float* b, float* out)
-{
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            double acc = (double)a[3 * i] * (double)b[j];
-            acc = acc + (double)a[3 * i + 1] * (double)b[3 + j];
-            acc = acc + (double)a[3 * i + 2] * (double)b[6 + j];
-            out[3 * i + j] = (float)acc;
-        }
-}
-
-__device__ inline void inv3(const float* mf, float* out)
-{
-    double m[9];
-#pragma unroll
-    for (int i = 0; i < 9; i++) m[i] = (double)mf[i];
-    double c[9];
-    c[0] = m[4] * m[8] - m[5] * m[7];
-    c[1] = m[2] * m[7] - m[1] * m[8];
-    c[2] = m[1] * m[5] - m[2] * m[4];
-    c[3] = m[5] * m[6] - m[3] * m[8];
-    c[4] = m[0] * m[8] - m[2] * m[6];
-    c[5] = m[2] * m[3] - m[0] * m[5];
-    c[6] = m[3] * m[7] - m[4] * m[6];
-    c[7] = m[1] * m[6] - m[0] * m[7];
-    c[8] = m[0] * m[4] - m[1] * m[3];
-    const double det = (m[0] * c[0] + m[1] * c[3]) + m[2] * c[6];
-#pragma unroll
-    for (int i = 0; i < 9; i++) out[i] = (float)(c[i] / det);
-}
 
 // ---------------------------------------------------------------------------
 // k_init_prepare
@@ -808,6 +719,7 @@ extern "C" int orbx_dev_init_models(orbx_ctx* ctx, int first, int count, int seq
     const int P = (int)descs.size();
     const InitLayout L = make_layout(max_iter, std::max(nf, 1));
     ctx->init_count = 0;
+    ctx->rec_count = 0;   // a reconstruction belongs to the models run it read
     if ((size_t)P * L.stride > ctx->init_res_bytes) {
         if (ctx->init_res) (void)hipFree(ctx->init_res);
         ctx->init_res = nullptr;
@@ -834,6 +746,7 @@ extern "C" int orbx_dev_init_models(orbx_ctx* ctx, int first, int count, int seq
     ctx->init_first = first;
     ctx->init_count = count;
     ctx->init_iter = max_iter;
+    ctx->init_sigma = sigma;
     ctx->init_pair = pair_of;
     return ORBX_OK;
 }

@@ -344,7 +344,14 @@ struct orbx_ctx {
     void* init_res = nullptr;
     size_t init_res_bytes = 0;
     int init_first = 0, init_count = 0, init_iter = 0;   // init_count 0: no run yet
+    float init_sigma = 0.f;
     std::vector<int> init_pair;
+    // reconstruction of those pairs (orbx_reconstruct.hip): the result blocks
+    // of the last orbx_dev_init_reconstruct run, in the models run's pair
+    // order (rec_count 0: no run since the last models run)
+    void* rec_res = nullptr;
+    size_t rec_res_bytes = 0;
+    int rec_first = 0, rec_count = 0, rec_cap = 0;
     // timing
     bool timing = false;
     std::string timing_only;   // non-empty: only this timer records (orbx_dev_kernel_time_select)

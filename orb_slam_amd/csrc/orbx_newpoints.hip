@@ -22,6 +22,7 @@
 #include "orbx_device.h"
 #include "orbx_internal.h"
 #include "orbx_jacobi.h"
+#include "orbx_linalg.h"
 
 namespace orbx {
 
@@ -45,62 +46,6 @@ struct TriJob {
     int32_t n1, n2, len;    // keypoints of KF1 / KF2; entries of the outputs (>= n1, status 0 past n1)
     TriGeom g1, g2;
 };
-
-// The unit right singular vector of A (row-major 4x4) for its smallest
-// singular value: FP64 from the float entries, rounded once; sign unspecified.
-__device__ inline void null_vector4(const float* A, float* out)
-{
-    double a[4][4], v[4][4];   // [column][row]
-#pragma unroll
-    for (int j = 0; j < 4; j++)
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            a[j][i] = (double)A[4 * i + j];
-            v[j][i] = i == j ? 1.0 : 0.0;
-        }
-    double floor = 0.0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) floor += (a[j][0] * a[j][0] + a[j][1] * a[j][1]) + (a[j][2] * a[j][2] + a[j][3] * a[j][3]);
-    floor *= kInitFloor;
-    for (int sweep = 0; sweep < kInitSweeps; sweep++) {
-        bool rot = false;
-#pragma unroll
-        for (int p = 0; p < 3; p++)
-#pragma unroll
-            for (int q = p + 1; q < 4; q++) {
-                const double al = (a[p][0] * a[p][0] + a[p][1] * a[p][1]) + (a[p][2] * a[p][2] + a[p][3] * a[p][3]);
-                const double be = (a[q][0] * a[q][0] + a[q][1] * a[q][1]) + (a[q][2] * a[q][2] + a[q][3] * a[q][3]);
-                const double ga = (a[p][0] * a[q][0] + a[p][1] * a[q][1]) + (a[p][2] * a[q][2] + a[p][3] * a[q][3]);
-                if (jacobi_wants(al, be, ga, floor)) {
-                    rot = true;
-                    double c, s;
-                    jacobi_cs(al, be, ga, c, s);
-#pragma unroll
-                    for (int i = 0; i < 4; i++) {
-                        const double ap = a[p][i], aq = a[q][i];
-                        a[p][i] = c * ap - s * aq;
-                        a[q][i] = s * ap + c * aq;
-                        const double vp = v[p][i], vq = v[q][i];
-                        v[p][i] = c * vp - s * vq;
-                        v[q][i] = s * vp + c * vq;
-                    }
-                }
-            }
-        if (!rot) break;
-    }
-    double best = 0.0, nv[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const double nj = (a[j][0] * a[j][0] + a[j][1] * a[j][1]) + (a[j][2] * a[j][2] + a[j][3] * a[j][3]);
-        if (j == 0 || nj < best) {
-            best = nj;
-#pragma unroll
-            for (int i = 0; i < 4; i++) nv[i] = v[j][i];
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; i++) out[i] = (float)nv[i];
-}
 
 // Rcw.row(r).dot(x3Dt) + tcw(r): cv::Mat::dot sums in double, the float
 // translation is added to that double, the assignment rounds (:322, :332).
