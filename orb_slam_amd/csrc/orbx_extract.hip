@@ -341,12 +341,18 @@ struct ResizeLevel {
     // (padded columns 0 .. kEdge + P.w), or 0 where the parent is the frame
     // itself (level 0 in direct mode: columns 0 .. P.w of the image)
     int plevel, ppad;
+    // Interior words [0, nslide) run the sliding form in whole waves; the
+    // other rem = nfast - nslide < 64 go to wave rem_wave as (row group,
+    // word) items, rem_n rows per group (0: no remainder).  The host leaves
+    // nslide = nfast where fewer than two groups fit a wave.
+    int nslide, rem_wave, rem_n;
 };
 
 __global__ __launch_bounds__(256) void k_pyr_resize_lds(ExtractArgs a, ResizeLevel L, int pitch)
 {
     extern __shared__ uint4 s_dyn[];
     __shared__ ResizeRow s_rows[kResRows];
+    __shared__ __attribute__((aligned(16))) uint2 s_slide[kResRows];
     const int f = blockIdx.y, tid = threadIdx.x;
     const int py0 = blockIdx.x * kResRows, nrows = min(kResRows, L.ph - py0);
     const int nch = pitch >> 4;
@@ -355,7 +361,18 @@ __global__ __launch_bounds__(256) void k_pyr_resize_lds(ExtractArgs a, ResizeLev
     // the strip's first source row comes from a host table (uniform scalar
     // load), so the staging loads go out together with the row/column tables
     const int lo = a.res_rows[L.strip_off + blockIdx.x].sy0;
-    if (tid < nrows) s_rows[tid] = a.res_rows[L.row_off + reflect101(py0 + tid - kEdge, L.h)];
+    if (tid < nrows) {
+        const ResizeRow e = a.res_rows[L.row_off + reflect101(py0 + tid - kEdge, L.h)];
+        s_rows[tid] = e;
+        // The sliding form's copy of the entry carries in the free bit 12 of
+        // b0 (weights are <= 2048) whether the row's first source row is new:
+        // not the previous row's second, which the sliding form still holds.
+        // Decided here once per strip, not per wave and row.
+        const ResizeRow p = a.res_rows[L.row_off + reflect101(py0 + max(tid, 1) - 1 - kEdge, L.h)];
+        const uint32_t first = (tid == 0 || p.sy1 != e.sy0) ? 0x1000u : 0u;
+        s_slide[tid] = make_uint2((uint32_t)(uint16_t)e.sy0 | (uint32_t)(uint16_t)e.sy1 << 16,
+                                  (uint32_t)(uint16_t)e.b0 | first | (uint32_t)(uint16_t)e.b1 << 16);
+    }
     stage_to_lds<4>(s_cols, L.w, tid, (int)blockDim.x, [&](int x) { return a.res_cols[L.col_off + x]; });
     const int nsrc = min(L.span, L.ph_parent_h - lo);
     // parent row lo from its column kEdge - ppad on: the padded row's first
@@ -381,13 +398,17 @@ __global__ __launch_bounds__(256) void k_pyr_resize_lds(ExtractArgs a, ResizeLev
     if (tid < 64) reinterpret_cast<uint32_t*>(dst)[tid] = s_src[tid * 7];
     return;
 #endif
-    // Output words split by form (no wave runs both):
+    // Output words split by form (one after the other: no wave runs two forms
+    // under a per-lane branch):
     //  * interior words [q_lo, q_hi) whose four columns are on the SSE2 path
     //    (x < nvec): the packed form below, one thread per word sliding
-    //    down the strip's rows;
-    //  * the rest -- the reflected border words, the scalar-tail columns
-    //    x >= nvec and the row padding -- one (row, word) item per thread,
-    //    in the general form.
+    //    down the strip's rows in whole waves, the last nfast % 64 words as
+    //    (row group, word) items of one wave (ResizeLevel::nslide);
+    //  * the words holding a scalar-tail column x >= nvec: one (row, word)
+    //    item per thread, in the general form;
+    //  * the reflected border words and the row padding: copies of the
+    //    strip's interior bytes after a barrier (levels narrower than two
+    //    borders and levels not packed: the general form for all of these).
     // sx1 is sx0 + 1, or sx0 with a1 = 0 (HResizeLinear tail), so the
     // second tap is always read at offset +1.
     const int nq = L.stride >> 2;
@@ -408,7 +429,11 @@ __global__ __launch_bounds__(256) void k_pyr_resize_lds(ExtractArgs a, ResizeLev
     auto mh = [](uint32_t x, uint32_t y) {   // bits 32..47 of the 24 x 24-bit product
         return (uint32_t)(((unsigned long long)(x & 0xFFFFFFu) * (unsigned long long)(y & 0xFFFFFFu)) >> 32);
     };
-    for (int t = tid; t < nfast; t += blockDim.x) {
+    // Word q_lo + t over the strip's rows [r0, r1).  kUni: the whole wave
+    // walks the same rows (the sliding form), so which source rows a row
+    // needs is wave-uniform.
+    auto word_rows = [&](auto uni, int t, int r0, int r1) {
+        constexpr bool kUni = decltype(uni)::value;
         const int q = q_lo + t, x0 = 4 * q - kEdge;
         int ca[4];
         uint32_t sel[4], wgt[4];
@@ -434,14 +459,57 @@ __global__ __launch_bounds__(256) void k_pyr_resize_lds(ExtractArgs a, ResizeLev
                                               __builtin_bit_cast(orbx_us2, wgt[b]), 0u, false) &
                        0x00FFFF00u;
         };
+        uint8_t* out = dst + (size_t)r0 * L.stride + 4 * q;
+        if constexpr (kUni) {
+            // The whole strip (r0 == 0: s_slide's flags count from its first
+            // row).  Two register sets hold the horizontal sums of a row's
+            // two source rows.  A row computes its second source row over
+            // the set that held the previous row's first, and its first only
+            // if that is not the previous row's second (s_slide's flag); then
+            // the sets swap roles.  The loop takes two rows per trip, one per
+            // role assignment: no sums are copied from set to set, and no
+            // wave compares source rows.
+            static_assert(kResRows % 2 == 0, "the sliding form reads s_slide in pairs");
+            uint32_t X[4], Y[4];
+            auto row = [&](const uint32_t w0, const uint32_t w1, uint32_t (&P)[4], uint32_t (&Q)[4]) {
+                const uint32_t B0 = (w1 & 0xFFFu) << 8, B1 = (w1 >> 16) << 8;
+                if (w1 & 0x1000u) {
+                    asm volatile("; first source row");   // (a branch, not a select over both sets)
+                    hrow((int)(w0 & 0xFFFFu), Q);
+                }
+                hrow((int)(w0 >> 16), P);
+                uint32_t word = 0;
+#pragma unroll
+                for (int b = 0; b < 4; b++) word |= ((mh(Q[b], B0) + mh(P[b], B1) + 2) >> 2) << (8 * b);
+                *reinterpret_cast<uint32_t*>(out) = word;
+                out += L.stride;
+            };
+            // a pair's entries go to scalar registers before the next pair's
+            // are read over them, a trip ahead of their use (the last trip
+            // reads the last pair again, not past the table)
+            int rr = 0;
+            uint4 e = *reinterpret_cast<const uint4*>(s_slide);
+            for (; rr + 1 < r1; rr += 2) {
+                const uint32_t a0 = __builtin_amdgcn_readfirstlane(e.x), a1 = __builtin_amdgcn_readfirstlane(e.y);
+                const uint32_t c0 = __builtin_amdgcn_readfirstlane(e.z), c1 = __builtin_amdgcn_readfirstlane(e.w);
+                e = *reinterpret_cast<const uint4*>(s_slide + min(rr + 2, kResRows - 2));
+                row(a0, a1, X, Y);
+                row(c0, c1, Y, X);
+            }
+            if (rr < r1) row(__builtin_amdgcn_readfirstlane(e.x), __builtin_amdgcn_readfirstlane(e.y), X, Y);
+            return;
+        }
+        // A row group of the remainder wave: rows differ from lane to lane,
+        // so the entries and the reuse of the previous row's sums (H0, H1:
+        // source rows c0, c1) are per lane.  The next row's table entry is
+        // read while this row is computed.
+        uint2 nxt = reinterpret_cast<const uint2*>(s_rows)[r0];
         uint32_t H0[4], H1[4];
         int c0 = -1, c1 = -1;
-        // the next row's table entry is read while this row is computed
-        uint2 nxt = reinterpret_cast<const uint2*>(s_rows)[0];
-        for (int rr = 0; rr < nrows; rr++) {
+        for (int rr = r0; rr < r1; rr++, out += L.stride) {
             const uint2 cur = nxt;
-            if (rr + 1 < nrows) nxt = reinterpret_cast<const uint2*>(s_rows)[rr + 1];
-            const uint32_t w0 = __builtin_amdgcn_readfirstlane(cur.x), w1 = __builtin_amdgcn_readfirstlane(cur.y);
+            if (rr + 1 < r1) nxt = reinterpret_cast<const uint2*>(s_rows)[rr + 1];
+            const uint32_t w0 = cur.x, w1 = cur.y;
             const int sy0 = (int)(int16_t)(w0 & 0xFFFF), sy1 = (int)(int16_t)(w0 >> 16);
             const uint32_t B0 = (w1 & 0xFFFFu) << 8, B1 = (w1 >> 16) << 8;
             uint32_t A[4], B[4];
@@ -473,14 +541,25 @@ __global__ __launch_bounds__(256) void k_pyr_resize_lds(ExtractArgs a, ResizeLev
             uint32_t word = 0;
 #pragma unroll
             for (int b = 0; b < 4; b++) word |= ((mh(A[b], B0) + mh(B[b], B1) + 2) >> 2) << (8 * b);
-            *reinterpret_cast<uint32_t*>(dst + (size_t)rr * L.stride + 4 * q) = word;
+            *reinterpret_cast<uint32_t*>(out) = word;
         }
+    };
+    const int rem = nfast - L.nslide;
+    for (int t = tid; t < L.nslide; t += blockDim.x) word_rows(std::true_type{}, t, 0, nrows);
+    if (rem > 0 && __builtin_amdgcn_readfirstlane(tid >> 6) == L.rem_wave) {
+        // lane -> (row group g, word lane - g rem); lane / rem as a float
+        // product (lane < 64: exact)
+        const int lane = tid & 63, g = (int)(((float)lane + 0.5f) * (1.0f / (float)rem));
+        // rem_n = ceil(kResRows / (64 / rem)): the groups tile the strip, and
+        // the lanes past the last whole group start at or after its end
+        const int r0 = g * L.rem_n;
+        if (r0 < nrows) word_rows(std::false_type{}, L.nslide + lane - g * rem, r0, min(r0 + L.rem_n, nrows));
     }
-    // the other words, one (row, word) each
-    const int nslow = nq - nfast;
-    for (int item = tid; item < nrows * nslow; item += blockDim.x) {
-        const int rr = item / nslow, k = item - rr * nslow;
-        const int q = k < q_lo ? k : k + nfast, px0 = 4 * q;
+    // The general form of one output word: per byte the reflected column,
+    // its two taps in both source rows and the column's rounding (SSE2 path
+    // or FixedPtCast<int, uchar, 22>); bytes past the padded width are zero.
+    auto general_word = [&](int rr, int q) {
+        const int px0 = 4 * q;
         const ResizeRow R = s_rows[rr];
         uint32_t word = 0;
 #pragma unroll
@@ -499,6 +578,52 @@ __global__ __launch_bounds__(256) void k_pyr_resize_lds(ExtractArgs a, ResizeLev
             word |= (uint32_t)sat_u8(v) << (8 * b);
         }
         *reinterpret_cast<uint32_t*>(dst + (size_t)rr * L.stride + px0) = word;
+    };
+    const int nslow = nq - nfast;
+    if (L.packed && L.w >= 2 * kEdge) {
+        // Borders as copies.  Only the words [q_hi, q_in) that hold an
+        // interior column outside the packed form (the scalar-tail columns
+        // x >= nvec and a word straddling nvec or w) are computed, in the
+        // general form, by the workgroup's last threads (the waves with the
+        // least packed work).  Once the strip's interior is written, every
+        // border byte is copyMakeBorder's REFLECT_101 copy of an interior byte
+        // of its own row: padded byte p < kEdge is padded byte 2 kEdge - p,
+        // p >= kEdge + w is 2 (kEdge + w - 1) - p, both at most kEdge bytes
+        // into the interior (w >= 2 kEdge).  A border word is the byte
+        // reversal of the four source bytes ending at its first byte's
+        // source: two aligned dwords read back from the level (written by
+        // this workgroup, ordered by the barrier), funnel-shifted and
+        // permuted; bytes at and past the padded width are zero.
+        const int q_in = (kEdge + L.w + 3) >> 2, ntail = q_in - q_hi;
+        for (int item = (int)blockDim.x - 1 - tid; item < kResRows * ntail; item += blockDim.x) {
+            const int rr = item % kResRows;
+            if (rr < nrows) general_word(rr, q_hi + item / kResRows);
+        }
+        __syncthreads();
+        const int ncopy = q_lo + nq - q_in;
+        for (int item = tid; item < kResRows * ncopy; item += blockDim.x) {
+            const int rr = item % kResRows, k = item / kResRows;
+            if (rr >= nrows) continue;
+            const int q = k < q_lo ? k : q_in + (k - q_lo), p0 = 4 * q;
+            const int nb = L.pw - p0;   // bytes of the word inside the padded width
+            uint8_t* row = dst + (size_t)rr * L.stride;
+            uint32_t word = 0;
+            if (nb > 0) {
+                const int s = (k < q_lo ? 2 * kEdge : 2 * (kEdge + L.w - 1)) - p0 - 3;   // the lowest source byte
+                const uint32_t* g = reinterpret_cast<const uint32_t*>(row + (s & ~3));
+                const uint32_t v = __builtin_amdgcn_alignbyte(g[1], g[0], s & 3);
+                word = __builtin_amdgcn_perm(0u, v, 0x00010203u);
+                if (nb < 4) word &= (1u << (8 * nb)) - 1u;
+            }
+            *reinterpret_cast<uint32_t*>(row + p0) = word;
+        }
+        return;
+    }
+    // levels narrower than two borders, and the form that is not packed:
+    // every other word in the general form, one (row, word) each
+    for (int item = tid; item < nrows * nslow; item += blockDim.x) {
+        const int rr = item / nslow, k = item - rr * nslow;
+        general_word(rr, k < q_lo ? k : k + nfast);
     }
 }
 
@@ -2467,8 +2592,21 @@ int launch_extract(orbx_ctx* ctx, int first, int count, const MatchSpec* m)
                 int packed = 1;
                 for (int x0 = 0; x0 + 3 < L.w; x0 += 4)
                     if (g.res_cols[L.res_col_off + x0 + 3].sx0 - g.res_cols[L.res_col_off + x0].sx0 > 6) packed = 0;
+                // interior words of the packed form (k_pyr_resize_lds's nfast):
+                // whole waves slide down the strip; a remainder of at most 32
+                // words shares one wave as 64 / rem row groups
+                const int q_lo = (kEdge + 3) >> 2;
+                const int nfast = packed ? std::max(q_lo, (kEdge + std::min(L.w, L.nvec_resize)) >> 2) - q_lo : 0;
+                int nslide = nfast, rem_wave = 0, rem_n = 0;
+                if (const int rem = nfast & 63; rem > 0 && rem <= 32) {
+                    nslide = nfast - rem;
+                    rem_wave = (nslide >> 6) % (threads >> 6);
+                    const int groups = 64 / rem;
+                    rem_n = (kResRows + groups - 1) / groups;
+                }
                 const ResizeLevel rl{L.off, P.off, L.stride, P.stride, L.w, L.h, L.pw, L.ph, P.h, L.nvec_resize,
-                                     L.res_span, L.res_strip_off, L.res_row_off, L.res_col_off, packed, l - 1, ppad};
+                                     L.res_span, L.res_strip_off, L.res_row_off, L.res_col_off, packed, l - 1, ppad,
+                                     nslide, rem_wave, rem_n};
                 for (int rep = 0; rep < kDiagRepeat[0]; rep++)
                     hipLaunchKernelGGL(k_pyr_resize_lds, dim3((L.ph + kResRows - 1) / kResRows, nb), dim3(threads), lds,
                                        st, x, rl, pitch);
