@@ -434,19 +434,23 @@ constexpr int kReplayThreads = 1024;
 constexpr int kReplayWaves = kReplayThreads / 64;
 constexpr int kReplayEntries = 8192;   // short-list entries staged in LDS (32 KB), at most
 constexpr int kMaxRounds = 24;
+// per-query int arrays of the replay: count, offset, angle, state, and the
+// list of the queries with more than 64 candidates (q_long)
+constexpr int kAreaQueryInts = 5;
 // rounds used and sequential fallbacks, summed over replays (orbx_debug_area_rounds)
 __device__ unsigned long long g_area_rounds[2];
 // LDS: table (x, y, cell_oct, taken), bins, keys, hist, angles, two claim
-// arrays; per query count, offset, angle, state (nq_lds of them: 0 when the
-// per-query arrays live in global memory); ent_cap short-list entries
+// arrays; the kAreaQueryInts per-query arrays (nq_lds queries: 0 when they
+// live in global memory); ent_cap short-list entries
 __host__ __device__ inline size_t area_replay_lds(int n2, int nq_lds, int ent_cap)
 {
     return (size_t)n2 * 16 + ((n2 + 15) & ~15) + (size_t)n2 * 4 + 48 * 4 + (size_t)n2 * 4 + (size_t)n2 * 8 +
-           (size_t)nq_lds * 20 + (size_t)ent_cap * 4;
+           (size_t)nq_lds * kAreaQueryInts * 4 + (size_t)ent_cap * 4;
 }
 
-// qglob: per job 5 cap_q ints (count, offset, angle, state, long-list
-// queries) when the per-query arrays do not fit LDS (q_lds 0), else unused
+// qglob: per job kAreaQueryInts arrays of cap_q ints (count, offset, angle,
+// state, long-list queries), 20 bytes per query as reserve_area sizes it,
+// used when the per-query arrays do not fit LDS (q_lds 0), else unused
 template <int K>
 __global__ __launch_bounds__(kReplayThreads) void k_area_replay(const SearchArgs* jobs, int cap_q,
                                                                 const uint32_t* lists_all, const int32_t* cnt_all,
@@ -472,13 +476,13 @@ __global__ __launch_bounds__(kReplayThreads) void k_area_replay(const SearchArgs
     float* ang2 = reinterpret_cast<float*>(hist + 48);
     int* claim0 = reinterpret_cast<int*>(ang2 + n2);
     int* claim1 = claim0 + n2;
-    int* qbase = q_lds ? claim1 + n2 : qglob + (size_t)blockIdx.x * 5 * cap_q;
+    int* qbase = q_lds ? claim1 + n2 : qglob + (size_t)blockIdx.x * kAreaQueryInts * cap_q;
     int* q_cnt = qbase;
     int* q_off = q_cnt + cap_q;                                // entry offset of the short list, -1: global
     float* q_ang = reinterpret_cast<float*>(q_off + cap_q);
     int* q_state = reinterpret_cast<int*>(q_ang + cap_q);      // accepted candidate, or -1
     int* q_long = q_state + cap_q;                             // the queries with more than 64 candidates
-    uint32_t* ent = reinterpret_cast<uint32_t*>(claim1 + n2 + (q_lds ? 5 * cap_q : 0));
+    uint32_t* ent = reinterpret_cast<uint32_t*>(claim1 + n2 + (q_lds ? kAreaQueryInts * cap_q : 0));
     const uint32_t* lists = lists_all + (size_t)blockIdx.x * cap_q * kAreaCap;
     const int32_t* cnt = cnt_all + (size_t)blockIdx.x * cap_q;
     constexpr bool kRot = K == kQWindow || K == kQMotion;
@@ -1420,7 +1424,7 @@ AreaBufs reserve_area(Uploader& u, int B, int nq)
     AreaBufs o;
     o.lists = u.reserve((size_t)B * std::max(nq, 1) * kAreaCap * 4);
     o.cnt = u.reserve((size_t)B * std::max(nq, 1) * 4);
-    o.qglob = u.reserve((size_t)B * std::max(nq, 1) * 16);
+    o.qglob = u.reserve((size_t)B * std::max(nq, 1) * kAreaQueryInts * 4);
     return o;
 }
 
