@@ -22,6 +22,7 @@
 #include "orbx_bow_queue.h"
 #include "orbx_internal.h"
 #include "orbx_match_common.h"
+#include "orbx_stage.h"
 
 namespace orbx {
 
@@ -298,7 +299,77 @@ std::vector<int4> common_nodes(const orbx_bow_view& a, const orbx_bow_view& b)
     return out;
 }
 
-inline size_t al256(size_t b) { return (b + 255) & ~size_t(255); }
+int n_feat(const orbx_bow_view& V) { return V.n_nodes ? V.node_ptr[V.n_nodes] : 0; }
+
+// One side of a match staged from the host: keypoints, descriptors,
+// map-point flags and the FeatureVector's feature indices.
+struct SideRegions {
+    Region<orbx_keypoint> k;
+    Region<uint8_t> d, m;
+    Region<int32_t> f;
+};
+
+SideRegions take_side(ArrayStage& s, const orbx_bow_view& V)
+{
+    SideRegions o;
+    o.k = s.take<orbx_keypoint>(V.n);
+    o.d = s.take<uint8_t>((size_t)V.n * 32);
+    o.m = s.take<uint8_t>(V.n);
+    o.f = s.take<int32_t>(n_feat(V));
+    return o;
+}
+
+int put_side(ArrayStage& s, const SideRegions& o, const orbx_bow_view& V)
+{
+    int r;
+    if ((r = s.put(o.k, V.keys)) || (r = s.put(o.d, V.desc)) || (r = s.put(o.m, V.mp)) ||
+        (r = s.put(o.f, V.n_nodes ? V.feat_idx : nullptr)))
+        return r;
+    return ORBX_OK;
+}
+
+BowSideDev side_dev(const ArrayStage& s, const SideRegions& o) { return {s.dev(o.k), s.dev(o.d), s.dev(o.m), s.dev(o.f)}; }
+
+// A side resident in an extraction slot; mp: its map-point flags on the device.
+BowSideDev slot_side(const orbx_ctx* ctx, int slot, const uint8_t* mp)
+{
+    const FrameDev F = slot_frame_dev(ctx, slot, nullptr);
+    return {F.kps, F.desc, mp, ctx->bow.fv_feat + (size_t)slot * ctx->bow_nf};
+}
+
+// One match's results: the match per first-side keypoint and its rotation
+// bin, both -1 before the launch, and the match count.
+struct OutRegions {
+    Region<int32_t> out;
+    Region<signed char> bin;
+    Region<int32_t> n;
+};
+
+OutRegions take_out(ArrayStage& s, int len)
+{
+    OutRegions o;
+    o.out = s.take<int32_t>(len);
+    o.bin = s.take<signed char>(len);
+    o.n = s.take<int32_t>(1);
+    return o;
+}
+
+int set_out(BowArgs& a, ArrayStage& s, const OutRegions& o)
+{
+    int r;
+    if ((r = s.fill(o.out, 0xFF)) || (r = s.fill(o.bin, 0xFF))) return r;
+    a.out = s.dev(o.out);
+    a.bins = s.dev(o.bin);
+    a.out_n = s.dev(o.n);
+    return ORBX_OK;
+}
+
+// mode 2: the pair's fundamental matrix and the second side's level sigmas
+void set_epipolar(BowArgs& a, const float* F12, const float* sigma2, int nlevels)
+{
+    for (int k = 0; k < 9; k++) a.F12[k] = F12[k];
+    for (int l = 0; l < nlevels; l++) a.sigma2[l] = sigma2[l];
+}
 
 int run_bow(orbx_ctx* ctx, const orbx_bow_view* V1, const orbx_bow_view* V2, int mode, float nnratio, int check_ori,
             const float* F12, const float* sigma2, int nlevels, int32_t* out, int* n_out)
@@ -311,60 +382,28 @@ int run_bow(orbx_ctx* ctx, const orbx_bow_view* V1, const orbx_bow_view* V2, int
         if (nd.w > 64 * kBowMaxChunks) return ORBX_ERR_UNSUPPORTED;
     const int out_len = mode == 0 ? V2->n : V1->n;
     ctx_enter(ctx);
-    const int nf1 = V1->n_nodes ? V1->node_ptr[V1->n_nodes] : 0, nf2 = V2->n_nodes ? V2->node_ptr[V2->n_nodes] : 0;
-    // layout in the context scratch
-    size_t at = 0;
-    auto res = [&](size_t bytes) {
-        const size_t o = at;
-        at += al256(std::max<size_t>(bytes, 1));
-        return o;
-    };
-    const size_t o_k1 = res((size_t)V1->n * sizeof(orbx_keypoint)), o_d1 = res((size_t)V1->n * 32),
-                 o_m1 = res(V1->n), o_f1 = res((size_t)nf1 * 4);
-    const size_t o_k2 = res((size_t)V2->n * sizeof(orbx_keypoint)), o_d2 = res((size_t)V2->n * 32),
-                 o_m2 = res(V2->n), o_f2 = res((size_t)nf2 * 4);
-    const size_t o_nd = res(nodes.size() * sizeof(int4)), o_out = res((size_t)out_len * 4), o_bin = res(out_len),
-                 o_n = res(4);
-    int r = ensure_scratch(ctx, at);
+    ArrayStage s(ctx);
+    const SideRegions o1 = take_side(s, *V1), o2 = take_side(s, *V2);
+    const Region<int4> o_nd = s.take<int4>(nodes.size());
+    const OutRegions oo = take_out(s, out_len);
+    int r = s.open();
     if (r != ORBX_OK) return r;
-    uint8_t* d = static_cast<uint8_t*>(ctx->scratch);
-    auto put = [&](size_t off, const void* src, size_t bytes) -> int {
-        if (bytes == 0 || !src) return ORBX_OK;
-        ORBX_HIP_CHECK(hipMemcpyAsync(d + off, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-        return ORBX_OK;
-    };
-    if ((r = put(o_k1, V1->keys, (size_t)V1->n * sizeof(orbx_keypoint))) ||
-        (r = put(o_d1, V1->desc, (size_t)V1->n * 32)) || (r = put(o_m1, V1->mp, V1->n)) ||
-        (r = put(o_f1, V1->n_nodes ? V1->feat_idx : nullptr, (size_t)nf1 * 4)) ||
-        (r = put(o_k2, V2->keys, (size_t)V2->n * sizeof(orbx_keypoint))) ||
-        (r = put(o_d2, V2->desc, (size_t)V2->n * 32)) || (r = put(o_m2, V2->mp, V2->n)) ||
-        (r = put(o_f2, V2->n_nodes ? V2->feat_idx : nullptr, (size_t)nf2 * 4)) ||
-        (r = put(o_nd, nodes.data(), nodes.size() * sizeof(int4))))
-        return r;
-    ORBX_HIP_CHECK(hipMemsetAsync(d + o_out, 0xFF, (size_t)out_len * 4, ctx->stream));
-    ORBX_HIP_CHECK(hipMemsetAsync(d + o_bin, 0xFF, (size_t)out_len, ctx->stream));
     BowArgs a{};
-    a.s1 = {reinterpret_cast<const orbx_keypoint*>(d + o_k1), d + o_d1, d + o_m1,
-            reinterpret_cast<const int32_t*>(d + o_f1)};
-    a.s2 = {reinterpret_cast<const orbx_keypoint*>(d + o_k2), d + o_d2, d + o_m2,
-            reinterpret_cast<const int32_t*>(d + o_f2)};
-    a.nodes = reinterpret_cast<const int4*>(d + o_nd);
+    if ((r = put_side(s, o1, *V1)) || (r = put_side(s, o2, *V2)) || (r = s.put(o_nd, nodes.data())) ||
+        (r = set_out(a, s, oo)))
+        return r;
+    a.s1 = side_dev(s, o1);
+    a.s2 = side_dev(s, o2);
+    a.nodes = s.dev(o_nd);
     a.n_common = (int)nodes.size();
     a.mode = mode;
     a.nnratio = nnratio;
     a.check_ori = check_ori;
-    if (mode == 2) {
-        for (int k = 0; k < 9; k++) a.F12[k] = F12[k];
-        for (int l = 0; l < nlevels; l++) a.sigma2[l] = sigma2[l];
-    }
-    a.out = reinterpret_cast<int32_t*>(d + o_out);
+    if (mode == 2) set_epipolar(a, F12, sigma2, nlevels);
     a.out_len = out_len;
-    a.bins = reinterpret_cast<signed char*>(d + o_bin);
-    a.out_n = reinterpret_cast<int32_t*>(d + o_n);
     hipLaunchKernelGGL(k_bow_match, dim3(1), dim3(kBlock), 0, ctx->stream, a);
     ORBX_HIP_CHECK(hipGetLastError());
-    if (out_len) ORBX_HIP_CHECK(hipMemcpyAsync(out, d + o_out, (size_t)out_len * 4, hipMemcpyDeviceToHost, ctx->stream));
-    ORBX_HIP_CHECK(hipMemcpyAsync(n_out, d + o_n, 4, hipMemcpyDeviceToHost, ctx->stream));
+    if ((r = s.get(out, oo.out)) || (r = s.get(n_out, oo.n))) return r;
     ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return ORBX_OK;
 }
@@ -391,95 +430,58 @@ int queue_bow_batch(orbx_ctx* ctx, const orbx_bow_view* V1, int n, const orbx_bo
     }
     ctx_enter(ctx);
     const int out_len = V1->n;
-    size_t at = 0;
-    auto res = [&](size_t bytes) {
-        const size_t o = at;
-        at += al256(std::max<size_t>(bytes, 1));
-        return o;
-    };
-    const int nf1 = V1->n_nodes ? V1->node_ptr[V1->n_nodes] : 0;
-    const size_t o_k1 = res((size_t)V1->n * sizeof(orbx_keypoint)), o_d1 = res((size_t)V1->n * 32),
-                 o_m1 = res(V1->n), o_f1 = res((size_t)nf1 * 4);
+    ArrayStage s(ctx);
+    const SideRegions o1 = take_side(s, *V1);
     struct Off {
-        size_t k2, d2, m2, f2, nd, out, bin, n;
+        SideRegions s2;
+        Region<int4> nd;
+        OutRegions oo;
     };
     std::vector<Off> o(n);
     for (int k = 0; k < n; k++) {
-        const orbx_bow_view& V2 = V2s[k];
-        const int nf2 = V2.n_nodes ? V2.node_ptr[V2.n_nodes] : 0;
-        o[k].k2 = res((size_t)V2.n * sizeof(orbx_keypoint));
-        o[k].d2 = res((size_t)V2.n * 32);
-        o[k].m2 = res(V2.n);
-        o[k].f2 = res((size_t)nf2 * 4);
-        o[k].nd = res(nodes[k].size() * sizeof(int4));
-        o[k].out = res((size_t)out_len * 4);
-        o[k].bin = res(out_len);
-        o[k].n = res(4);
+        o[k].s2 = take_side(s, V2s[k]);
+        o[k].nd = s.take<int4>(nodes[k].size());
+        o[k].oo = take_out(s, out_len);
     }
-    const size_t o_jobs = res(sizeof(BowArgs) * (size_t)n);
-    const size_t o_extra = res(extra_bytes);
-    int r = ensure_scratch(ctx, at);
+    const Region<BowArgs> o_jobs = s.take<BowArgs>(n);
+    const Region<uint8_t> o_extra = s.take<uint8_t>(extra_bytes);
+    int r = s.open();
     if (r != ORBX_OK) return r;
-    uint8_t* d = static_cast<uint8_t*>(ctx->scratch);
-    auto put = [&](size_t off, const void* src, size_t bytes) -> int {
-        if (bytes == 0 || !src) return ORBX_OK;
-        ORBX_HIP_CHECK(hipMemcpyAsync(d + off, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-        return ORBX_OK;
-    };
-    if ((r = put(o_k1, V1->keys, (size_t)V1->n * sizeof(orbx_keypoint))) ||
-        (r = put(o_d1, V1->desc, (size_t)V1->n * 32)) || (r = put(o_m1, V1->mp, V1->n)) ||
-        (r = put(o_f1, V1->n_nodes ? V1->feat_idx : nullptr, (size_t)nf1 * 4)))
-        return r;
+    if ((r = put_side(s, o1, *V1))) return r;
     std::vector<BowArgs> jobs(n);
     for (int k = 0; k < n; k++) {
-        const orbx_bow_view& V2 = V2s[k];
-        const int nf2 = V2.n_nodes ? V2.node_ptr[V2.n_nodes] : 0;
-        if ((r = put(o[k].k2, V2.keys, (size_t)V2.n * sizeof(orbx_keypoint))) ||
-            (r = put(o[k].d2, V2.desc, (size_t)V2.n * 32)) || (r = put(o[k].m2, V2.mp, V2.n)) ||
-            (r = put(o[k].f2, V2.n_nodes ? V2.feat_idx : nullptr, (size_t)nf2 * 4)) ||
-            (r = put(o[k].nd, nodes[k].data(), nodes[k].size() * sizeof(int4))))
-            return r;
-        ORBX_HIP_CHECK(hipMemsetAsync(d + o[k].out, 0xFF, (size_t)out_len * 4, ctx->stream));
-        ORBX_HIP_CHECK(hipMemsetAsync(d + o[k].bin, 0xFF, (size_t)out_len, ctx->stream));
         BowArgs& a = jobs[k];
-        a = BowArgs{};
-        a.s1 = {reinterpret_cast<const orbx_keypoint*>(d + o_k1), d + o_d1, d + o_m1,
-                reinterpret_cast<const int32_t*>(d + o_f1)};
-        a.s2 = {reinterpret_cast<const orbx_keypoint*>(d + o[k].k2), d + o[k].d2, d + o[k].m2,
-                reinterpret_cast<const int32_t*>(d + o[k].f2)};
-        a.nodes = reinterpret_cast<const int4*>(d + o[k].nd);
+        if ((r = put_side(s, o[k].s2, V2s[k])) || (r = s.put(o[k].nd, nodes[k].data())) || (r = set_out(a, s, o[k].oo)))
+            return r;
+        a.s1 = side_dev(s, o1);
+        a.s2 = side_dev(s, o[k].s2);
+        a.nodes = s.dev(o[k].nd);
         a.n_common = (int)nodes[k].size();
         a.mode = mode;
         a.nnratio = nnratio;
         a.check_ori = check_ori;
-        if (mode == 2) {
-            for (int c = 0; c < 9; c++) a.F12[c] = F12s[9 * k + c];
-            for (int l = 0; l < nlevels; l++) a.sigma2[l] = sigma2s[(size_t)nlevels * k + l];
-        }
-        a.out = reinterpret_cast<int32_t*>(d + o[k].out);
+        if (mode == 2) set_epipolar(a, F12s + 9 * k, sigma2s + (size_t)nlevels * k, nlevels);
         a.out_len = out_len;
-        a.bins = reinterpret_cast<signed char*>(d + o[k].bin);
-        a.out_n = reinterpret_cast<int32_t*>(d + o[k].n);
     }
-    if ((r = put(o_jobs, jobs.data(), sizeof(BowArgs) * (size_t)n))) return r;
+    if ((r = s.put(o_jobs, jobs.data()))) return r;
     if (q) {
-        q->k1 = reinterpret_cast<const orbx_keypoint*>(d + o_k1);
-        q->mp1 = d + o_m1;
+        q->k1 = s.dev(o1.k);
+        q->mp1 = s.dev(o1.m);
         q->n1 = V1->n;
         q->out_len = out_len;
-        q->extra = d + o_extra;
+        q->extra = s.dev(o_extra);
         q->k2.resize(n);
         q->n2.resize(n);
         q->out.resize(n);
         q->out_n.resize(n);
         for (int k = 0; k < n; k++) {
-            q->k2[k] = reinterpret_cast<const orbx_keypoint*>(d + o[k].k2);
+            q->k2[k] = s.dev(o[k].s2.k);
             q->n2[k] = V2s[k].n;
-            q->out[k] = reinterpret_cast<int32_t*>(d + o[k].out);
-            q->out_n[k] = reinterpret_cast<int32_t*>(d + o[k].n);
+            q->out[k] = s.dev(o[k].oo.out);
+            q->out_n[k] = s.dev(o[k].oo.n);
         }
     }
-    const BowArgs* djobs = reinterpret_cast<const BowArgs*>(d + o_jobs);
+    const BowArgs* djobs = s.dev(o_jobs);
     if (!after) {
         hipLaunchKernelGGL(k_bow_match_jobs, dim3(n), dim3(kBlock), 0, ctx->stream, djobs);
         ORBX_HIP_CHECK(hipGetLastError());
@@ -576,85 +578,57 @@ extern "C" int orbx_dev_search_by_bow(orbx_ctx* ctx, int slot, int n, const orbx
         if (!valid_bow(&KFs[k], 0) || !matches_f[k]) return ORBX_ERR_ARG;
     if (n == 0) return ORBX_OK;
     ctx_enter(ctx);
-    size_t at = 0;
-    auto res = [&](size_t bytes) {
-        const size_t o = at;
-        at += al256(std::max<size_t>(bytes, 1));
-        return o;
-    };
+    ArrayStage s(ctx);
     struct Off {
-        size_t k1, d1, m1, f1, nid, nptr, nd, out, bin, n;
+        SideRegions s1;
+        Region<uint32_t> nid;
+        Region<int32_t> nptr;
+        Region<int4> nd;
+        OutRegions oo;
     };
     std::vector<Off> o(n);
     for (int k = 0; k < n; k++) {
         const orbx_bow_view& V = KFs[k];
-        const int nf1 = V.n_nodes ? V.node_ptr[V.n_nodes] : 0;
-        o[k].k1 = res((size_t)V.n * sizeof(orbx_keypoint));
-        o[k].d1 = res((size_t)V.n * 32);
-        o[k].m1 = res(V.n);
-        o[k].f1 = res((size_t)nf1 * 4);
-        o[k].nid = res((size_t)V.n_nodes * 4);
-        o[k].nptr = res((size_t)(V.n_nodes + 1) * 4);
-        o[k].nd = res((size_t)V.n_nodes * sizeof(int4));
-        o[k].out = res((size_t)nf * 4);
-        o[k].bin = res(nf);
-        o[k].n = res(4);
+        o[k].s1 = take_side(s, V);
+        o[k].nid = s.take<uint32_t>(V.n_nodes);
+        o[k].nptr = s.take<int32_t>((size_t)V.n_nodes + 1);
+        o[k].nd = s.take<int4>(V.n_nodes);
+        o[k].oo = take_out(s, nf);
     }
-    const size_t o_jobs = res(sizeof(BowSlotJob) * (size_t)n);
-    int r = ensure_scratch(ctx, at);
+    const Region<BowSlotJob> o_jobs = s.take<BowSlotJob>(n);
+    int r = s.open();
     if (r != ORBX_OK) return r;
-    uint8_t* d = static_cast<uint8_t*>(ctx->scratch);
-    auto put = [&](size_t off, const void* src, size_t bytes) -> int {
-        if (bytes == 0 || !src) return ORBX_OK;
-        ORBX_HIP_CHECK(hipMemcpyAsync(d + off, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-        return ORBX_OK;
-    };
     const SlotBowDev& b = ctx->bow;
     std::vector<BowSlotJob> jobs(n);
     for (int k = 0; k < n; k++) {
         const orbx_bow_view& V = KFs[k];
-        const int nf1 = V.n_nodes ? V.node_ptr[V.n_nodes] : 0;
-        if ((r = put(o[k].k1, V.keys, (size_t)V.n * sizeof(orbx_keypoint))) ||
-            (r = put(o[k].d1, V.desc, (size_t)V.n * 32)) || (r = put(o[k].m1, V.mp, V.n)) ||
-            (r = put(o[k].f1, V.n_nodes ? V.feat_idx : nullptr, (size_t)nf1 * 4)) ||
-            (r = put(o[k].nid, V.n_nodes ? V.node_id : nullptr, (size_t)V.n_nodes * 4)) ||
-            (r = put(o[k].nptr, V.n_nodes ? V.node_ptr : nullptr, (size_t)(V.n_nodes + 1) * 4)))
-            return r;
-        ORBX_HIP_CHECK(hipMemsetAsync(d + o[k].out, 0xFF, (size_t)nf * 4, ctx->stream));
-        ORBX_HIP_CHECK(hipMemsetAsync(d + o[k].bin, 0xFF, (size_t)nf, ctx->stream));
         BowSlotJob& j = jobs[k];
-        j = BowSlotJob{};
         BowArgs& a = j.a;
-        a.s1 = {reinterpret_cast<const orbx_keypoint*>(d + o[k].k1), d + o[k].d1, d + o[k].m1,
-                reinterpret_cast<const int32_t*>(d + o[k].f1)};
-        a.s2 = {ctx->out_kps + (size_t)slot * nf, ctx->out_desc + (size_t)slot * nf * 32, nullptr,
-                b.fv_feat + (size_t)slot * nf};
+        if ((r = put_side(s, o[k].s1, V)) || (r = s.put(o[k].nid, V.n_nodes ? V.node_id : nullptr)) ||
+            (r = s.put(o[k].nptr, V.n_nodes ? V.node_ptr : nullptr)) || (r = set_out(a, s, o[k].oo)))
+            return r;
+        a.s1 = side_dev(s, o[k].s1);
+        a.s2 = slot_side(ctx, slot, nullptr);
         a.mode = 0;
         a.nnratio = nnratio;
         a.check_ori = check_ori;
-        a.out = reinterpret_cast<int32_t*>(d + o[k].out);
-        a.bins = reinterpret_cast<signed char*>(d + o[k].bin);
-        a.out_n = reinterpret_cast<int32_t*>(d + o[k].n);
-        j.kf_node_id = reinterpret_cast<const uint32_t*>(d + o[k].nid);
-        j.kf_node_ptr = reinterpret_cast<const int32_t*>(d + o[k].nptr);
+        j.kf_node_id = s.dev(o[k].nid);
+        j.kf_node_ptr = s.dev(o[k].nptr);
         j.kf_n_nodes = V.n_nodes;
         j.f_node_id = b.fv_nodes + (size_t)slot * nf;
         j.f_node_ptr = b.fv_ptr + (size_t)slot * (nf + 1);
         j.f_counts = b.counts + 2 * slot;
         j.out_count = ctx->out_n + slot;
         j.nf = nf;
-        j.nodes = reinterpret_cast<int4*>(d + o[k].nd);
+        j.nodes = s.dev(o[k].nd);
     }
-    if ((r = put(o_jobs, jobs.data(), sizeof(BowSlotJob) * (size_t)n))) return r;
+    if ((r = s.put(o_jobs, jobs.data()))) return r;
     timer_begin(ctx, "bow_match_slot");
-    hipLaunchKernelGGL(k_bow_match_slot, dim3(n), dim3(kBlock), 0, ctx->stream,
-                       reinterpret_cast<const BowSlotJob*>(d + o_jobs));
+    hipLaunchKernelGGL(k_bow_match_slot, dim3(n), dim3(kBlock), 0, ctx->stream, s.dev(o_jobs));
     timer_end(ctx, "bow_match_slot");
     ORBX_HIP_CHECK(hipGetLastError());
-    for (int k = 0; k < n; k++) {
-        ORBX_HIP_CHECK(hipMemcpyAsync(matches_f[k], d + o[k].out, (size_t)nf * 4, hipMemcpyDeviceToHost, ctx->stream));
-        ORBX_HIP_CHECK(hipMemcpyAsync(&n_matches[k], d + o[k].n, 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
+    for (int k = 0; k < n; k++)
+        if ((r = s.get(matches_f[k], o[k].oo.out)) || (r = s.get(&n_matches[k], o[k].oo.n))) return r;
     ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     for (int k = 0; k < n; k++)
         if (n_matches[k] < 0) return ORBX_ERR_UNSUPPORTED;
@@ -689,57 +663,38 @@ int queue_bow_slots(orbx_ctx* ctx, int mode, int slot1, const uint8_t* mp1, int 
     ORBX_HIP_CHECK(hipMemcpyAsync(cnt.data(), ctx->out_n, sizeof(int32_t) * ctx->slots, hipMemcpyDeviceToHost,
                                   ctx->stream));
     ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    auto count = [&](int s) { return std::min<int>(cnt[s], nf); };
-    size_t at = 0;
-    auto res = [&](size_t bytes) {
-        const size_t o = at;
-        at += al256(std::max<size_t>(bytes, 1));
-        return o;
-    };
-    const size_t o_m1 = res(nf);
+    auto count = [&](int slot) { return std::min<int>(cnt[slot], nf); };
+    ArrayStage s(ctx);
+    const Region<uint8_t> o_m1 = s.take<uint8_t>(nf);
     struct Off {
-        size_t m2, nd, out, bin, n;
+        Region<uint8_t> m2;
+        Region<int4> nd;
+        OutRegions oo;
     };
     std::vector<Off> o(n);
     for (int k = 0; k < n; k++) {
-        o[k].m2 = res(nf);
-        o[k].nd = res((size_t)nf * sizeof(int4));
-        o[k].out = res((size_t)nf * 4);
-        o[k].bin = res(nf);
-        o[k].n = res(4);
+        o[k].m2 = s.take<uint8_t>(nf);
+        o[k].nd = s.take<int4>(nf);
+        o[k].oo = take_out(s, nf);
     }
-    const size_t o_jobs = res(sizeof(BowSlotJob) * (size_t)n);
-    const size_t o_extra = res(extra_bytes);
-    int r = ensure_scratch(ctx, at);
+    const Region<BowSlotJob> o_jobs = s.take<BowSlotJob>(n);
+    const Region<uint8_t> o_extra = s.take<uint8_t>(extra_bytes);
+    int r = s.open();
     if (r != ORBX_OK) return r;
-    uint8_t* d = static_cast<uint8_t*>(ctx->scratch);
-    if (count(slot1) > 0)
-        ORBX_HIP_CHECK(hipMemcpyAsync(d + o_m1, mp1, count(slot1), hipMemcpyHostToDevice, ctx->stream));
+    if ((r = s.put(o_m1, mp1, count(slot1)))) return r;
     const SlotBowDev& b = ctx->bow;
     std::vector<BowSlotJob> jobs(n);
     for (int k = 0; k < n; k++) {
         const int s2 = slots2[k];
-        if (count(s2) > 0)
-            ORBX_HIP_CHECK(hipMemcpyAsync(d + o[k].m2, mp2s[k], count(s2), hipMemcpyHostToDevice, ctx->stream));
-        ORBX_HIP_CHECK(hipMemsetAsync(d + o[k].out, 0xFF, (size_t)nf * 4, ctx->stream));
-        ORBX_HIP_CHECK(hipMemsetAsync(d + o[k].bin, 0xFF, (size_t)nf, ctx->stream));
         BowSlotJob& j = jobs[k];
-        j = BowSlotJob{};
         BowArgs& a = j.a;
-        a.s1 = {ctx->out_kps + (size_t)slot1 * nf, ctx->out_desc + (size_t)slot1 * nf * 32, d + o_m1,
-                b.fv_feat + (size_t)slot1 * nf};
-        a.s2 = {ctx->out_kps + (size_t)s2 * nf, ctx->out_desc + (size_t)s2 * nf * 32, d + o[k].m2,
-                b.fv_feat + (size_t)s2 * nf};
+        if ((r = s.put(o[k].m2, mp2s[k], count(s2))) || (r = set_out(a, s, o[k].oo))) return r;
+        a.s1 = slot_side(ctx, slot1, s.dev(o_m1));
+        a.s2 = slot_side(ctx, s2, s.dev(o[k].m2));
         a.mode = mode;
         a.nnratio = nnratio;
         a.check_ori = check_ori;
-        if (mode == 2) {
-            for (int c = 0; c < 9; c++) a.F12[c] = F12s[9 * k + c];
-            for (int l = 0; l < nlevels; l++) a.sigma2[l] = sigma2s[(size_t)nlevels * k + l];
-        }
-        a.out = reinterpret_cast<int32_t*>(d + o[k].out);
-        a.bins = reinterpret_cast<signed char*>(d + o[k].bin);
-        a.out_n = reinterpret_cast<int32_t*>(d + o[k].n);
+        if (mode == 2) set_epipolar(a, F12s + 9 * k, sigma2s + (size_t)nlevels * k, nlevels);
         j.kf_node_id = b.fv_nodes + (size_t)slot1 * nf;
         j.kf_node_ptr = b.fv_ptr + (size_t)slot1 * (nf + 1);
         j.kf_counts = b.counts + 2 * slot1;
@@ -748,28 +703,27 @@ int queue_bow_slots(orbx_ctx* ctx, int mode, int slot1, const uint8_t* mp1, int 
         j.f_counts = b.counts + 2 * s2;
         j.out_count = ctx->out_n + slot1;
         j.nf = nf;
-        j.nodes = reinterpret_cast<int4*>(d + o[k].nd);
+        j.nodes = s.dev(o[k].nd);
     }
-    ORBX_HIP_CHECK(hipMemcpyAsync(d + o_jobs, jobs.data(), sizeof(BowSlotJob) * (size_t)n, hipMemcpyHostToDevice,
-                                  ctx->stream));
+    if ((r = s.put(o_jobs, jobs.data()))) return r;
     if (q) {
-        q->k1 = ctx->out_kps + (size_t)slot1 * nf;
-        q->mp1 = d + o_m1;
+        q->k1 = slot_frame_dev(ctx, slot1, nullptr).kps;
+        q->mp1 = s.dev(o_m1);
         q->n1 = count(slot1);
         q->out_len = nf;
-        q->extra = d + o_extra;
+        q->extra = s.dev(o_extra);
         q->k2.resize(n);
         q->n2.resize(n);
         q->out.resize(n);
         q->out_n.resize(n);
         for (int k = 0; k < n; k++) {
-            q->k2[k] = ctx->out_kps + (size_t)slots2[k] * nf;
+            q->k2[k] = slot_frame_dev(ctx, slots2[k], nullptr).kps;
             q->n2[k] = count(slots2[k]);
-            q->out[k] = reinterpret_cast<int32_t*>(d + o[k].out);
-            q->out_n[k] = reinterpret_cast<int32_t*>(d + o[k].n);
+            q->out[k] = s.dev(o[k].oo.out);
+            q->out_n[k] = s.dev(o[k].oo.n);
         }
     }
-    const BowSlotJob* djobs = reinterpret_cast<const BowSlotJob*>(d + o_jobs);
+    const BowSlotJob* djobs = s.dev(o_jobs);
     if (!after) {
         timer_begin(ctx, "bow_match_slot");
         hipLaunchKernelGGL(k_bow_match_slot, dim3(n), dim3(kBlock), 0, ctx->stream, djobs);

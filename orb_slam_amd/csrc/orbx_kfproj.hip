@@ -26,6 +26,7 @@
 #include "orbx_device.h"
 #include "orbx_internal.h"
 #include "orbx_match_common.h"
+#include "orbx_stage.h"
 
 namespace orbx {
 
@@ -351,14 +352,6 @@ __global__ __launch_bounds__(64) void k_proj_seq(SeqProjArgs a)
 
 namespace {
 
-inline size_t al256(size_t b) { return (b + 255) & ~size_t(255); }
-
-bool valid_kf(const orbx_frame_view* v)
-{
-    return v && v->n >= 0 && v->n <= kMaxFeatures && (v->n == 0 || (v->keys_un && v->desc)) && v->max_x > v->min_x &&
-           v->max_y > v->min_y && v->nlevels > 0 && v->nlevels <= kMaxLevels;
-}
-
 bool valid_mps(const orbx_mappoint_view* p, bool need_normal)
 {
     return p && p->n >= 0 &&
@@ -387,83 +380,170 @@ void pose_parts(const float* T, int sim3, float* R, float* t, float* Ow)
     for (int c = 0; c < 3; c++) Ow[c] = -(R[c] * t[0] + R[3 + c] * t[1] + R[6 + c] * t[2]);
 }
 
-FrameDev kf_dev(const orbx_frame_view* v, const uint8_t* base, size_t kp_off, size_t desc_off)
+// The slot's count as the device holds it, at most nfeatures.
+int slot_count(const orbx_ctx* ctx, int32_t cnt) { return std::min<int>(cnt, ctx->geom.nfeatures); }
+
+// The frame in `slot` with the bounds the kfproj calls document: the
+// caller's, or 0..w x 0..h.
+FrameDev kf_slot_dev(const orbx_ctx* ctx, int slot, const float* bounds, int n)
 {
-    FrameDev F;
-    F.kps = reinterpret_cast<const orbx_keypoint*>(base + kp_off);
-    F.desc = base + desc_off;
-    F.n = v->n;
-    F.min_x = v->min_x;
-    F.max_x = v->max_x;
-    F.min_y = v->min_y;
-    F.max_y = v->max_y;
-    F.grid_w_inv = static_cast<float>(kGridCols) / (v->max_x - v->min_x);   // src/Frame.cc:76-77
-    F.grid_h_inv = static_cast<float>(kGridRows) / (v->max_y - v->min_y);
+    const float image[4] = {0.f, (float)ctx->geom.w, 0.f, (float)ctx->geom.h};
+    FrameDev F = slot_frame_dev(ctx, slot, bounds ? bounds : image);
+    F.n = n;
     return F;
 }
 
-struct Staging {
-    orbx_ctx* ctx;
-    size_t at = 0;
-    std::vector<std::pair<size_t, std::pair<const void*, size_t>>> puts;
-    size_t res(size_t bytes, const void* src = nullptr)
-    {
-        const size_t o = at;
-        at += al256(std::max<size_t>(bytes, 1));
-        if (src && bytes) puts.push_back({o, {src, bytes}});
-        return o;
-    }
-    int upload()
-    {
-        int r = ensure_scratch(ctx, at);
-        if (r != ORBX_OK) return r;
-        uint8_t* d = static_cast<uint8_t*>(ctx->scratch);
-        for (auto& p : puts)
-            ORBX_HIP_CHECK(hipMemcpyAsync(d + p.first, p.second.first, p.second.second, hipMemcpyHostToDevice,
-                                          ctx->stream));
-        return ORBX_OK;
-    }
-    uint8_t* base() const { return static_cast<uint8_t*>(ctx->scratch); }
+struct KfRegions {
+    Region<orbx_keypoint> kp;
+    Region<uint8_t> kd;
 };
 
-// Stages the keyframe and the map points, fills the common fields.
-struct ProjStage {
-    size_t kp, kd, pos, nrm, dmin, dmax, qd, qv, bi, bd;
-};
-
-ProjStage stage_proj(Staging& s, const orbx_frame_view* K, const orbx_mappoint_view* P, const uint8_t* qvalid)
+KfRegions take_kf(ArrayStage& s, const orbx_frame_view* K)
 {
-    ProjStage o;
-    o.kp = s.res((size_t)K->n * sizeof(orbx_keypoint), K->keys_un);
-    o.kd = s.res((size_t)K->n * 32, K->desc);
-    o.pos = s.res((size_t)P->n * 12, P->pos);
-    o.nrm = s.res((size_t)P->n * 12, P->normal);
-    o.dmin = s.res((size_t)P->n * 4, P->min_dist);
-    o.dmax = s.res((size_t)P->n * 4, P->max_dist);
-    o.qd = s.res((size_t)P->n * 32, P->desc);
-    o.qv = s.res((size_t)P->n, qvalid);
-    o.bi = s.res((size_t)P->n * 4);
-    o.bd = s.res((size_t)P->n * 4);
+    KfRegions o;
+    o.kp = s.take((size_t)K->n, K->keys_un);
+    o.kd = s.take((size_t)K->n * 32, K->desc);
     return o;
 }
 
-void fill_proj(KfProjArgs& a, const Staging& s, const ProjStage& o, const orbx_frame_view* K,
+struct MpRegions {
+    Region<float> pos, nrm, dmin, dmax;
+    Region<uint8_t> qd;
+};
+
+MpRegions take_mps(ArrayStage& s, const orbx_mappoint_view* P)
+{
+    MpRegions o;
+    o.pos = s.take((size_t)P->n * 3, P->pos);
+    o.nrm = s.take((size_t)P->n * 3, P->normal);
+    o.dmin = s.take((size_t)P->n, P->min_dist);
+    o.dmax = s.take((size_t)P->n, P->max_dist);
+    o.qd = s.take((size_t)P->n * 32, P->desc);
+    return o;
+}
+
+// KfProjArgs and SeqProjArgs name the map-point arrays alike.
+template <typename Args>
+void set_mps(Args& a, const ArrayStage& s, const MpRegions& o, int nq)
+{
+    a.nq = nq;
+    a.pos = s.dev(o.pos);
+    a.normal = s.dev(o.nrm);
+    a.dmin = s.dev(o.dmin);
+    a.dmax = s.dev(o.dmax);
+    a.qdesc = s.dev(o.qd);
+}
+
+// Stages the keyframe and the map points, fills the common fields.
+struct ProjStage {
+    KfRegions k;
+    MpRegions mp;
+    Region<uint8_t> qv;
+    Region<int32_t> bi, bd;
+};
+
+ProjStage stage_proj(ArrayStage& s, const orbx_frame_view* K, const orbx_mappoint_view* P, const uint8_t* qvalid)
+{
+    ProjStage o;
+    o.k = take_kf(s, K);
+    o.mp = take_mps(s, P);
+    o.qv = s.take((size_t)P->n, qvalid);
+    o.bi = s.take<int32_t>(P->n);
+    o.bd = s.take<int32_t>(P->n);
+    return o;
+}
+
+// One projection job of keyframe K (n levels of scale_factor) over nq points.
+void fill_job(KfProjArgs& a, const ArrayStage& s, const FrameDev& K, int nlevels, float scale_factor,
+              const MpRegions& mp, int nq, Region<int32_t> bi, Region<int32_t> bd)
+{
+    a.K = K;
+    a.nlevels = nlevels;
+    level_scales(nlevels, scale_factor, a.scales);
+    set_mps(a, s, mp, nq);
+    a.best_idx = s.dev(bi);
+    a.best_dist = s.dev(bd);
+}
+
+void fill_proj(KfProjArgs& a, const ArrayStage& s, const ProjStage& o, const orbx_frame_view* K,
                const orbx_mappoint_view* P, bool has_valid)
 {
-    uint8_t* d = s.base();
-    a.K = kf_dev(K, d, o.kp, o.kd);
-    a.nlevels = K->nlevels;
-    a.scales[0] = 1.0f;
-    for (int l = 1; l < K->nlevels; l++) a.scales[l] = a.scales[l - 1] * K->scale_factor;   // src/Frame.cc:98-102
-    a.nq = P->n;
-    a.pos = reinterpret_cast<const float*>(d + o.pos);
-    a.normal = reinterpret_cast<const float*>(d + o.nrm);
-    a.dmin = reinterpret_cast<const float*>(d + o.dmin);
-    a.dmax = reinterpret_cast<const float*>(d + o.dmax);
-    a.qdesc = d + o.qd;
-    a.qvalid = has_valid ? d + o.qv : nullptr;
-    a.best_idx = reinterpret_cast<int32_t*>(d + o.bi);
-    a.best_dist = reinterpret_cast<int32_t*>(d + o.bd);
+    fill_job(a, s, frame_dev(K, s.dev(o.k.kp), s.dev(o.k.kd)), K->nlevels, K->scale_factor, o.mp, P->n, o.bi, o.bd);
+    a.qvalid = has_valid ? s.dev(o.qv) : nullptr;
+}
+
+// Fuse's job k of a batch: camera, pose and threshold.
+void set_fuse(KfProjArgs& a, const float* cam, const float* T, int sim3, float th)
+{
+    for (int c = 0; c < 4; c++) a.cam[c] = cam[c];
+    pose_parts(T, sim3, a.Ra, a.ta, a.Ow);
+    a.two_stage = 0;
+    a.mode = sim3 ? 1 : 0;
+    a.th = th;
+}
+
+// A fuse batch's tail: the job table up, one launch, each job's two result
+// arrays straight into the caller's.
+struct FuseOut {
+    Region<int32_t> bi, bd;
+};
+int run_fuse_jobs(ArrayStage& s, const std::vector<KfProjArgs>& jobs, Region<KfProjArgs> o_jobs, int max_q, int max_n,
+                  const std::vector<FuseOut>& o, int32_t* const* best_idx, int32_t* const* best_dist)
+{
+    orbx_ctx* ctx = s.ctx;
+    s.later(o_jobs, jobs.data());
+    int r = s.upload();
+    if (r != ORBX_OK) return r;
+    if (max_q > 0) {
+        const int per = kBlock / 64;
+        hipLaunchKernelGGL(k_kf_project_jobs, dim3((max_q + per - 1) / per, (unsigned)jobs.size()), dim3(kBlock),
+                           (size_t)max_n * 12, ctx->stream, s.dev(o_jobs));
+        ORBX_HIP_CHECK(hipGetLastError());
+    }
+    for (size_t k = 0; k < jobs.size(); k++)
+        if ((r = s.get(best_idx[k], o[k].bi)) || (r = s.get(best_dist[k], o[k].bd))) return r;
+    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return ORBX_OK;
+}
+
+// The map points of job k: those of an earlier job that passed the same view
+// (uploaded once), else staged here.
+MpRegions take_shared_mps(ArrayStage& s, const orbx_mappoint_view* const* mps, const std::vector<MpRegions>& mp, int k)
+{
+    for (int j = 0; j < k; j++)
+        if (mps[j] == mps[k]) return mp[j];
+    return take_mps(s, mps[k]);
+}
+
+// k_proj_seq over the frame a.T, then its matches (n of them) and their
+// count into the caller's memory.
+int run_proj_seq(ArrayStage& s, SeqProjArgs& a, Region<int32_t> out, Region<int32_t> out_n, int32_t* matches,
+                 int* n_matches)
+{
+    orbx_ctx* ctx = s.ctx;
+    a.out = s.dev(out);
+    a.out_n = s.dev(out_n);
+    const size_t lds = (size_t)std::max(a.T.n, 1) * 21 + 32 * 4 + 64;
+    hipLaunchKernelGGL(k_proj_seq, dim3(1), dim3(64), lds, ctx->stream, a);
+    ORBX_HIP_CHECK(hipGetLastError());
+    int r;
+    if ((r = s.get(matches, out, a.T.n)) || (r = s.get(n_matches, out_n))) return r;
+    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return ORBX_OK;
+}
+
+// What the sequential searches set alike: the searched frame, its pyramid,
+// camera and pose.
+void set_seq(SeqProjArgs& a, const FrameDev& T, int nlevels, float scale_factor, const float* cam, const float* pose,
+             int sim3, float th, int variant)
+{
+    a.T = T;
+    a.nlevels = nlevels;
+    level_scales(nlevels, scale_factor, a.scales);
+    for (int k = 0; k < 4; k++) a.cam[k] = cam[k];
+    pose_parts(pose, sim3, a.R, a.t, a.Ow);
+    a.th = th;
+    a.variant = variant;
 }
 
 int launch_proj(orbx_ctx* ctx, const KfProjArgs& a)
@@ -485,25 +565,19 @@ extern "C" int orbx_fuse_candidates(orbx_ctx* ctx, const orbx_frame_view* KF, co
                                     const orbx_mappoint_view* mps, const float* T, int sim3, float th,
                                     int32_t* best_idx, int32_t* best_dist)
 {
-    if (!ctx || !valid_kf(KF) || !cam || !valid_mps(mps, true) || !T || (mps->n > 0 && (!best_idx || !best_dist)))
+    if (!ctx || !valid_frame_view(KF) || !cam || !valid_mps(mps, true) || !T ||
+        (mps->n > 0 && (!best_idx || !best_dist)))
         return ORBX_ERR_ARG;
     ctx_enter(ctx);
-    Staging s{ctx};
+    ArrayStage s(ctx);
     const ProjStage o = stage_proj(s, KF, mps, nullptr);
     int r = s.upload();
     if (r != ORBX_OK) return r;
     KfProjArgs a{};
     fill_proj(a, s, o, KF, mps, false);
-    for (int k = 0; k < 4; k++) a.cam[k] = cam[k];
-    pose_parts(T, sim3, a.Ra, a.ta, a.Ow);
-    a.two_stage = 0;
-    a.mode = sim3 ? 1 : 0;
-    a.th = th;
+    set_fuse(a, cam, T, sim3, th);
     if ((r = launch_proj(ctx, a)) != ORBX_OK) return r;
-    if (mps->n) {
-        ORBX_HIP_CHECK(hipMemcpyAsync(best_idx, s.base() + o.bi, (size_t)mps->n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        ORBX_HIP_CHECK(hipMemcpyAsync(best_dist, s.base() + o.bd, (size_t)mps->n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
+    if ((r = s.get(best_idx, o.bi)) || (r = s.get(best_dist, o.bd))) return r;
     ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return ORBX_OK;
 }
@@ -518,88 +592,34 @@ extern "C" int orbx_fuse_candidates_batch(orbx_ctx* ctx, int n_kf, const orbx_fr
 {
     if (!ctx || n_kf < 0 || (n_kf > 0 && (!KFs || !cams || !mps || !Ts || !best_idx || !best_dist))) return ORBX_ERR_ARG;
     for (int k = 0; k < n_kf; k++)
-        if (!valid_kf(&KFs[k]) || !valid_mps(mps[k], true) || (mps[k]->n > 0 && (!best_idx[k] || !best_dist[k])))
+        if (!valid_frame_view(&KFs[k]) || !valid_mps(mps[k], true) || (mps[k]->n > 0 && (!best_idx[k] || !best_dist[k])))
             return ORBX_ERR_ARG;
     if (n_kf == 0) return ORBX_OK;
     ctx_enter(ctx);
-    Staging s{ctx};
-    struct Off {
-        size_t kp, kd, pos, nrm, dmin, dmax, qd, bi, bd;
-    };
-    std::vector<Off> o(n_kf);
+    ArrayStage s(ctx);
+    std::vector<KfRegions> kf(n_kf);
+    std::vector<MpRegions> mp(n_kf);
+    std::vector<FuseOut> o(n_kf);
     int max_n = 1, max_q = 0;
     for (int k = 0; k < n_kf; k++) {
-        const orbx_frame_view* K = &KFs[k];
-        const orbx_mappoint_view* P = mps[k];
-        o[k].kp = s.res((size_t)K->n * sizeof(orbx_keypoint), K->keys_un);
-        o[k].kd = s.res((size_t)K->n * 32, K->desc);
-        int same = -1;
-        for (int j = 0; j < k && same < 0; j++)
-            if (mps[j] == P) same = j;
-        if (same >= 0) {   // the same map points: reuse their upload
-            o[k].pos = o[same].pos;
-            o[k].nrm = o[same].nrm;
-            o[k].dmin = o[same].dmin;
-            o[k].dmax = o[same].dmax;
-            o[k].qd = o[same].qd;
-        } else {
-            o[k].pos = s.res((size_t)P->n * 12, P->pos);
-            o[k].nrm = s.res((size_t)P->n * 12, P->normal);
-            o[k].dmin = s.res((size_t)P->n * 4, P->min_dist);
-            o[k].dmax = s.res((size_t)P->n * 4, P->max_dist);
-            o[k].qd = s.res((size_t)P->n * 32, P->desc);
-        }
-        o[k].bi = s.res((size_t)P->n * 4);
-        o[k].bd = s.res((size_t)P->n * 4);
-        max_n = std::max(max_n, K->n);
-        max_q = std::max(max_q, P->n);
+        kf[k] = take_kf(s, &KFs[k]);
+        mp[k] = take_shared_mps(s, mps, mp, k);
+        o[k].bi = s.take<int32_t>(mps[k]->n);
+        o[k].bd = s.take<int32_t>(mps[k]->n);
+        max_n = std::max(max_n, KFs[k].n);
+        max_q = std::max(max_q, mps[k]->n);
     }
-    const size_t o_jobs = s.res(sizeof(KfProjArgs) * (size_t)n_kf);
+    const Region<KfProjArgs> o_jobs = s.take<KfProjArgs>(n_kf);
     std::vector<KfProjArgs> jobs(n_kf);
-    uint8_t* d = nullptr;
-    int r = ensure_scratch(ctx, s.at);
+    const int r = s.open();
     if (r != ORBX_OK) return r;
-    d = s.base();
     for (int k = 0; k < n_kf; k++) {
         const orbx_frame_view* K = &KFs[k];
-        KfProjArgs& a = jobs[k];
-        a = KfProjArgs{};
-        a.K = kf_dev(K, d, o[k].kp, o[k].kd);
-        a.nlevels = K->nlevels;
-        a.scales[0] = 1.0f;
-        for (int l = 1; l < K->nlevels; l++) a.scales[l] = a.scales[l - 1] * K->scale_factor;   // src/Frame.cc:98-102
-        a.nq = mps[k]->n;
-        a.pos = reinterpret_cast<const float*>(d + o[k].pos);
-        a.normal = reinterpret_cast<const float*>(d + o[k].nrm);
-        a.dmin = reinterpret_cast<const float*>(d + o[k].dmin);
-        a.dmax = reinterpret_cast<const float*>(d + o[k].dmax);
-        a.qdesc = d + o[k].qd;
-        a.qvalid = nullptr;
-        a.best_idx = reinterpret_cast<int32_t*>(d + o[k].bi);
-        a.best_dist = reinterpret_cast<int32_t*>(d + o[k].bd);
-        for (int c = 0; c < 4; c++) a.cam[c] = cams[4 * k + c];
-        pose_parts(Ts + 16 * k, sim3, a.Ra, a.ta, a.Ow);
-        a.two_stage = 0;
-        a.mode = sim3 ? 1 : 0;
-        a.th = th;
+        fill_job(jobs[k], s, frame_dev(K, s.dev(kf[k].kp), s.dev(kf[k].kd)), K->nlevels, K->scale_factor, mp[k],
+                 mps[k]->n, o[k].bi, o[k].bd);
+        set_fuse(jobs[k], cams + 4 * k, Ts + 16 * k, sim3, th);
     }
-    s.puts.push_back({o_jobs, {jobs.data(), sizeof(KfProjArgs) * (size_t)n_kf}});
-    if ((r = s.upload()) != ORBX_OK) return r;
-    if (max_q > 0) {
-        const int per = kBlock / 64;
-        hipLaunchKernelGGL(k_kf_project_jobs, dim3((max_q + per - 1) / per, n_kf), dim3(kBlock), (size_t)max_n * 12,
-                           ctx->stream, reinterpret_cast<const KfProjArgs*>(d + o_jobs));
-        ORBX_HIP_CHECK(hipGetLastError());
-    }
-    for (int k = 0; k < n_kf; k++)
-        if (mps[k]->n) {
-            ORBX_HIP_CHECK(hipMemcpyAsync(best_idx[k], d + o[k].bi, (size_t)mps[k]->n * 4, hipMemcpyDeviceToHost,
-                                          ctx->stream));
-            ORBX_HIP_CHECK(hipMemcpyAsync(best_dist[k], d + o[k].bd, (size_t)mps[k]->n * 4, hipMemcpyDeviceToHost,
-                                          ctx->stream));
-        }
-    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return ORBX_OK;
+    return run_fuse_jobs(s, jobs, o_jobs, max_q, max_n, o, best_idx, best_dist);
 }
 
 // LocalMapping::SearchInNeighbors' Fuse loop against keyframes that stay in
@@ -627,87 +647,29 @@ extern "C" int orbx_dev_fuse_candidates(orbx_ctx* ctx, int n_kf, const int* slot
                                   ctx->stream));
     ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     const Geometry& g = ctx->geom;
-    const size_t nf = g.nfeatures;
-    Staging s{ctx};
-    struct Off {
-        size_t pos, nrm, dmin, dmax, qd, bi, bd;
-    };
-    std::vector<Off> o(n_kf);
+    ArrayStage s(ctx);
+    std::vector<MpRegions> mp(n_kf);
+    std::vector<FuseOut> o(n_kf);
     int max_n = 1, max_q = 0;
     for (int k = 0; k < n_kf; k++) {
-        const orbx_mappoint_view* P = mps[k];
-        int same = -1;
-        for (int j = 0; j < k && same < 0; j++)
-            if (mps[j] == P) same = j;
-        if (same >= 0) {
-            o[k] = o[same];
-        } else {
-            o[k].pos = s.res((size_t)P->n * 12, P->pos);
-            o[k].nrm = s.res((size_t)P->n * 12, P->normal);
-            o[k].dmin = s.res((size_t)P->n * 4, P->min_dist);
-            o[k].dmax = s.res((size_t)P->n * 4, P->max_dist);
-            o[k].qd = s.res((size_t)P->n * 32, P->desc);
-        }
-        o[k].bi = s.res((size_t)P->n * 4);
-        o[k].bd = s.res((size_t)P->n * 4);
-        max_n = std::max(max_n, std::min<int>(cnt[slots[k]], (int)nf));
-        max_q = std::max(max_q, P->n);
+        mp[k] = take_shared_mps(s, mps, mp, k);
+        o[k].bi = s.take<int32_t>(mps[k]->n);
+        o[k].bd = s.take<int32_t>(mps[k]->n);
+        max_n = std::max(max_n, slot_count(ctx, cnt[slots[k]]));
+        max_q = std::max(max_q, mps[k]->n);
     }
-    const size_t o_jobs = s.res(sizeof(KfProjArgs) * (size_t)n_kf);
+    const Region<KfProjArgs> o_jobs = s.take<KfProjArgs>(n_kf);
     std::vector<KfProjArgs> jobs(n_kf);
-    int r = ensure_scratch(ctx, s.at);
+    const int r = s.open();
     if (r != ORBX_OK) return r;
-    uint8_t* d = s.base();
     for (int k = 0; k < n_kf; k++) {
-        const int sl = slots[k];
-        // the extracted frame as a keyframe view (bounds: the caller's
+        // the extracted frame as a keyframe (bounds: the caller's
         // ComputeImageBounds, or the undistorted image 0..w, 0..h)
-        orbx_frame_view v{};
-        v.n = std::min<int>(cnt[sl], (int)nf);
-        v.min_x = bounds ? bounds[4 * k] : 0.f;
-        v.max_x = bounds ? bounds[4 * k + 1] : (float)g.w;
-        v.min_y = bounds ? bounds[4 * k + 2] : 0.f;
-        v.max_y = bounds ? bounds[4 * k + 3] : (float)g.h;
-        KfProjArgs& a = jobs[k];
-        a = KfProjArgs{};
-        a.K = kf_dev(&v, nullptr, 0, 0);
-        a.K.kps = ctx->out_kps + (size_t)sl * nf;
-        a.K.desc = ctx->out_desc + (size_t)sl * nf * 32;
-        a.nlevels = g.nlevels;
-        a.scales[0] = 1.0f;
-        for (int l = 1; l < g.nlevels; l++) a.scales[l] = a.scales[l - 1] * g.scale_factor;   // src/Frame.cc:98-102
-        a.nq = mps[k]->n;
-        a.pos = reinterpret_cast<const float*>(d + o[k].pos);
-        a.normal = reinterpret_cast<const float*>(d + o[k].nrm);
-        a.dmin = reinterpret_cast<const float*>(d + o[k].dmin);
-        a.dmax = reinterpret_cast<const float*>(d + o[k].dmax);
-        a.qdesc = d + o[k].qd;
-        a.qvalid = nullptr;
-        a.best_idx = reinterpret_cast<int32_t*>(d + o[k].bi);
-        a.best_dist = reinterpret_cast<int32_t*>(d + o[k].bd);
-        for (int c = 0; c < 4; c++) a.cam[c] = cams[4 * k + c];
-        pose_parts(Ts + 16 * k, sim3, a.Ra, a.ta, a.Ow);
-        a.two_stage = 0;
-        a.mode = sim3 ? 1 : 0;
-        a.th = th;
+        const FrameDev K = kf_slot_dev(ctx, slots[k], bounds ? bounds + 4 * k : nullptr, slot_count(ctx, cnt[slots[k]]));
+        fill_job(jobs[k], s, K, g.nlevels, g.scale_factor, mp[k], mps[k]->n, o[k].bi, o[k].bd);
+        set_fuse(jobs[k], cams + 4 * k, Ts + 16 * k, sim3, th);
     }
-    s.puts.push_back({o_jobs, {jobs.data(), sizeof(KfProjArgs) * (size_t)n_kf}});
-    if ((r = s.upload()) != ORBX_OK) return r;
-    if (max_q > 0) {
-        const int per = kBlock / 64;
-        hipLaunchKernelGGL(k_kf_project_jobs, dim3((max_q + per - 1) / per, n_kf), dim3(kBlock), (size_t)max_n * 12,
-                           ctx->stream, reinterpret_cast<const KfProjArgs*>(d + o_jobs));
-        ORBX_HIP_CHECK(hipGetLastError());
-    }
-    for (int k = 0; k < n_kf; k++)
-        if (mps[k]->n) {
-            ORBX_HIP_CHECK(hipMemcpyAsync(best_idx[k], d + o[k].bi, (size_t)mps[k]->n * 4, hipMemcpyDeviceToHost,
-                                          ctx->stream));
-            ORBX_HIP_CHECK(hipMemcpyAsync(best_dist[k], d + o[k].bd, (size_t)mps[k]->n * 4, hipMemcpyDeviceToHost,
-                                          ctx->stream));
-        }
-    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return ORBX_OK;
+    return run_fuse_jobs(s, jobs, o_jobs, max_q, max_n, o, best_idx, best_dist);
 }
 
 // SearchBySim3 for keyframe views whose keypoints and descriptors are on
@@ -746,7 +708,7 @@ static int run_sim3(orbx_ctx* ctx, const orbx_frame_view* KF1, const orbx_frame_
         }
     for (int r = 0; r < 3; r++) t21[r] = -(sR21[3 * r] * t12[0] + sR21[3 * r + 1] * t12[1] + sR21[3 * r + 2] * t12[2]);
     ctx_enter(ctx);
-    Staging s{ctx};
+    ArrayStage s(ctx);
     const ProjStage o1 = stage_proj(s, KF2, mp1, q1.data());   // KF1 points searched in KF2
     const ProjStage o2 = stage_proj(s, KF1, mp2, q2.data());   // KF2 points searched in KF1
     int r = s.upload();
@@ -782,14 +744,9 @@ static int run_sim3(orbx_ctx* ctx, const orbx_frame_view* KF1, const orbx_frame_
     b.th = th;
     if ((r = launch_proj(ctx, b)) != ORBX_OK) return r;
     std::vector<int32_t> bi1(N1), bd1(N1), bi2(N2), bd2(N2);
-    if (N1) {
-        ORBX_HIP_CHECK(hipMemcpyAsync(bi1.data(), s.base() + o1.bi, (size_t)N1 * 4, hipMemcpyDeviceToHost, ctx->stream));
-        ORBX_HIP_CHECK(hipMemcpyAsync(bd1.data(), s.base() + o1.bd, (size_t)N1 * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (N2) {
-        ORBX_HIP_CHECK(hipMemcpyAsync(bi2.data(), s.base() + o2.bi, (size_t)N2 * 4, hipMemcpyDeviceToHost, ctx->stream));
-        ORBX_HIP_CHECK(hipMemcpyAsync(bd2.data(), s.base() + o2.bd, (size_t)N2 * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
+    if ((r = s.get(bi1.data(), o1.bi)) || (r = s.get(bd1.data(), o1.bd)) || (r = s.get(bi2.data(), o2.bi)) ||
+        (r = s.get(bd2.data(), o2.bd)))
+        return r;
     ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     // bestDist <= TH_HIGH (:1395, :1480), then the agreement check (:1486-1502)
     int nFound = 0;
@@ -811,7 +768,7 @@ extern "C" int orbx_search_by_sim3(orbx_ctx* ctx, const orbx_frame_view* KF1, co
                                    const float* T2w, float s12, const float* R12, const float* t12, float th,
                                    const int32_t* prior12, int32_t* new12, int* n_found)
 {
-    if (!ctx || !valid_kf(KF1) || !valid_kf(KF2) || !cam || !valid_mps(mp1, false) || !valid_mps(mp2, false) ||
+    if (!ctx || !valid_frame_view(KF1) || !valid_frame_view(KF2) || !cam || !valid_mps(mp1, false) || !valid_mps(mp2, false) ||
         mp1->n != KF1->n || mp2->n != KF2->n || (KF1->n && (!valid1 || !prior12 || !new12)) ||
         (KF2->n && !valid2) || !T1w || !T2w || !R12 || !t12 || !n_found)
         return ORBX_ERR_ARG;
@@ -839,8 +796,7 @@ extern "C" int orbx_dev_search_by_sim3(orbx_ctx* ctx, int slot1, const float* bo
                                   ctx->stream));
     ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     const Geometry& g = ctx->geom;
-    const size_t nf = g.nfeatures;
-    const int N1 = std::min<int>(cnt[slot1], (int)nf), N2 = std::min<int>(cnt[slot2], (int)nf);
+    const int N1 = slot_count(ctx, cnt[slot1]), N2 = slot_count(ctx, cnt[slot2]);
     if (mp1->n != N1 || mp2->n != N2 || (N1 && (!valid1 || !prior12)) || (N2 && !valid2)) return ORBX_ERR_ARG;
     if (cap < N1) return ORBX_ERR_CAPACITY;
     auto view = [&](int n, const float* b) {
@@ -855,9 +811,9 @@ extern "C" int orbx_dev_search_by_sim3(orbx_ctx* ctx, int slot1, const float* bo
         return v;
     };
     const orbx_frame_view K1 = view(N1, bounds1), K2 = view(N2, bounds2);
-    return run_sim3(ctx, &K1, &K2, ctx->out_kps + (size_t)slot1 * nf, ctx->out_desc + (size_t)slot1 * nf * 32,
-                    ctx->out_kps + (size_t)slot2 * nf, ctx->out_desc + (size_t)slot2 * nf * 32, cam, mp1, valid1, mp2,
-                    valid2, T1w, T2w, s12, R12, t12, th, prior12, new12, n_found);
+    const FrameDev S1 = slot_frame_dev(ctx, slot1, nullptr), S2 = slot_frame_dev(ctx, slot2, nullptr);
+    return run_sim3(ctx, &K1, &K2, S1.kps, S1.desc, S2.kps, S2.desc, cam, mp1, valid1, mp2, valid2, T1w, T2w, s12, R12,
+                    t12, th, prior12, new12, n_found);
 }
 
 extern "C" int orbx_distinctive_descriptors(orbx_ctx* ctx, int n_mp, const int32_t* obs_ptr, const uint8_t* desc,
@@ -871,63 +827,56 @@ extern "C" int orbx_distinctive_descriptors(orbx_ctx* ctx, int n_mp, const int32
     const size_t rows = (size_t)obs_ptr[n_mp];
     if (rows && !desc) return ORBX_ERR_ARG;
     ctx_enter(ctx);
-    Staging s{ctx};
-    const size_t o_ptr = s.res((size_t)(n_mp + 1) * 4, obs_ptr), o_d = s.res(rows * 32, desc),
-                 o_b = s.res((size_t)n_mp * 4);
+    ArrayStage s(ctx);
+    const Region<int32_t> o_ptr = s.take((size_t)n_mp + 1, obs_ptr);
+    const Region<uint8_t> o_d = s.take(rows * 32, desc);
+    const Region<int32_t> o_b = s.take<int32_t>(n_mp);
     int r = s.upload();
     if (r != ORBX_OK) return r;
     const int per = kBlock / 64;
-    hipLaunchKernelGGL(k_distinctive, dim3((n_mp + per - 1) / per), dim3(kBlock), 0, ctx->stream,
-                       reinterpret_cast<const int32_t*>(s.base() + o_ptr), s.base() + o_d, n_mp,
-                       reinterpret_cast<int32_t*>(s.base() + o_b));
+    hipLaunchKernelGGL(k_distinctive, dim3((n_mp + per - 1) / per), dim3(kBlock), 0, ctx->stream, s.dev(o_ptr),
+                       s.dev(o_d), n_mp, s.dev(o_b));
     ORBX_HIP_CHECK(hipGetLastError());
-    ORBX_HIP_CHECK(hipMemcpyAsync(best, s.base() + o_b, (size_t)n_mp * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if ((r = s.get(best, o_b)) != ORBX_OK) return r;
     ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return ORBX_OK;
+}
+
+// SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) against the keyframe
+// T, whose keypoints and descriptors are staged here (kf) or already on the
+// device (kf null).  matched: T.n entries, in and out.
+static int run_kf_sim3(ArrayStage& s, const KfRegions* kf, FrameDev T, int nlevels, float scale_factor,
+                       const float* cam, const orbx_mappoint_view* mps, const uint8_t* mp_skip, const float* Scw, int th,
+                       int32_t* matched, int* n_matches)
+{
+    const MpRegions mp = take_mps(s, mps);
+    const Region<uint8_t> o_sk = s.take((size_t)mps->n, mp_skip);
+    const Region<int32_t> o_out = s.take((size_t)T.n, matched), o_n = s.take<int32_t>(1);
+    const int r = s.upload();
+    if (r != ORBX_OK) return r;
+    if (kf) {
+        T.kps = s.dev(kf->kp);
+        T.desc = s.dev(kf->kd);
+    }
+    SeqProjArgs a{};
+    set_seq(a, T, nlevels, scale_factor, cam, Scw, 1, (float)th, 0);
+    set_mps(a, s, mp, mps->n);
+    a.qskip = s.dev(o_sk);
+    return run_proj_seq(s, a, o_out, o_n, matched, n_matches);
 }
 
 extern "C" int orbx_search_by_projection_kf_sim3(orbx_ctx* ctx, const orbx_frame_view* KF, const float* cam,
                                                  const orbx_mappoint_view* mps, const uint8_t* mp_skip,
                                                  const float* Scw, int th, int32_t* matched, int* n_matches)
 {
-    if (!ctx || !valid_kf(KF) || !cam || !valid_mps(mps, true) || !Scw || !n_matches || (mps->n && !mp_skip) ||
-        (KF->n && !matched))
+    if (!ctx || !valid_frame_view(KF) || !cam || !valid_mps(mps, true) || !Scw || !n_matches ||
+        (mps->n && !mp_skip) || (KF->n && !matched))
         return ORBX_ERR_ARG;
     ctx_enter(ctx);
-    Staging s{ctx};
-    const size_t o_kp = s.res((size_t)KF->n * sizeof(orbx_keypoint), KF->keys_un), o_kd = s.res((size_t)KF->n * 32, KF->desc);
-    const size_t o_pos = s.res((size_t)mps->n * 12, mps->pos), o_nrm = s.res((size_t)mps->n * 12, mps->normal),
-                 o_mn = s.res((size_t)mps->n * 4, mps->min_dist), o_mx = s.res((size_t)mps->n * 4, mps->max_dist),
-                 o_qd = s.res((size_t)mps->n * 32, mps->desc), o_sk = s.res(mps->n, mp_skip),
-                 o_out = s.res((size_t)KF->n * 4, matched), o_n = s.res(4);
-    int r = s.upload();
-    if (r != ORBX_OK) return r;
-    uint8_t* d = s.base();
-    SeqProjArgs a{};
-    a.T = kf_dev(KF, d, o_kp, o_kd);
-    a.nlevels = KF->nlevels;
-    a.scales[0] = 1.0f;
-    for (int l = 1; l < KF->nlevels; l++) a.scales[l] = a.scales[l - 1] * KF->scale_factor;
-    for (int k = 0; k < 4; k++) a.cam[k] = cam[k];
-    pose_parts(Scw, 1, a.R, a.t, a.Ow);
-    a.th = (float)th;
-    a.variant = 0;
-    a.nq = mps->n;
-    a.pos = reinterpret_cast<const float*>(d + o_pos);
-    a.normal = reinterpret_cast<const float*>(d + o_nrm);
-    a.dmin = reinterpret_cast<const float*>(d + o_mn);
-    a.dmax = reinterpret_cast<const float*>(d + o_mx);
-    a.qdesc = d + o_qd;
-    a.qskip = d + o_sk;
-    a.out = reinterpret_cast<int32_t*>(d + o_out);
-    a.out_n = reinterpret_cast<int32_t*>(d + o_n);
-    const size_t lds = (size_t)std::max(KF->n, 1) * 21 + 32 * 4 + 64;
-    hipLaunchKernelGGL(k_proj_seq, dim3(1), dim3(64), lds, ctx->stream, a);
-    ORBX_HIP_CHECK(hipGetLastError());
-    if (KF->n) ORBX_HIP_CHECK(hipMemcpyAsync(matched, d + o_out, (size_t)KF->n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    ORBX_HIP_CHECK(hipMemcpyAsync(n_matches, d + o_n, 4, hipMemcpyDeviceToHost, ctx->stream));
-    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return ORBX_OK;
+    ArrayStage s(ctx);
+    const KfRegions kf = take_kf(s, KF);
+    return run_kf_sim3(s, &kf, frame_dev(KF, nullptr, nullptr), KF->nlevels, KF->scale_factor, cam, mps, mp_skip, Scw,
+                       th, matched, n_matches);
 }
 
 // LoopClosing::ComputeSim3 / CorrectLoop's SearchByProjection(pKF, Scw, ...)
@@ -945,51 +894,48 @@ extern "C" int orbx_dev_search_by_projection_kf_sim3(orbx_ctx* ctx, int slot, co
     int32_t cnt = 0;
     ORBX_HIP_CHECK(hipMemcpyAsync(&cnt, ctx->out_n + slot, 4, hipMemcpyDeviceToHost, ctx->stream));
     ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    const Geometry& g = ctx->geom;
-    const size_t nf = g.nfeatures;
-    const int n = std::min<int>(cnt, (int)nf);
+    const int n = slot_count(ctx, cnt);
     if (cap < n) return ORBX_ERR_CAPACITY;
-    Staging s{ctx};
-    const size_t o_pos = s.res((size_t)mps->n * 12, mps->pos), o_nrm = s.res((size_t)mps->n * 12, mps->normal),
-                 o_mn = s.res((size_t)mps->n * 4, mps->min_dist), o_mx = s.res((size_t)mps->n * 4, mps->max_dist),
-                 o_qd = s.res((size_t)mps->n * 32, mps->desc), o_sk = s.res(mps->n, mp_skip),
-                 o_out = s.res((size_t)n * 4, matched), o_n = s.res(4);
+    ArrayStage s(ctx);
+    return run_kf_sim3(s, nullptr, kf_slot_dev(ctx, slot, bounds, n), ctx->geom.nlevels, ctx->geom.scale_factor, cam,
+                       mps, mp_skip, Scw, th, matched, n_matches);
+}
+
+// SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) of the nK
+// keyframe keypoints (their keys staged at qk, or at dev_qkps) in the frame
+// T, staged (f) or on the device (f null).
+static int run_frame_kf(ArrayStage& s, const KfRegions* f, FrameDev T, int nlevels, float scale_factor,
+                        Region<orbx_keypoint> qk, const orbx_keypoint* dev_qkps, int nK, const float* cam,
+                        const orbx_mappoint_view* kf_mps, const uint8_t* kf_valid, const uint8_t* f_assigned,
+                        const float* Tcw, float th, int orb_dist, int check_ori, int32_t* matches_f, int* n_matches)
+{
+    const Region<float> o_pos = s.take((size_t)nK * 3, kf_mps->pos), o_mn = s.take((size_t)nK, kf_mps->min_dist);
+    const Region<uint8_t> o_qd = s.take((size_t)nK * 32, kf_mps->desc), o_sk = s.take<uint8_t>(nK),
+                          o_as = s.take((size_t)T.n, f_assigned);
+    // at least one entry, all -1 before the search
+    const Region<int32_t> o_out = s.take<int32_t>(std::max(T.n, 1)), o_n = s.take<int32_t>(1);
+    std::vector<uint8_t> skip(nK);
+    for (int i = 0; i < nK; i++) skip[i] = !kf_valid[i];
+    s.later(o_sk, skip.data());
     int r = s.upload();
+    if (r == ORBX_OK) r = s.fill(o_out, 0xFF);
     if (r != ORBX_OK) return r;
-    uint8_t* d = s.base();
-    orbx_frame_view v{};
-    v.n = n;
-    v.min_x = bounds ? bounds[0] : 0.f;
-    v.max_x = bounds ? bounds[1] : (float)g.w;
-    v.min_y = bounds ? bounds[2] : 0.f;
-    v.max_y = bounds ? bounds[3] : (float)g.h;
+    if (f) {
+        T.kps = s.dev(f->kp);
+        T.desc = s.dev(f->kd);
+    }
     SeqProjArgs a{};
-    a.T = kf_dev(&v, nullptr, 0, 0);
-    a.T.kps = ctx->out_kps + (size_t)slot * nf;
-    a.T.desc = ctx->out_desc + (size_t)slot * nf * 32;
-    a.nlevels = g.nlevels;
-    a.scales[0] = 1.0f;
-    for (int l = 1; l < g.nlevels; l++) a.scales[l] = a.scales[l - 1] * g.scale_factor;
-    for (int k = 0; k < 4; k++) a.cam[k] = cam[k];
-    pose_parts(Scw, 1, a.R, a.t, a.Ow);
-    a.th = (float)th;
-    a.variant = 0;
-    a.nq = mps->n;
-    a.pos = reinterpret_cast<const float*>(d + o_pos);
-    a.normal = reinterpret_cast<const float*>(d + o_nrm);
-    a.dmin = reinterpret_cast<const float*>(d + o_mn);
-    a.dmax = reinterpret_cast<const float*>(d + o_mx);
-    a.qdesc = d + o_qd;
-    a.qskip = d + o_sk;
-    a.out = reinterpret_cast<int32_t*>(d + o_out);
-    a.out_n = reinterpret_cast<int32_t*>(d + o_n);
-    const size_t lds = (size_t)std::max(n, 1) * 21 + 32 * 4 + 64;
-    hipLaunchKernelGGL(k_proj_seq, dim3(1), dim3(64), lds, ctx->stream, a);
-    ORBX_HIP_CHECK(hipGetLastError());
-    if (n) ORBX_HIP_CHECK(hipMemcpyAsync(matched, d + o_out, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    ORBX_HIP_CHECK(hipMemcpyAsync(n_matches, d + o_n, 4, hipMemcpyDeviceToHost, ctx->stream));
-    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return ORBX_OK;
+    set_seq(a, T, nlevels, scale_factor, cam, Tcw, 0, th, 1);
+    a.orb_dist = orb_dist;
+    a.check_ori = check_ori;
+    a.nq = nK;
+    a.pos = s.dev(o_pos);
+    a.dmin = s.dev(o_mn);
+    a.qdesc = s.dev(o_qd);
+    a.qskip = s.dev(o_sk);
+    a.qkps = dev_qkps ? dev_qkps : s.dev(qk);
+    a.assigned = s.dev(o_as);
+    return run_proj_seq(s, a, o_out, o_n, matches_f, n_matches);
 }
 
 extern "C" int orbx_search_by_projection_frame_kf(orbx_ctx* ctx, const orbx_frame_view* F, const orbx_frame_view* KF,
@@ -998,50 +944,15 @@ extern "C" int orbx_search_by_projection_frame_kf(orbx_ctx* ctx, const orbx_fram
                                                   const float* Tcw, float th, int orb_dist, int check_ori,
                                                   int32_t* matches_f, int* n_matches)
 {
-    if (!ctx || !valid_kf(F) || !valid_kf(KF) || !cam || !valid_mps(kf_mps, false) || kf_mps->n != KF->n || !Tcw ||
-        !n_matches || (KF->n && !kf_valid) || (F->n && (!f_assigned || !matches_f)))
+    if (!ctx || !valid_frame_view(F) || !valid_frame_view(KF) || !cam || !valid_mps(kf_mps, false) ||
+        kf_mps->n != KF->n || !Tcw || !n_matches || (KF->n && !kf_valid) || (F->n && (!f_assigned || !matches_f)))
         return ORBX_ERR_ARG;
     ctx_enter(ctx);
-    Staging s{ctx};
-    const size_t o_kp = s.res((size_t)F->n * sizeof(orbx_keypoint), F->keys_un), o_kd = s.res((size_t)F->n * 32, F->desc);
-    const size_t o_qk = s.res((size_t)KF->n * sizeof(orbx_keypoint), KF->keys_un),
-                 o_pos = s.res((size_t)KF->n * 12, kf_mps->pos), o_mn = s.res((size_t)KF->n * 4, kf_mps->min_dist),
-                 o_qd = s.res((size_t)KF->n * 32, kf_mps->desc), o_sk = s.res(KF->n), o_as = s.res(F->n, f_assigned),
-                 o_out = s.res((size_t)F->n * 4), o_n = s.res(4);
-    std::vector<uint8_t> skip(KF->n);
-    for (int i = 0; i < KF->n; i++) skip[i] = !kf_valid[i];
-    if (KF->n) s.puts.push_back({o_sk, {skip.data(), (size_t)KF->n}});
-    int r = s.upload();
-    if (r != ORBX_OK) return r;
-    uint8_t* d = s.base();
-    ORBX_HIP_CHECK(hipMemsetAsync(d + o_out, 0xFF, (size_t)std::max(F->n, 1) * 4, ctx->stream));
-    SeqProjArgs a{};
-    a.T = kf_dev(F, d, o_kp, o_kd);
-    a.nlevels = F->nlevels;
-    a.scales[0] = 1.0f;
-    for (int l = 1; l < F->nlevels; l++) a.scales[l] = a.scales[l - 1] * F->scale_factor;
-    for (int k = 0; k < 4; k++) a.cam[k] = cam[k];
-    pose_parts(Tcw, 0, a.R, a.t, a.Ow);
-    a.th = th;
-    a.orb_dist = orb_dist;
-    a.check_ori = check_ori;
-    a.variant = 1;
-    a.nq = KF->n;
-    a.pos = reinterpret_cast<const float*>(d + o_pos);
-    a.dmin = reinterpret_cast<const float*>(d + o_mn);
-    a.qdesc = d + o_qd;
-    a.qskip = d + o_sk;
-    a.qkps = reinterpret_cast<const orbx_keypoint*>(d + o_qk);
-    a.assigned = d + o_as;
-    a.out = reinterpret_cast<int32_t*>(d + o_out);
-    a.out_n = reinterpret_cast<int32_t*>(d + o_n);
-    const size_t lds = (size_t)std::max(F->n, 1) * 21 + 32 * 4 + 64;
-    hipLaunchKernelGGL(k_proj_seq, dim3(1), dim3(64), lds, ctx->stream, a);
-    ORBX_HIP_CHECK(hipGetLastError());
-    if (F->n) ORBX_HIP_CHECK(hipMemcpyAsync(matches_f, d + o_out, (size_t)F->n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    ORBX_HIP_CHECK(hipMemcpyAsync(n_matches, d + o_n, 4, hipMemcpyDeviceToHost, ctx->stream));
-    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return ORBX_OK;
+    ArrayStage s(ctx);
+    const KfRegions f = take_kf(s, F);
+    const Region<orbx_keypoint> qk = s.take((size_t)KF->n, KF->keys_un);
+    return run_frame_kf(s, &f, frame_dev(F, nullptr, nullptr), F->nlevels, F->scale_factor, qk, nullptr, KF->n, cam,
+                        kf_mps, kf_valid, f_assigned, Tcw, th, orb_dist, check_ori, matches_f, n_matches);
 }
 
 // Tracking::Relocalisation's second search, SearchByProjection(CurrentFrame,
@@ -1065,55 +976,12 @@ extern "C" int orbx_dev_search_by_projection_frame_kf(orbx_ctx* ctx, int f_slot,
     ORBX_HIP_CHECK(hipMemcpyAsync(cnt.data(), ctx->out_n, sizeof(int32_t) * ctx->slots, hipMemcpyDeviceToHost,
                                   ctx->stream));
     ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    const Geometry& g = ctx->geom;
-    const size_t nf = g.nfeatures;
-    const int nF = std::min<int>(cnt[f_slot], (int)nf), nK = std::min<int>(cnt[kf_slot], (int)nf);
+    const int nF = slot_count(ctx, cnt[f_slot]), nK = slot_count(ctx, cnt[kf_slot]);
     if (kf_mps->n != nK) return ORBX_ERR_ARG;   // one map-point entry per keyframe keypoint
     if (cap < nF) return ORBX_ERR_CAPACITY;
-    Staging s{ctx};
-    const size_t o_pos = s.res((size_t)nK * 12, kf_mps->pos), o_mn = s.res((size_t)nK * 4, kf_mps->min_dist),
-                 o_qd = s.res((size_t)nK * 32, kf_mps->desc), o_sk = s.res(nK), o_as = s.res(nF, f_assigned),
-                 o_out = s.res((size_t)nF * 4), o_n = s.res(4);
-    std::vector<uint8_t> skip(nK);
-    for (int i = 0; i < nK; i++) skip[i] = !kf_valid[i];
-    if (nK) s.puts.push_back({o_sk, {skip.data(), (size_t)nK}});
-    int r = s.upload();
-    if (r != ORBX_OK) return r;
-    uint8_t* d = s.base();
-    ORBX_HIP_CHECK(hipMemsetAsync(d + o_out, 0xFF, (size_t)std::max(nF, 1) * 4, ctx->stream));
-    orbx_frame_view v{};
-    v.n = nF;
-    v.min_x = f_bounds ? f_bounds[0] : 0.f;
-    v.max_x = f_bounds ? f_bounds[1] : (float)g.w;
-    v.min_y = f_bounds ? f_bounds[2] : 0.f;
-    v.max_y = f_bounds ? f_bounds[3] : (float)g.h;
-    SeqProjArgs a{};
-    a.T = kf_dev(&v, nullptr, 0, 0);
-    a.T.kps = ctx->out_kps + (size_t)f_slot * nf;
-    a.T.desc = ctx->out_desc + (size_t)f_slot * nf * 32;
-    a.nlevels = g.nlevels;
-    a.scales[0] = 1.0f;
-    for (int l = 1; l < g.nlevels; l++) a.scales[l] = a.scales[l - 1] * g.scale_factor;
-    for (int k = 0; k < 4; k++) a.cam[k] = cam[k];
-    pose_parts(Tcw, 0, a.R, a.t, a.Ow);
-    a.th = th;
-    a.orb_dist = orb_dist;
-    a.check_ori = check_ori;
-    a.variant = 1;
-    a.nq = nK;
-    a.pos = reinterpret_cast<const float*>(d + o_pos);
-    a.dmin = reinterpret_cast<const float*>(d + o_mn);
-    a.qdesc = d + o_qd;
-    a.qskip = d + o_sk;
-    a.qkps = ctx->out_kps + (size_t)kf_slot * nf;
-    a.assigned = d + o_as;
-    a.out = reinterpret_cast<int32_t*>(d + o_out);
-    a.out_n = reinterpret_cast<int32_t*>(d + o_n);
-    const size_t lds = (size_t)std::max(nF, 1) * 21 + 32 * 4 + 64;
-    hipLaunchKernelGGL(k_proj_seq, dim3(1), dim3(64), lds, ctx->stream, a);
-    ORBX_HIP_CHECK(hipGetLastError());
-    if (nF) ORBX_HIP_CHECK(hipMemcpyAsync(matches_f, d + o_out, (size_t)nF * 4, hipMemcpyDeviceToHost, ctx->stream));
-    ORBX_HIP_CHECK(hipMemcpyAsync(n_matches, d + o_n, 4, hipMemcpyDeviceToHost, ctx->stream));
-    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return ORBX_OK;
+    ArrayStage s(ctx);
+    return run_frame_kf(s, nullptr, kf_slot_dev(ctx, f_slot, f_bounds, nF), ctx->geom.nlevels, ctx->geom.scale_factor,
+                        {}, slot_frame_dev(ctx, kf_slot, nullptr).kps, nK, cam, kf_mps, kf_valid, f_assigned, Tcw, th,
+                        orb_dist, check_ori, matches_f, n_matches);
 }
+

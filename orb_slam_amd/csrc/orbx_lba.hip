@@ -51,6 +51,7 @@
 #include "orbx_device.h"
 #include "orbx_internal.h"
 #include "orbx_se3.h"
+#include "orbx_stage.h"
 
 namespace orbx {
 
@@ -2559,7 +2560,6 @@ void host_parallel(int n, Fn fn)
     for (auto& th : pool) th.join();
 }
 
-inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
 }  // namespace
 
 // Device layout of one batch of P problems (planned on the host from the

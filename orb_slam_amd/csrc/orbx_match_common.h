@@ -20,6 +20,33 @@ struct FrameDev {
     float grid_w_inv, grid_h_inv;   // FRAME_GRID_COLS / (maxX - minX) etc.
 };
 
+inline FrameDev bounded_frame_dev(const orbx_keypoint* kps, const uint8_t* desc, int n, float min_x, float max_x,
+                                  float min_y, float max_y)
+{
+    // src/Frame.cc:76-77: FRAME_GRID_COLS / (mnMaxX - mnMinX) in float
+    return FrameDev{kps, desc, n, min_x, max_x, min_y, max_y, static_cast<float>(kGridCols) / (max_x - min_x),
+                    static_cast<float>(kGridRows) / (max_y - min_y)};
+}
+
+// A frame view whose keypoints and descriptors lie at kps / desc on the device.
+inline FrameDev frame_dev(const orbx_frame_view* v, const orbx_keypoint* kps, const uint8_t* desc)
+{
+    return bounded_frame_dev(kps, desc, v->n, v->min_x, v->max_x, v->min_y, v->max_y);
+}
+
+// The frame in an extraction slot, keypoints and descriptors where extraction
+// left them.  bounds (min_x, max_x, min_y, max_y) or, null, those of
+// orbx_dev_set_image_bounds (default the image).  n is the slot's capacity:
+// the caller sets the count it knows.
+inline FrameDev slot_frame_dev(const orbx_ctx* ctx, int slot, const float* bounds)
+{
+    const Geometry& g = ctx->geom;
+    const float image[4] = {0.f, (float)g.w, 0.f, (float)g.h};
+    const float* b = bounds ? bounds : ctx->has_bounds ? ctx->bounds : image;
+    const size_t first = (size_t)slot * g.nfeatures;
+    return bounded_frame_dev(ctx->out_kps + first, ctx->out_desc + first * 32, g.nfeatures, b[0], b[1], b[2], b[3]);
+}
+
 __device__ inline void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();

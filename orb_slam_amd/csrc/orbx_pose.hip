@@ -39,6 +39,7 @@
 #include "orbx_internal.h"
 #include "orbx_pose_dev.h"
 #include "orbx_se3.h"
+#include "orbx_stage.h"
 
 namespace orbx {
 
@@ -1281,7 +1282,6 @@ __global__ __launch_bounds__(kPxThreads) void k_pose_exact_wide(const PoseHdr* _
 }
 
 namespace {
-inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
 
 template <typename Fn>
 void pose_parallel(int n, Fn fn)

@@ -14,6 +14,7 @@
 
 #include "orbx_match_common.h"
 #include "orbx_pose_dev.h"
+#include "orbx_stage.h"
 
 namespace orbx {
 
@@ -1317,99 +1318,148 @@ __global__ __launch_bounds__(kTrackThreads) void k_track_stage(TrackDev d, int s
 // ---------------------------------------------------------------------------
 namespace {
 
-struct Uploader {
-    orbx_ctx* ctx;
-    std::vector<std::pair<size_t, size_t>> parts;   // offset, bytes
-    size_t total = 0;
-    size_t reserve(size_t bytes)
-    {
-        const size_t off = total;
-        total += (bytes + 255) & ~size_t(255);
-        return off;
-    }
-    uint8_t* base() const { return static_cast<uint8_t*>(ctx->scratch); }
+struct FrameRegions {
+    Region<orbx_keypoint> kp;
+    Region<uint8_t> desc;
 };
 
-// One call's device block staged through the context's page-locked buffer:
-// inputs (and initialised outputs) are written at their device offsets into
-// the pinned copy and go over in ONE copy, the outputs come back in ONE copy
-// from out_begin -- instead of a copy per array, each of which costs a
-// DMA setup (and, from pageable memory, a staging kernel).
-struct Pinned {
-    orbx_ctx* ctx;
-    uint8_t* h = nullptr;
-    int open(size_t total)
-    {
-        const int r = ensure_pinned(ctx, total);
-        h = static_cast<uint8_t*>(ctx->host_pinned);
-        return r;
-    }
-    void put(size_t off, const void* src, size_t bytes)
-    {
-        if (bytes && src) std::memcpy(h + off, src, bytes);
-    }
-    void fill(size_t off, int v, size_t bytes) { std::memset(h + off, v, bytes); }
-    int upload(size_t bytes)
-    {
-        ORBX_HIP_CHECK(hipMemcpyAsync(ctx->scratch, h, bytes, hipMemcpyHostToDevice, ctx->stream));
-        return ORBX_OK;
-    }
-    int download(size_t begin, size_t end)
-    {
-        ORBX_HIP_CHECK(hipMemcpyAsync(h + begin, static_cast<uint8_t*>(ctx->scratch) + begin, end - begin,
-                                      hipMemcpyDeviceToHost, ctx->stream));
-        ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        return ORBX_OK;
-    }
-    void get(void* dst, size_t off, size_t bytes) const
-    {
-        if (bytes && dst) std::memcpy(dst, h + off, bytes);
-    }
-};
-
-bool valid_view(const orbx_frame_view* v)
+FrameRegions take_frame(BlockStage& s, const orbx_frame_view* v)
 {
-    return v && v->n >= 0 && v->n <= kMaxFeatures && (v->n == 0 || (v->keys_un && v->desc)) && v->max_x > v->min_x &&
-           v->max_y > v->min_y && v->nlevels > 0 && v->nlevels <= kMaxLevels;
-}
-
-FrameDev dev_frame(const orbx_frame_view* v, const uint8_t* base, size_t kp_off, size_t desc_off)
-{
-    FrameDev F;
-    F.kps = reinterpret_cast<const orbx_keypoint*>(base + kp_off);
-    F.desc = base + desc_off;
-    F.n = v->n;
-    F.min_x = v->min_x;
-    F.max_x = v->max_x;
-    F.min_y = v->min_y;
-    F.max_y = v->max_y;
-    // src/Frame.cc:76-77: FRAME_GRID_COLS / (mnMaxX - mnMinX) in float
-    F.grid_w_inv = static_cast<float>(kGridCols) / (v->max_x - v->min_x);
-    F.grid_h_inv = static_cast<float>(kGridRows) / (v->max_y - v->min_y);
-    return F;
-}
-
-void frame_scales(const orbx_frame_view* v, float* s)
-{
-    s[0] = 1.0f;
-    for (int i = 1; i < v->nlevels; i++) s[i] = s[i - 1] * v->scale_factor;   // src/Frame.cc:98-102
-}
-
-// Uploads a frame view; returns offsets.
-struct FrameOffs { size_t kp, desc; };
-
-FrameOffs reserve_frame(Uploader& u, const orbx_frame_view* v)
-{
-    FrameOffs o;
-    o.kp = u.reserve((size_t)v->n * sizeof(orbx_keypoint));
-    o.desc = u.reserve((size_t)v->n * 32);
+    FrameRegions o;
+    o.kp = s.take<orbx_keypoint>(v->n);
+    o.desc = s.take<uint8_t>((size_t)v->n * 32);
     return o;
 }
 
-void put_frame(Pinned& pin, const FrameOffs& o, const orbx_frame_view* v)
+void put_frame(BlockStage& s, const FrameRegions& o, const orbx_frame_view* v)
 {
-    pin.put(o.kp, v->keys_un, (size_t)v->n * sizeof(orbx_keypoint));
-    pin.put(o.desc, v->desc, (size_t)v->n * 32);
+    s.put(o.kp, v->keys_un);
+    s.put(o.desc, v->desc);
+}
+
+FrameDev staged_frame(const BlockStage& s, const FrameRegions& o, const orbx_frame_view* v)
+{
+    return frame_dev(v, s.dev(o.kp), s.dev(o.desc));
+}
+
+// A search's result: the match per searched keypoint (and one spare entry),
+// all -1 at upload, and the match count.
+struct MatchRegions {
+    Region<int32_t> out, n;
+};
+
+MatchRegions take_matches(BlockStage& s, int n2)
+{
+    MatchRegions o;
+    o.out = s.take<int32_t>((size_t)n2 + 1);
+    o.n = s.take<int32_t>(1);
+    return o;
+}
+
+// One job's arrays of the frustum test and the local-map search behind it.
+struct LocalMapRegions {
+    Region<float> pos, normal, dist;         // inputs: n_mp x 3, x 3, x 2
+    Region<uint8_t> skip, desc, assigned;
+    Region<uint8_t> in_view;                 // frustum results, the search's per-point inputs
+    Region<float> proj, cos;
+    Region<int32_t> pred, count;
+    MatchRegions m;
+};
+
+// The four kinds of SearchArgs that both a stand-alone entry point and
+// orbx_track_frame build.  Each fills what the two share; the caller adds
+// what it alone knows (a pose the device fills in later, F2_cnt, nq).
+
+// SearchByProjection(CurrentFrame, LastFrame, th) (src/ORBmatcher.cc:1507):
+// F1 the last frame (its keypoints are the queries), F2 the current one
+SearchArgs motion_job(const BlockStage& s, const FrameDev& F1, const FrameDev& F2, Region<float> q_xyz,
+                      Region<uint8_t> q_valid, Region<uint8_t> f2_assigned, const float* Tcw, const float* cam,
+                      int nlevels, float scale_factor, float th, int check_ori, const MatchRegions& m)
+{
+    SearchArgs a{};
+    a.F1 = F1;
+    a.F2 = F2;
+    a.q_xyz = s.dev(q_xyz);
+    a.q_valid = s.dev(q_valid);
+    a.f2_assigned = s.dev(f2_assigned);
+    for (int i = 0; i < 12; i++) a.T[i] = Tcw[i];
+    for (int i = 0; i < 4; i++) a.cam[i] = cam[i];
+    level_scales(nlevels, scale_factor, a.scale);
+    a.th = th;
+    a.check_ori = check_ori;
+    a.out = s.dev(m.out);
+    a.out_n = s.dev(m.n);
+    return a;
+}
+
+// SearchByProjection(F1, F2, Tcw2, window); the caller sets T and window
+SearchArgs pair_job(const BlockStage& s, const FrameDev& F1, const FrameDev& F2, Region<float> q_xyz,
+                    Region<uint8_t> q_valid, Region<uint8_t> f2_assigned, const float* cam, float nnratio,
+                    const MatchRegions& m)
+{
+    SearchArgs a{};
+    a.F1 = F1;
+    a.F2 = F2;
+    a.q_xyz = s.dev(q_xyz);
+    a.q_valid = s.dev(q_valid);
+    a.f2_assigned = s.dev(f2_assigned);
+    for (int i = 0; i < 4; i++) a.cam[i] = cam[i];
+    a.nnratio = nnratio;
+    a.out = s.dev(m.out);
+    a.out_n = s.dev(m.n);
+    return a;
+}
+
+// WindowSearch(F1, F2, window, vpMapPointMatches21, minScaleLevel, maxScaleLevel)
+SearchArgs window_job(const BlockStage& s, const FrameDev& F1, const FrameDev& F2, Region<uint8_t> q_valid,
+                      int window, int min_level, int max_level, float nnratio, int check_ori, const MatchRegions& m)
+{
+    SearchArgs a{};
+    a.F1 = F1;
+    a.F2 = F2;
+    a.q_valid = s.dev(q_valid);
+    a.window = window;
+    a.min_level = min_level;
+    a.max_level = max_level < 0 ? 0x7fffffff : max_level;
+    a.nnratio = nnratio;
+    a.check_ori = check_ori;
+    a.out = s.dev(m.out);
+    a.out_n = s.dev(m.n);
+    return a;
+}
+
+// SearchReferencePointsInFrustum (src/Tracking.cc:701-752): k_frustum writes
+// the fr_ arrays, the search reads them as its per-point inputs.  The caller
+// sets nq and the pose (Rcw, tcw, Ow).
+SearchArgs local_map_job(const BlockStage& s, const FrameDev& F, const LocalMapRegions& o, const float* cam,
+                         int nlevels, float scale_factor, float view_cos_limit, float th, float nnratio)
+{
+    SearchArgs a{};
+    a.F2 = F;
+    a.q_xyz = s.dev(o.pos);
+    a.mp_normal = s.dev(o.normal);
+    a.mp_dist = s.dev(o.dist);
+    a.mp_skip = s.dev(o.skip);
+    a.q_desc = s.dev(o.desc);
+    a.f2_assigned = s.dev(o.assigned);
+    for (int i = 0; i < 4; i++) a.cam[i] = cam[i];
+    level_scales(nlevels, scale_factor, a.scale);
+    a.nlevels = nlevels;
+    a.view_cos_limit = view_cos_limit;
+    a.th = th;
+    a.nnratio = nnratio;
+    a.fr_in_view = s.dev(o.in_view);
+    a.fr_proj = s.dev(o.proj);
+    a.fr_pred = s.dev(o.pred);
+    a.fr_cos = s.dev(o.cos);
+    a.fr_count = s.dev(o.count);
+    a.q_valid = a.fr_in_view;
+    a.proj_xy = a.fr_proj;
+    a.pred_level = a.fr_pred;
+    a.view_cos = a.fr_cos;
+    a.out = s.dev(o.m.out);
+    a.out_n = s.dev(o.m.n);
+    return a;
 }
 
 size_t tab_lds(int n) { return (size_t)n * 16 + ((n + 15) & ~15) + (size_t)n * 4 + 32 * 4 + 64; }
@@ -1417,25 +1467,28 @@ size_t tab_lds(int n) { return (size_t)n * 16 + ((n + 15) & ~15) + (size_t)n * 4
 // Device space of the two-phase searches' candidate lists: B jobs of up to
 // nq queries (reserved after the read-back range; never copied).
 struct AreaBufs {
-    size_t lists, cnt, qglob;
+    Region<uint32_t> lists;
+    Region<int32_t> cnt;
+    Region<int> qglob;
 };
-AreaBufs reserve_area(Uploader& u, int B, int nq)
+AreaBufs take_area(BlockStage& s, int B, int nq)
 {
+    const size_t q = (size_t)B * std::max(nq, 1);
     AreaBufs o;
-    o.lists = u.reserve((size_t)B * std::max(nq, 1) * kAreaCap * 4);
-    o.cnt = u.reserve((size_t)B * std::max(nq, 1) * 4);
-    o.qglob = u.reserve((size_t)B * std::max(nq, 1) * kAreaQueryInts * 4);
+    o.lists = s.take<uint32_t>(q * kAreaCap);
+    o.cnt = s.take<int32_t>(q);
+    o.qglob = s.take<int>(q * kAreaQueryInts);
     return o;
 }
 
 // The two launches of a search of kind K over B jobs whose SearchArgs are
 // in device memory at dj (nq_max queries, n2_max searched keypoints at most).
 template <int K>
-int launch_area_search(orbx_ctx* ctx, const SearchArgs* dj, int B, int nq_max, int n2_max, const Uploader& u,
-                       const AreaBufs& o)
+int launch_area_search(const BlockStage& s, const SearchArgs* dj, int B, int nq_max, int n2_max, const AreaBufs& o)
 {
-    uint32_t* lists = reinterpret_cast<uint32_t*>(u.base() + o.lists);
-    int32_t* cnt = reinterpret_cast<int32_t*>(u.base() + o.cnt);
+    orbx_ctx* ctx = s.ctx;
+    uint32_t* lists = s.dev(o.lists);
+    int32_t* cnt = s.dev(o.cnt);
     const int cap_q = std::max(nq_max, 1);
     n2_max = std::max(n2_max, 1);
     // the replay's per-query arrays in LDS when they fit beside the table
@@ -1450,8 +1503,31 @@ int launch_area_search(orbx_ctx* ctx, const SearchArgs* dj, int B, int nq_max, i
         hipLaunchKernelGGL(k_area_lists<K>, dim3((nq_max + kAreaListWaves - 1) / kAreaListWaves, B),
                            dim3(kAreaListWaves * 64), area_lists_lds(n2_max), ctx->stream, dj, cap_q, lists, cnt);
     hipLaunchKernelGGL(k_area_replay<K>, dim3(B), dim3(kReplayThreads), area_replay_lds(n2_max, q_lds ? cap_q : 0, ent_cap),
-                       ctx->stream, dj, cap_q, lists, cnt, q_lds, ent_cap, reinterpret_cast<int*>(u.base() + o.qglob));
+                       ctx->stream, dj, cap_q, lists, cnt, q_lds, ent_cap, s.dev(o.qglob));
     ORBX_HIP_CHECK(hipGetLastError());
+    return ORBX_OK;
+}
+
+// Puts one job struct into the block; its device address.
+const SearchArgs* put_job(BlockStage& s, Region<SearchArgs> r, const SearchArgs& a)
+{
+    s.put(r, &a, 1);
+    return s.dev(r);
+}
+
+// The stand-alone searches' common tail: job and block up, the two launches,
+// the read-back range down, the matches of n2 keypoints and their count out.
+template <int K>
+int run_area_search(BlockStage& s, Region<SearchArgs> job, const SearchArgs& a, int nq, int n2, const AreaBufs& area,
+                    const MatchRegions& m, int32_t* matches, int* n_matches)
+{
+    const SearchArgs* da = put_job(s, job, a);
+    int r = s.upload(m.n.end());
+    if (r == ORBX_OK) r = launch_area_search<K>(s, da, 1, nq, n2, area);
+    if (r == ORBX_OK) r = s.download(m.out.off, m.n.end());
+    if (r != ORBX_OK) return r;
+    s.get(matches, m.out, n2);
+    s.get(n_matches, m.n);
     return ORBX_OK;
 }
 
@@ -1475,14 +1551,15 @@ int orbx_search_for_initialization(orbx_ctx* ctx, const orbx_frame_view* F1, con
                                    float* prev_matched, int32_t* matches12, int window, float nnratio,
                                    int check_ori, int* n_matches)
 {
-    if (!ctx || !valid_view(F1) || !valid_view(F2) || !prev_matched || !matches12 || !n_matches || window < 0)
+    if (!ctx || !valid_frame_view(F1) || !valid_frame_view(F2) || !prev_matched || !matches12 || !n_matches ||
+        window < 0)
         return ORBX_ERR_ARG;
     ctx_enter(ctx);
     // inputs, then the outputs (prev_out starts as a copy of prev_matched)
-    Uploader u{ctx};
-    const FrameOffs o1 = reserve_frame(u, F1), o2 = reserve_frame(u, F2);
-    const size_t op = u.reserve((size_t)F1->n * 8);
-    const size_t opo = u.reserve((size_t)F1->n * 8), oo = u.reserve((size_t)F1->n * 4 + 4), on = u.reserve(4);
+    BlockStage s(ctx);
+    const FrameRegions o1 = take_frame(s, F1), o2 = take_frame(s, F2);
+    const Region<float> op = s.take<float>((size_t)F1->n * 2), opo = s.take<float>((size_t)F1->n * 2);
+    const MatchRegions m = take_matches(s, F1->n);
     // candidate slots = F2 keypoints of octave 0; queries = F1's up to its
     // last octave-0 keypoint
     int cap_c = 0, n1q = 0;
@@ -1492,44 +1569,40 @@ int orbx_search_for_initialization(orbx_ctx* ctx, const orbx_frame_view* F1, con
     cap_c = std::max(cap_c, 1);
     if (cap_c > kInitMaxCand) return ORBX_ERR_UNSUPPORTED;
     // k_sfi_lists' output (device only, after the read-back range)
-    const size_t out_end = on + 4;
-    const size_t okeys = u.reserve((size_t)std::max(n1q, 1) * cap_c * 4), ocnt = u.reserve((size_t)std::max(n1q, 1) * 4);
+    const Region<uint32_t> okeys = s.take<uint32_t>((size_t)std::max(n1q, 1) * cap_c);
+    const Region<int32_t> ocnt = s.take<int32_t>(std::max(n1q, 1));
     const int cap1 = std::max(F1->n, 1);
     const size_t fixed = init_lds_bytes(cap_c, cap1, 0);
     const int cap_keys = std::max<int>(cap_c, (int)((kInitLdsBudget - std::min(fixed, kInitLdsBudget)) / 4));
     const size_t lds = init_lds_bytes(cap_c, cap1, cap_keys);
     if (lds > 160 * 1024) return ORBX_ERR_UNSUPPORTED;
-    int r = ensure_scratch(ctx, u.total);
-    Pinned pin{ctx};
-    if (r == ORBX_OK) r = pin.open(out_end);
+    int r = s.open(m.n.end());
     if (r != ORBX_OK) return r;
-    put_frame(pin, o1, F1);
-    put_frame(pin, o2, F2);
-    pin.put(op, prev_matched, (size_t)F1->n * 8);
-    pin.put(opo, prev_matched, (size_t)F1->n * 8);
-    if ((r = pin.upload(oo)) != ORBX_OK) return r;
+    put_frame(s, o1, F1);
+    put_frame(s, o2, F2);
+    s.put(op, prev_matched);
+    s.put(opo, prev_matched);
+    if ((r = s.upload(m.out.off)) != ORBX_OK) return r;
     SearchArgs a{};
-    a.F1 = dev_frame(F1, u.base(), o1.kp, o1.desc);
-    a.F2 = dev_frame(F2, u.base(), o2.kp, o2.desc);
-    a.prev_xy = reinterpret_cast<const float*>(u.base() + op);
-    a.prev_out = reinterpret_cast<float*>(u.base() + opo);
+    a.F1 = staged_frame(s, o1, F1);
+    a.F2 = staged_frame(s, o2, F2);
+    a.prev_xy = s.dev(op);
+    a.prev_out = s.dev(opo);
     a.window = window;
     a.nnratio = nnratio;
     a.check_ori = check_ori;
-    a.out = reinterpret_cast<int32_t*>(u.base() + oo);
-    a.out_n = reinterpret_cast<int32_t*>(u.base() + on);
-    uint32_t* dkeys = reinterpret_cast<uint32_t*>(u.base() + okeys);
-    int32_t* dcnt = reinterpret_cast<int32_t*>(u.base() + ocnt);
+    a.out = s.dev(m.out);
+    a.out_n = s.dev(m.n);
     if (n1q > 0)
         hipLaunchKernelGGL(k_sfi_lists, dim3((n1q + kListWaves - 1) / kListWaves), dim3(kListWaves * 64),
-                           sfi_lists_lds(cap_c), ctx->stream, a, cap_c, n1q, dkeys, dcnt);
+                           sfi_lists_lds(cap_c), ctx->stream, a, cap_c, n1q, s.dev(okeys), s.dev(ocnt));
     hipLaunchKernelGGL(k_search_init_one, dim3(1), dim3(kInitOneThreads), lds, ctx->stream, a, cap_c, cap_keys,
-                       ctx->error_flags, dkeys, dcnt);
+                       ctx->error_flags, s.dev(okeys), s.dev(ocnt));
     ORBX_HIP_CHECK(hipGetLastError());
-    if ((r = pin.download(opo, out_end)) != ORBX_OK) return r;
-    pin.get(matches12, oo, (size_t)F1->n * 4);
-    pin.get(n_matches, on, 4);
-    pin.get(prev_matched, opo, (size_t)F1->n * 8);
+    if ((r = s.download(opo.off, m.n.end())) != ORBX_OK) return r;
+    s.get(matches12, m.out, F1->n);
+    s.get(n_matches, m.n);
+    s.get(prev_matched, opo);
     return *n_matches < 0 ? *n_matches : ORBX_OK;
 }
 
@@ -1537,41 +1610,24 @@ int orbx_window_search(orbx_ctx* ctx, const orbx_frame_view* F1, const orbx_fram
                        int window, int min_level, int max_level, float nnratio, int check_ori, int32_t* matches21,
                        int* n_matches)
 {
-    if (!ctx || !valid_view(F1) || !valid_view(F2) || !f1_mp || !matches21 || !n_matches || window < 0)
+    if (!ctx || !valid_frame_view(F1) || !valid_frame_view(F2) || !f1_mp || !matches21 || !n_matches || window < 0)
         return ORBX_ERR_ARG;
     ctx_enter(ctx);
-    Uploader u{ctx};
-    const FrameOffs o1 = reserve_frame(u, F1), o2 = reserve_frame(u, F2);
-    const size_t ov = u.reserve(F1->n), oarg = u.reserve(sizeof(SearchArgs));
-    const size_t oo = u.reserve((size_t)F2->n * 4 + 4), on = u.reserve(4), io_end = on + 4;
-    const AreaBufs ol = reserve_area(u, 1, F1->n);
-    int r = ensure_scratch(ctx, u.total);
-    Pinned pin{ctx};
-    if (r == ORBX_OK) r = pin.open(io_end);
+    BlockStage s(ctx);
+    const FrameRegions o1 = take_frame(s, F1), o2 = take_frame(s, F2);
+    const Region<uint8_t> ov = s.take<uint8_t>(F1->n);
+    const Region<SearchArgs> job = s.take<SearchArgs>(1);
+    const MatchRegions m = take_matches(s, F2->n);
+    const AreaBufs area = take_area(s, 1, F1->n);
+    const int r = s.open(m.n.end());
     if (r != ORBX_OK) return r;
-    put_frame(pin, o1, F1);
-    put_frame(pin, o2, F2);
-    pin.put(ov, f1_mp, F1->n);
-    pin.fill(oo, 0xFF, (size_t)F2->n * 4 + 4);
-    SearchArgs a{};
-    a.F1 = dev_frame(F1, u.base(), o1.kp, o1.desc);
-    a.F2 = dev_frame(F2, u.base(), o2.kp, o2.desc);
-    a.q_valid = u.base() + ov;
-    a.window = window;
-    a.min_level = min_level;
-    a.max_level = max_level < 0 ? 0x7fffffff : max_level;
-    a.nnratio = nnratio;
-    a.check_ori = check_ori;
-    a.out = reinterpret_cast<int32_t*>(u.base() + oo);
-    a.out_n = reinterpret_cast<int32_t*>(u.base() + on);
-    pin.put(oarg, &a, sizeof(a));
-    if ((r = pin.upload(io_end)) != ORBX_OK) return r;
-    const SearchArgs* da = reinterpret_cast<const SearchArgs*>(u.base() + oarg);
-    if ((r = launch_area_search<kQWindow>(ctx, da, 1, F1->n, F2->n, u, ol)) != ORBX_OK) return r;
-    if ((r = pin.download(oo, io_end)) != ORBX_OK) return r;
-    pin.get(matches21, oo, (size_t)F2->n * 4);
-    pin.get(n_matches, on, 4);
-    return ORBX_OK;
+    put_frame(s, o1, F1);
+    put_frame(s, o2, F2);
+    s.put(ov, f1_mp);
+    s.fill(m.out, 0xFF);
+    const SearchArgs a = window_job(s, staged_frame(s, o1, F1), staged_frame(s, o2, F2), ov, window, min_level,
+                                    max_level, nnratio, check_ori, m);
+    return run_area_search<kQWindow>(s, job, a, F1->n, F2->n, area, m, matches21, n_matches);
 }
 
 int orbx_search_by_projection_pair(orbx_ctx* ctx, const orbx_frame_view* F1, const orbx_frame_view* F2,
@@ -1579,46 +1635,29 @@ int orbx_search_by_projection_pair(orbx_ctx* ctx, const orbx_frame_view* F1, con
                                    const float* Tcw2, const float* cam, int window, float nnratio, int32_t* matches21,
                                    int* n_matches)
 {
-    if (!ctx || !valid_view(F1) || !valid_view(F2) || !f1_mp_xyz || !f1_mp_valid || !f2_assigned || !Tcw2 || !cam ||
-        !matches21 || !n_matches || window < 0)
+    if (!ctx || !valid_frame_view(F1) || !valid_frame_view(F2) || !f1_mp_xyz || !f1_mp_valid || !f2_assigned ||
+        !Tcw2 || !cam || !matches21 || !n_matches || window < 0)
         return ORBX_ERR_ARG;
     ctx_enter(ctx);
-    Uploader u{ctx};
-    const FrameOffs o1 = reserve_frame(u, F1), o2 = reserve_frame(u, F2);
-    const size_t ox = u.reserve((size_t)F1->n * 12), ov = u.reserve(F1->n), oa = u.reserve(F2->n);
-    const size_t oarg = u.reserve(sizeof(SearchArgs));
-    const size_t oo = u.reserve((size_t)F2->n * 4 + 4), on = u.reserve(4), io_end = on + 4;
-    const AreaBufs ol = reserve_area(u, 1, F1->n);
-    int r = ensure_scratch(ctx, u.total);
-    Pinned pin{ctx};
-    if (r == ORBX_OK) r = pin.open(io_end);
+    BlockStage s(ctx);
+    const FrameRegions o1 = take_frame(s, F1), o2 = take_frame(s, F2);
+    const Region<float> ox = s.take<float>((size_t)F1->n * 3);
+    const Region<uint8_t> ov = s.take<uint8_t>(F1->n), oa = s.take<uint8_t>(F2->n);
+    const Region<SearchArgs> job = s.take<SearchArgs>(1);
+    const MatchRegions m = take_matches(s, F2->n);
+    const AreaBufs area = take_area(s, 1, F1->n);
+    const int r = s.open(m.n.end());
     if (r != ORBX_OK) return r;
-    put_frame(pin, o1, F1);
-    put_frame(pin, o2, F2);
-    pin.put(ox, f1_mp_xyz, (size_t)F1->n * 12);
-    pin.put(ov, f1_mp_valid, F1->n);
-    pin.put(oa, f2_assigned, F2->n);
-    pin.fill(oo, 0xFF, (size_t)F2->n * 4 + 4);
-    SearchArgs a{};
-    a.F1 = dev_frame(F1, u.base(), o1.kp, o1.desc);
-    a.F2 = dev_frame(F2, u.base(), o2.kp, o2.desc);
-    a.q_xyz = reinterpret_cast<const float*>(u.base() + ox);
-    a.q_valid = u.base() + ov;
-    a.f2_assigned = u.base() + oa;
+    put_frame(s, o1, F1);
+    put_frame(s, o2, F2);
+    s.put(ox, f1_mp_xyz);
+    s.put(ov, f1_mp_valid);
+    s.put(oa, f2_assigned);
+    s.fill(m.out, 0xFF);
+    SearchArgs a = pair_job(s, staged_frame(s, o1, F1), staged_frame(s, o2, F2), ox, ov, oa, cam, nnratio, m);
     for (int i = 0; i < 12; i++) a.T[i] = Tcw2[i];
-    for (int i = 0; i < 4; i++) a.cam[i] = cam[i];
     a.window = window;
-    a.nnratio = nnratio;
-    a.out = reinterpret_cast<int32_t*>(u.base() + oo);
-    a.out_n = reinterpret_cast<int32_t*>(u.base() + on);
-    pin.put(oarg, &a, sizeof(a));
-    if ((r = pin.upload(io_end)) != ORBX_OK) return r;
-    const SearchArgs* da = reinterpret_cast<const SearchArgs*>(u.base() + oarg);
-    if ((r = launch_area_search<kQPair>(ctx, da, 1, F1->n, F2->n, u, ol)) != ORBX_OK) return r;
-    if ((r = pin.download(oo, io_end)) != ORBX_OK) return r;
-    pin.get(matches21, oo, (size_t)F2->n * 4);
-    pin.get(n_matches, on, 4);
-    return ORBX_OK;
+    return run_area_search<kQPair>(s, job, a, F1->n, F2->n, area, m, matches21, n_matches);
 }
 
 int orbx_search_by_projection_motion(orbx_ctx* ctx, const orbx_frame_view* Cur, const orbx_frame_view* Last,
@@ -1626,101 +1665,79 @@ int orbx_search_by_projection_motion(orbx_ctx* ctx, const orbx_frame_view* Cur, 
                                      const uint8_t* cur_assigned, const float* Tcw, const float* cam, float th,
                                      int check_ori, int32_t* matches_cur, int* n_matches)
 {
-    if (!ctx || !valid_view(Cur) || !valid_view(Last) || !last_mp_xyz || !last_mp_valid || !cur_assigned || !Tcw ||
-        !cam || !matches_cur || !n_matches)
+    if (!ctx || !valid_frame_view(Cur) || !valid_frame_view(Last) || !last_mp_xyz || !last_mp_valid || !cur_assigned ||
+        !Tcw || !cam || !matches_cur || !n_matches)
         return ORBX_ERR_ARG;
     ctx_enter(ctx);
-    Uploader u{ctx};
-    const FrameOffs oL = reserve_frame(u, Last), oC = reserve_frame(u, Cur);
-    const size_t ox = u.reserve((size_t)Last->n * 12), ov = u.reserve(Last->n), oa = u.reserve(Cur->n);
-    const size_t oarg = u.reserve(sizeof(SearchArgs));
-    const size_t oo = u.reserve((size_t)Cur->n * 4 + 4), on = u.reserve(4), io_end = on + 4;
-    const AreaBufs ol = reserve_area(u, 1, Last->n);
-    int r = ensure_scratch(ctx, u.total);
-    Pinned pin{ctx};
-    if (r == ORBX_OK) r = pin.open(io_end);
+    BlockStage s(ctx);
+    const FrameRegions oL = take_frame(s, Last), oC = take_frame(s, Cur);
+    const Region<float> ox = s.take<float>((size_t)Last->n * 3);
+    const Region<uint8_t> ov = s.take<uint8_t>(Last->n), oa = s.take<uint8_t>(Cur->n);
+    const Region<SearchArgs> job = s.take<SearchArgs>(1);
+    const MatchRegions m = take_matches(s, Cur->n);
+    const AreaBufs area = take_area(s, 1, Last->n);
+    const int r = s.open(m.n.end());
     if (r != ORBX_OK) return r;
-    put_frame(pin, oL, Last);
-    put_frame(pin, oC, Cur);
-    pin.put(ox, last_mp_xyz, (size_t)Last->n * 12);
-    pin.put(ov, last_mp_valid, Last->n);
-    pin.put(oa, cur_assigned, Cur->n);
-    pin.fill(oo, 0xFF, (size_t)Cur->n * 4 + 4);
-    SearchArgs a{};
-    a.F1 = dev_frame(Last, u.base(), oL.kp, oL.desc);
-    a.F2 = dev_frame(Cur, u.base(), oC.kp, oC.desc);
-    a.q_xyz = reinterpret_cast<const float*>(u.base() + ox);
-    a.q_valid = u.base() + ov;
-    a.f2_assigned = u.base() + oa;
-    for (int i = 0; i < 12; i++) a.T[i] = Tcw[i];
-    for (int i = 0; i < 4; i++) a.cam[i] = cam[i];
-    frame_scales(Cur, a.scale);
-    a.th = th;
-    a.check_ori = check_ori;
-    a.out = reinterpret_cast<int32_t*>(u.base() + oo);
-    a.out_n = reinterpret_cast<int32_t*>(u.base() + on);
-    pin.put(oarg, &a, sizeof(a));
-    if ((r = pin.upload(io_end)) != ORBX_OK) return r;
-    const SearchArgs* da = reinterpret_cast<const SearchArgs*>(u.base() + oarg);
-    if ((r = launch_area_search<kQMotion>(ctx, da, 1, Last->n, Cur->n, u, ol)) != ORBX_OK) return r;
-    if ((r = pin.download(oo, io_end)) != ORBX_OK) return r;
-    pin.get(matches_cur, oo, (size_t)Cur->n * 4);
-    pin.get(n_matches, on, 4);
-    return ORBX_OK;
+    put_frame(s, oL, Last);
+    put_frame(s, oC, Cur);
+    s.put(ox, last_mp_xyz);
+    s.put(ov, last_mp_valid);
+    s.put(oa, cur_assigned);
+    s.fill(m.out, 0xFF);
+    const SearchArgs a = motion_job(s, staged_frame(s, oL, Last), staged_frame(s, oC, Cur), ox, ov, oa, Tcw, cam,
+                                    Cur->nlevels, Cur->scale_factor, th, check_ori, m);
+    return run_area_search<kQMotion>(s, job, a, Last->n, Cur->n, area, m, matches_cur, n_matches);
 }
 
+// The local search over frustum results the caller computed: the one job
+// kind built in a single place, so it has no builder.
 int orbx_search_by_projection_local(orbx_ctx* ctx, const orbx_frame_view* F, int n_mp, const uint8_t* in_view,
                                     const float* proj_xy, const int32_t* pred_level, const float* view_cos,
                                     const uint8_t* mp_desc, const uint8_t* f_assigned, float th, float nnratio,
                                     int32_t* matches_f, int* n_matches)
 {
-    if (!ctx || !valid_view(F) || n_mp < 0 || (n_mp > 0 && (!in_view || !proj_xy || !pred_level || !view_cos || !mp_desc)) ||
-        !f_assigned || !matches_f || !n_matches)
+    if (!ctx || !valid_frame_view(F) || n_mp < 0 ||
+        (n_mp > 0 && (!in_view || !proj_xy || !pred_level || !view_cos || !mp_desc)) || !f_assigned || !matches_f ||
+        !n_matches)
         return ORBX_ERR_ARG;
     for (int m = 0; m < n_mp; m++)
         if (in_view[m] && (pred_level[m] < 0 || pred_level[m] >= F->nlevels)) return ORBX_ERR_ARG;
     ctx_enter(ctx);
-    Uploader u{ctx};
-    const FrameOffs oF = reserve_frame(u, F);
-    const size_t ov = u.reserve(n_mp), op = u.reserve((size_t)n_mp * 8), ol = u.reserve((size_t)n_mp * 4);
-    const size_t oc = u.reserve((size_t)n_mp * 4), od = u.reserve((size_t)n_mp * 32), oa = u.reserve(F->n);
-    const size_t oarg = u.reserve(sizeof(SearchArgs));
-    const size_t oo = u.reserve((size_t)F->n * 4 + 4), on = u.reserve(4), io_end = on + 4;
-    const AreaBufs oli = reserve_area(u, 1, n_mp);
-    int r = ensure_scratch(ctx, u.total);
-    Pinned pin{ctx};
-    if (r == ORBX_OK) r = pin.open(io_end);
+    BlockStage s(ctx);
+    const FrameRegions oF = take_frame(s, F);
+    const Region<uint8_t> ov = s.take<uint8_t>(n_mp);
+    const Region<float> op = s.take<float>((size_t)n_mp * 2);
+    const Region<int32_t> ol = s.take<int32_t>(n_mp);
+    const Region<float> oc = s.take<float>(n_mp);
+    const Region<uint8_t> od = s.take<uint8_t>((size_t)n_mp * 32), oa = s.take<uint8_t>(F->n);
+    const Region<SearchArgs> job = s.take<SearchArgs>(1);
+    const MatchRegions m = take_matches(s, F->n);
+    const AreaBufs area = take_area(s, 1, n_mp);
+    const int r = s.open(m.n.end());
     if (r != ORBX_OK) return r;
-    put_frame(pin, oF, F);
-    pin.put(ov, in_view, n_mp);
-    pin.put(op, proj_xy, (size_t)n_mp * 8);
-    pin.put(ol, pred_level, (size_t)n_mp * 4);
-    pin.put(oc, view_cos, (size_t)n_mp * 4);
-    pin.put(od, mp_desc, (size_t)n_mp * 32);
-    pin.put(oa, f_assigned, F->n);
-    pin.fill(oo, 0xFF, (size_t)F->n * 4 + 4);
+    put_frame(s, oF, F);
+    s.put(ov, in_view);
+    s.put(op, proj_xy);
+    s.put(ol, pred_level);
+    s.put(oc, view_cos);
+    s.put(od, mp_desc);
+    s.put(oa, f_assigned);
+    s.fill(m.out, 0xFF);
     SearchArgs a{};
-    a.F2 = dev_frame(F, u.base(), oF.kp, oF.desc);
+    a.F2 = staged_frame(s, oF, F);
     a.nq = n_mp;
-    a.q_valid = u.base() + ov;
-    a.proj_xy = reinterpret_cast<const float*>(u.base() + op);
-    a.pred_level = reinterpret_cast<const int32_t*>(u.base() + ol);
-    a.view_cos = reinterpret_cast<const float*>(u.base() + oc);
-    a.q_desc = u.base() + od;
-    a.f2_assigned = u.base() + oa;
-    frame_scales(F, a.scale);
+    a.q_valid = s.dev(ov);
+    a.proj_xy = s.dev(op);
+    a.pred_level = s.dev(ol);
+    a.view_cos = s.dev(oc);
+    a.q_desc = s.dev(od);
+    a.f2_assigned = s.dev(oa);
+    level_scales(F->nlevels, F->scale_factor, a.scale);
     a.th = th;
     a.nnratio = nnratio;
-    a.out = reinterpret_cast<int32_t*>(u.base() + oo);
-    a.out_n = reinterpret_cast<int32_t*>(u.base() + on);
-    pin.put(oarg, &a, sizeof(a));
-    if ((r = pin.upload(io_end)) != ORBX_OK) return r;
-    const SearchArgs* da = reinterpret_cast<const SearchArgs*>(u.base() + oarg);
-    if ((r = launch_area_search<kQLocal>(ctx, da, 1, n_mp, F->n, u, oli)) != ORBX_OK) return r;
-    if ((r = pin.download(oo, io_end)) != ORBX_OK) return r;
-    pin.get(matches_f, oo, (size_t)F->n * 4);
-    pin.get(n_matches, on, 4);
-    return ORBX_OK;
+    a.out = s.dev(m.out);
+    a.out_n = s.dev(m.n);
+    return run_area_search<kQLocal>(s, job, a, n_mp, F->n, area, m, matches_f, n_matches);
 }
 
 // Tracking::SearchReferencePointsInFrustum for B frames: one packed upload
@@ -1733,136 +1750,102 @@ static int search_local_map_impl(orbx_ctx* ctx, int B, orbx_local_map_query* qs)
     for (int b = 0; b < B; b++) {
         const orbx_local_map_query& q = qs[b];
         const orbx_frame_view* F = q.frame;
-        if (!valid_view(F) || q.n_mp < 0 || !q.Rcw || !q.tcw || !q.Ow || !q.cam || !q.f_assigned || !q.matches_f ||
-            (q.n_mp > 0 && (!q.mp_pos || !q.mp_normal || !q.mp_dist || !q.mp_desc)))
+        if (!valid_frame_view(F) || q.n_mp < 0 || !q.Rcw || !q.tcw || !q.Ow || !q.cam || !q.f_assigned ||
+            !q.matches_f || (q.n_mp > 0 && (!q.mp_pos || !q.mp_normal || !q.mp_dist || !q.mp_desc)))
             return ORBX_ERR_ARG;
         max_n = std::max(max_n, F->n);
         max_mp = std::max(max_mp, q.n_mp);
     }
     ctx_enter(ctx);
     // layout: [inputs of every job | SearchArgs[B] | outputs of every job]
-    struct Offs {
-        FrameOffs f;
-        size_t assigned, pos, normal, dist, skip, desc;        // inputs
-        size_t in_view, proj, pred, cos, out, out_n, count;    // outputs
+    struct Job {
+        FrameRegions f;
+        LocalMapRegions r;
     };
-    std::vector<Offs> o(B);
-    Uploader u{ctx};
+    std::vector<Job> o(B);
+    BlockStage s(ctx);
     for (int b = 0; b < B; b++) {
         const orbx_local_map_query& q = qs[b];
         const size_t n = q.frame->n, m = q.n_mp;
-        o[b].f = reserve_frame(u, q.frame);
-        o[b].assigned = u.reserve(n);
-        o[b].pos = u.reserve(m * 12);
-        o[b].normal = u.reserve(m * 12);
-        o[b].dist = u.reserve(m * 8);
-        o[b].skip = u.reserve(m);
-        o[b].desc = u.reserve(m * 32);
+        LocalMapRegions& r = o[b].r;
+        o[b].f = take_frame(s, q.frame);
+        r.assigned = s.take<uint8_t>(n);
+        r.pos = s.take<float>(m * 3);
+        r.normal = s.take<float>(m * 3);
+        r.dist = s.take<float>(m * 2);
+        r.skip = s.take<uint8_t>(m);
+        r.desc = s.take<uint8_t>(m * 32);
     }
-    const size_t o_jobs = u.reserve((size_t)B * sizeof(SearchArgs));
-    const size_t o_outputs = u.total;
-    size_t o_end = 0;
+    const Region<SearchArgs> jobs = s.take<SearchArgs>(B);
+    const size_t o_outputs = s.total;
     for (int b = 0; b < B; b++) {
         const orbx_local_map_query& q = qs[b];
         const size_t n = q.frame->n, m = q.n_mp;
-        o[b].out = u.reserve(n * 4);
-        o[b].out_n = u.reserve(4);
-        o[b].count = u.reserve(4);
-        o[b].in_view = u.reserve(m);
-        o[b].proj = u.reserve(m * 8);
-        o[b].pred = u.reserve(m * 4);
-        o[b].cos = u.reserve(m * 4);
+        LocalMapRegions& r = o[b].r;
+        r.m.out = s.take<int32_t>(n);
+        r.m.n = s.take<int32_t>(1);
+        r.count = s.take<int32_t>(1);
+        r.in_view = s.take<uint8_t>(m);
+        r.proj = s.take<float>(m * 2);
+        r.pred = s.take<int32_t>(m);
+        r.cos = s.take<float>(m);
     }
-    o_end = u.total;
+    const size_t o_end = s.total;
     // one frame (Tracking's per-frame call): the two-phase search; batches of
     // frames keep one wave per frame (k_proj_local_jobs)
-    const AreaBufs oa = reserve_area(u, 1, B == 1 ? max_mp : 0);
-    int r = ensure_scratch(ctx, u.total);
-    if (r == ORBX_OK) r = ensure_pinned(ctx, o_end);
+    const AreaBufs area = take_area(s, 1, B == 1 ? max_mp : 0);
+    int r = s.open(o_end);
     if (r != ORBX_OK) return r;
-    uint8_t* h = static_cast<uint8_t*>(ctx->host_pinned);
-    uint8_t* d = u.base();
-    auto cp = [&](size_t off, const void* src, size_t bytes) {
-        if (bytes && src) std::memcpy(h + off, src, bytes);
-    };
-    std::vector<SearchArgs> jobs(B);
     for (int b = 0; b < B; b++) {
         const orbx_local_map_query& q = qs[b];
         const orbx_frame_view* F = q.frame;
-        const size_t n = F->n, m = q.n_mp;
-        cp(o[b].f.kp, F->keys_un, n * sizeof(orbx_keypoint));
-        cp(o[b].f.desc, F->desc, n * 32);
-        cp(o[b].assigned, q.f_assigned, n);
-        cp(o[b].pos, q.mp_pos, m * 12);
-        cp(o[b].normal, q.mp_normal, m * 12);
-        cp(o[b].dist, q.mp_dist, m * 8);
-        if (q.mp_skip) cp(o[b].skip, q.mp_skip, m);
-        else if (m) std::memset(h + o[b].skip, 0, m);
-        cp(o[b].desc, q.mp_desc, m * 32);
-        std::memset(h + o[b].out, 0xFF, n * 4);   // matches_f: -1 unless assigned here
-        std::memset(h + o[b].out_n, 0, 8);        // out_n, count
-        SearchArgs& a = jobs[b];
-        a = SearchArgs{};
-        a.F2 = dev_frame(F, d, o[b].f.kp, o[b].f.desc);
+        const LocalMapRegions& l = o[b].r;
+        put_frame(s, o[b].f, F);
+        s.put(l.assigned, q.f_assigned);
+        s.put(l.pos, q.mp_pos);
+        s.put(l.normal, q.mp_normal);
+        s.put(l.dist, q.mp_dist);
+        if (q.mp_skip) s.put(l.skip, q.mp_skip);
+        else s.fill(l.skip, 0);
+        s.put(l.desc, q.mp_desc);
+        s.fill(l.m.out, 0xFF);   // matches_f: -1 unless assigned here
+        s.fill(l.m.n, 0);
+        s.fill(l.count, 0);      // k_frustum only adds to it
+        SearchArgs a = local_map_job(s, staged_frame(s, o[b].f, F), l, q.cam, F->nlevels, F->scale_factor,
+                                     q.view_cos_limit, q.th, q.nnratio);
         a.nq = q.n_mp;
-        a.q_xyz = reinterpret_cast<const float*>(d + o[b].pos);
-        a.mp_normal = reinterpret_cast<const float*>(d + o[b].normal);
-        a.mp_dist = reinterpret_cast<const float*>(d + o[b].dist);
-        a.mp_skip = d + o[b].skip;
-        a.q_desc = d + o[b].desc;
-        a.f2_assigned = d + o[b].assigned;
         for (int i = 0; i < 9; i++) a.Rcw[i] = q.Rcw[i];
         for (int i = 0; i < 3; i++) {
             a.tcw[i] = q.tcw[i];
             a.Ow[i] = q.Ow[i];
         }
-        for (int i = 0; i < 4; i++) a.cam[i] = q.cam[i];
-        frame_scales(F, a.scale);
-        a.nlevels = F->nlevels;
-        a.view_cos_limit = q.view_cos_limit;
-        a.th = q.th;
-        a.nnratio = q.nnratio;
-        a.fr_in_view = d + o[b].in_view;
-        a.fr_proj = reinterpret_cast<float*>(d + o[b].proj);
-        a.fr_pred = reinterpret_cast<int32_t*>(d + o[b].pred);
-        a.fr_cos = reinterpret_cast<float*>(d + o[b].cos);
-        a.fr_count = reinterpret_cast<int32_t*>(d + o[b].count);
-        // the search reads the frustum results as its per-point inputs
-        a.q_valid = a.fr_in_view;
-        a.proj_xy = a.fr_proj;
-        a.pred_level = a.fr_pred;
-        a.view_cos = a.fr_cos;
-        a.out = reinterpret_cast<int32_t*>(d + o[b].out);
-        a.out_n = reinterpret_cast<int32_t*>(d + o[b].out_n);
+        s.put(jobs.part(b * sizeof(SearchArgs), 1), &a);
     }
-    cp(o_jobs, jobs.data(), (size_t)B * sizeof(SearchArgs));
     // inputs and the job table in one copy, then each job's -1 match vector
     // and zero counters (contiguous per job)
-    ORBX_HIP_CHECK(hipMemcpyAsync(d, h, o_outputs, hipMemcpyHostToDevice, ctx->stream));
+    if ((r = s.upload(o_outputs)) != ORBX_OK) return r;
     for (int b = 0; b < B; b++)
-        ORBX_HIP_CHECK(hipMemcpyAsync(d + o[b].out, h + o[b].out, o[b].count + 4 - o[b].out, hipMemcpyHostToDevice,
-                                      ctx->stream));
-    const SearchArgs* dj = reinterpret_cast<const SearchArgs*>(d + o_jobs);
+        if ((r = s.upload(o[b].r.m.out.off, o[b].r.count.end())) != ORBX_OK) return r;
+    const SearchArgs* dj = s.dev(jobs);
     if (max_mp > 0)
         hipLaunchKernelGGL(k_frustum, dim3((max_mp + 255) / 256, B), dim3(256), 0, ctx->stream, dj);
     if (B == 1) {
-        if ((r = launch_area_search<kQLocal>(ctx, dj, 1, max_mp, max_n, u, oa)) != ORBX_OK) return r;
+        if ((r = launch_area_search<kQLocal>(s, dj, 1, max_mp, max_n, area)) != ORBX_OK) return r;
     } else {
         hipLaunchKernelGGL(k_proj_local_jobs, dim3(B), dim3(64), tab_lds(max_n), ctx->stream, dj);
     }
     ORBX_HIP_CHECK(hipGetLastError());
-    ORBX_HIP_CHECK(hipMemcpyAsync(h + o_outputs, d + o_outputs, o_end - o_outputs, hipMemcpyDeviceToHost, ctx->stream));
-    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if ((r = s.download(o_outputs, o_end)) != ORBX_OK) return r;
     for (int b = 0; b < B; b++) {
         orbx_local_map_query& q = qs[b];
-        const size_t n = q.frame->n, m = q.n_mp;
-        std::memcpy(q.matches_f, h + o[b].out, n * 4);
-        std::memcpy(&q.n_matches, h + o[b].out_n, 4);
-        std::memcpy(&q.n_in_view, h + o[b].count, 4);
-        if (q.in_view) std::memcpy(q.in_view, h + o[b].in_view, m);
-        if (q.proj_xy) std::memcpy(q.proj_xy, h + o[b].proj, m * 8);
-        if (q.pred_level) std::memcpy(q.pred_level, h + o[b].pred, m * 4);
-        if (q.view_cos) std::memcpy(q.view_cos, h + o[b].cos, m * 4);
+        const LocalMapRegions& l = o[b].r;
+        s.get(q.matches_f, l.m.out);
+        s.get(&q.n_matches, l.m.n);
+        s.get(&q.n_in_view, l.count);
+        s.get(q.in_view, l.in_view);
+        s.get(q.proj_xy, l.proj);
+        s.get(q.pred_level, l.pred);
+        s.get(q.view_cos, l.cos);
     }
     return ORBX_OK;
 }
@@ -1873,28 +1856,23 @@ static int hamming_bf_impl(orbx_ctx* ctx, const uint8_t* dA, int nA, const uint8
     if (!ctx || nA < 0 || nB < 0 || (nA && (!dA || !best_idx || !best || !second)) || (nB && !dB)) return ORBX_ERR_ARG;
     if (nA == 0) return ORBX_OK;
     ctx_enter(ctx);
-    Uploader u{ctx};
-    const size_t oa = u.reserve((size_t)nA * 32), ob = u.reserve((size_t)nB * 32);
-    const size_t oi = u.reserve((size_t)nA * 4), o1 = u.reserve((size_t)nA * 4), o2 = u.reserve((size_t)nA * 4);
-    const size_t om = u.reserve((size_t)nA * 4);
-    int r = ensure_scratch(ctx, u.total);
-    Pinned pin{ctx};
-    if (r == ORBX_OK) r = pin.open(u.total);
+    BlockStage s(ctx);
+    const Region<uint8_t> oa = s.take<uint8_t>((size_t)nA * 32), ob = s.take<uint8_t>((size_t)nB * 32);
+    const Region<int32_t> oi = s.take<int32_t>(nA), o1 = s.take<int32_t>(nA), o2 = s.take<int32_t>(nA);
+    const Region<int32_t> om = s.take<int32_t>(nA);
+    int r = s.open(s.total);
     if (r != ORBX_OK) return r;
-    pin.put(oa, dA, (size_t)nA * 32);
-    pin.put(ob, dB, (size_t)nB * 32);
-    if ((r = pin.upload(oi)) != ORBX_OK) return r;
-    uint8_t* base = u.base();
-    hipLaunchKernelGGL(k_hamming_bf, dim3((nA + 255) / 256), dim3(256), 0, ctx->stream, base + oa, nA, base + ob, nB,
-                       reinterpret_cast<int32_t*>(base + oi), reinterpret_cast<int32_t*>(base + o1),
-                       reinterpret_cast<int32_t*>(base + o2), m12 ? reinterpret_cast<int32_t*>(base + om) : nullptr,
-                       th_low, nnratio);
+    s.put(oa, dA);
+    s.put(ob, dB);
+    if ((r = s.upload(oi.off)) != ORBX_OK) return r;
+    hipLaunchKernelGGL(k_hamming_bf, dim3((nA + 255) / 256), dim3(256), 0, ctx->stream, s.dev(oa), nA, s.dev(ob), nB,
+                       s.dev(oi), s.dev(o1), s.dev(o2), m12 ? s.dev(om) : nullptr, th_low, nnratio);
     ORBX_HIP_CHECK(hipGetLastError());
-    if ((r = pin.download(oi, u.total)) != ORBX_OK) return r;
-    pin.get(best_idx, oi, (size_t)nA * 4);
-    pin.get(best, o1, (size_t)nA * 4);
-    pin.get(second, o2, (size_t)nA * 4);
-    pin.get(m12, om, (size_t)nA * 4);
+    if ((r = s.download(oi.off, s.total)) != ORBX_OK) return r;
+    s.get(best_idx, oi);
+    s.get(best, o1);
+    s.get(second, o2);
+    s.get(m12, om);
     return ORBX_OK;
 }
 
@@ -1907,7 +1885,7 @@ int orbx_track_frame(orbx_ctx* ctx, orbx_track_query* q)
     if (!ctx || !q) return ORBX_ERR_ARG;
     const bool from_slot = q->last_slot >= 0;
     if (q->slot < 0 || q->slot >= ctx->slots || q->last_slot >= ctx->slots || q->last_slot == q->slot ||
-        (!from_slot && !valid_view(q->last)) || (from_slot && q->last_cap < 0) || q->n_mp < 0 ||
+        (!from_slot && !valid_frame_view(q->last)) || (from_slot && q->last_cap < 0) || q->n_mp < 0 ||
         (q->n_mp > 0 && (!q->mp_pos || !q->mp_normal || !q->mp_dist || !q->mp_desc)) || !q->Tcw_pred || !q->cam ||
         !q->inv_level_sigma2 || !q->cur_mp || !q->cur_outlier || q->cap < 0 || q->nlevels <= 0 ||
         q->nlevels > kMaxLevels || q->mode < 0 || q->mode > 1 || q->min_octave < 0)
@@ -1928,163 +1906,105 @@ int orbx_track_frame(orbx_ctx* ctx, orbx_track_query* q)
     const int m_local = q->n_local_mp > 0 ? std::min(q->n_local_mp, m) : m;   // the frustum search's points
     const size_t img_bytes = q->image ? (size_t)q->w * q->h : 0;
     // [inputs | SearchArgs x2 | read-back block | device-only state]
-    Uploader u{ctx};
-    FrameOffs oL{};
-    if (!from_slot) oL = reserve_frame(u, q->last);
-    const size_t o_lmp = u.reserve((size_t)n1 * 4), o_lout = u.reserve(n1);
-    const size_t o_pos = u.reserve((size_t)m * 12), o_nrm = u.reserve((size_t)m * 12), o_dist = u.reserve((size_t)m * 8);
-    const size_t o_desc = u.reserve((size_t)m * 32), o_skin = u.reserve(m), o_isig = u.reserve(4 * kMaxLevels);
-    const size_t o_img = u.reserve(img_bytes);
-    const size_t o_jm = u.reserve(sizeof(SearchArgs)), o_jl = u.reserve(sizeof(SearchArgs));
+    BlockStage s(ctx);
+    FrameRegions oL{};
+    if (!from_slot) oL = take_frame(s, q->last);
+    const Region<int32_t> o_lmp = s.take<int32_t>(n1);
+    const Region<uint8_t> o_lout = s.take<uint8_t>(n1);
+    LocalMapRegions lm;
+    lm.pos = s.take<float>((size_t)m * 3);
+    lm.normal = s.take<float>((size_t)m * 3);
+    lm.dist = s.take<float>((size_t)m * 2);
+    lm.desc = s.take<uint8_t>((size_t)m * 32);
+    const Region<uint8_t> o_skin = s.take<uint8_t>(m);
+    const Region<float> o_isig = s.take<float>(kMaxLevels);
+    const Region<uint8_t> o_img = s.take<uint8_t>(img_bytes);
+    const Region<SearchArgs> o_jm = s.take<SearchArgs>(1), o_jl = s.take<SearchArgs>(1);
     // mode 1: the two WindowSearch jobs and the pair search's
-    const size_t o_jw = u.reserve(prev ? 2 * sizeof(SearchArgs) : 0), o_jp = u.reserve(prev ? sizeof(SearchArgs) : 0);
-    const size_t in_end = u.total;
-    const size_t o_out = u.reserve(sizeof(TrackOut) + (size_t)cap * 5), out_end = u.total;
-    const size_t o_qxyz = u.reserve((size_t)n1 * 12), o_qv = u.reserve(n1);
-    const size_t o_mout = u.reserve((size_t)cap * 4 + 4), o_mn = u.reserve(4);
-    const size_t o_lo = u.reserve((size_t)cap * 4 + 4), o_ln = u.reserve(4), o_cnt = u.reserve(4);
-    const size_t o_fiv = u.reserve(m), o_fpr = u.reserve((size_t)m * 8), o_fpl = u.reserve((size_t)m * 4);
-    const size_t o_fcos = u.reserve((size_t)m * 4), o_cmp = u.reserve((size_t)cap * 4), o_fas = u.reserve(cap);
-    const size_t o_skip = u.reserve(m), o_hdr = u.reserve(3 * sizeof(PoseHdr)), o_edg = u.reserve((size_t)cap * 72);
-    const size_t o_ekp = u.reserve((size_t)cap * 12), o_flg = u.reserve((size_t)cap * 3);
-    const size_t o_pout = u.reserve(3 * sizeof(PoseOut)), o_st = u.reserve(32);
-    size_t o_wout[2] = {0, 0}, o_wn[2] = {0, 0}, o_pout2 = 0, o_pn = 0, o_wv = 0, o_pv = 0;
+    const Region<SearchArgs> o_jw = s.take<SearchArgs>(prev ? 2 : 0), o_jp = s.take<SearchArgs>(prev ? 1 : 0);
+    const size_t in_end = s.total;
+    // TrackOut, then cur_mp[cap] and cur_outlier[cap] behind it
+    const Region<uint8_t> o_out = s.take<uint8_t>(sizeof(TrackOut) + (size_t)cap * 5);
+    const size_t out_end = s.total;
+    const Region<float> o_qxyz = s.take<float>((size_t)n1 * 3);
+    const Region<uint8_t> o_qv = s.take<uint8_t>(n1);
+    const MatchRegions mm = take_matches(s, cap);
+    lm.m = take_matches(s, cap);
+    lm.count = s.take<int32_t>(1);
+    lm.in_view = s.take<uint8_t>(m);
+    lm.proj = s.take<float>((size_t)m * 2);
+    lm.pred = s.take<int32_t>(m);
+    lm.cos = s.take<float>(m);
+    const Region<int32_t> o_cmp = s.take<int32_t>(cap);
+    lm.assigned = s.take<uint8_t>(cap);
+    lm.skip = s.take<uint8_t>(m);
+    const Region<PoseHdr> o_hdr = s.take<PoseHdr>(3);
+    const Region<float> o_edg = s.take<float>((size_t)cap * 18);
+    const Region<int32_t> o_ekp = s.take<int32_t>((size_t)cap * 3);
+    const Region<uint8_t> o_flg = s.take<uint8_t>((size_t)cap * 3);
+    const Region<PoseOut> o_pout = s.take<PoseOut>(3);
+    const Region<int32_t> o_st = s.take<int32_t>(8);
+    MatchRegions mw[2] = {}, mp{};
+    Region<uint8_t> o_wv, o_pv;
     if (prev) {
-        for (int k = 0; k < 2; k++) {
-            o_wout[k] = u.reserve((size_t)cap * 4 + 4);
-            o_wn[k] = u.reserve(4);
-        }
-        o_pout2 = u.reserve((size_t)cap * 4 + 4);
-        o_pn = u.reserve(4);
-        o_wv = u.reserve(n1);
-        o_pv = u.reserve(n1);
+        for (int k = 0; k < 2; k++) mw[k] = take_matches(s, cap);
+        mp = take_matches(s, cap);
+        o_wv = s.take<uint8_t>(n1);
+        o_pv = s.take<uint8_t>(n1);
     }
-    const AreaBufs am = reserve_area(u, 1, n1), al = reserve_area(u, 1, m_local);
-    r = ensure_scratch(ctx, u.total);
-    Pinned pin{ctx};
-    if (r == ORBX_OK) r = pin.open(out_end);
-    if (r != ORBX_OK) return r;
-    uint8_t* d = u.base();
-    if (!from_slot) put_frame(pin, oL, q->last);
-    pin.put(o_lmp, q->last_mp, (size_t)n1 * 4);
-    pin.put(o_lout, q->last_outlier, n1);
-    pin.put(o_pos, q->mp_pos, (size_t)m * 12);
-    pin.put(o_nrm, q->mp_normal, (size_t)m * 12);
-    pin.put(o_dist, q->mp_dist, (size_t)m * 8);
-    pin.put(o_desc, q->mp_desc, (size_t)m * 32);
-    if (q->mp_skip) pin.put(o_skin, q->mp_skip, m);
-    pin.put(o_isig, q->inv_level_sigma2, (size_t)q->nlevels * 4);
+    const AreaBufs am = take_area(s, 1, n1), al = take_area(s, 1, m_local);
+    if ((r = s.open(out_end)) != ORBX_OK) return r;
+    if (!from_slot) put_frame(s, oL, q->last);
+    s.put(o_lmp, q->last_mp);
+    s.put(o_lout, q->last_outlier);
+    s.put(lm.pos, q->mp_pos);
+    s.put(lm.normal, q->mp_normal);
+    s.put(lm.dist, q->mp_dist);
+    s.put(lm.desc, q->mp_desc);
+    if (q->mp_skip) s.put(o_skin, q->mp_skip);
+    s.put(o_isig, q->inv_level_sigma2, q->nlevels);
     if (q->image) {
         if (q->stride == (size_t)q->w) {
-            pin.put(o_img, q->image, img_bytes);
+            s.put(o_img, q->image);
         } else {
-            for (int y = 0; y < q->h; y++) pin.put(o_img + (size_t)y * q->w, q->image + (size_t)y * q->stride, q->w);
+            for (int y = 0; y < q->h; y++) s.put(o_img.part((size_t)y * q->w, q->w), q->image + (size_t)y * q->stride);
         }
     }
-    // the slots' frames: keypoints where extraction left them, the count on
-    // the device, bounds of orbx_dev_set_image_bounds (default the image)
-    auto slot_frame = [&](int slot) {
-        FrameDev F;
-        F.kps = ctx->out_kps + (size_t)slot * nf;
-        F.desc = ctx->out_desc + (size_t)slot * nf * 32;
-        F.n = nf;
-        F.min_x = ctx->has_bounds ? ctx->bounds[0] : 0.f;
-        F.max_x = ctx->has_bounds ? ctx->bounds[1] : (float)g.w;
-        F.min_y = ctx->has_bounds ? ctx->bounds[2] : 0.f;
-        F.max_y = ctx->has_bounds ? ctx->bounds[3] : (float)g.h;
-        F.grid_w_inv = static_cast<float>(kGridCols) / (F.max_x - F.min_x);
-        F.grid_h_inv = static_cast<float>(kGridRows) / (F.max_y - F.min_y);
-        return F;
-    };
-    float scale[kMaxLevels] = {};
-    scale[0] = 1.0f;
-    for (int i = 1; i < g.nlevels; i++) scale[i] = scale[i - 1] * g.scale_factor;   // src/Frame.cc:98-102
     // SearchByProjection(mCurrentFrame, mLastFrame, 15), ORBmatcher(0.9, true)
-    // (src/Tracking.cc:574-584): queries = the last frame's keypoints
-    SearchArgs jm{};
-    jm.F1 = from_slot ? slot_frame(q->last_slot) : dev_frame(q->last, d, oL.kp, oL.desc);
-    jm.F2 = slot_frame(q->slot);
+    // (src/Tracking.cc:574-584): queries = the last frame's keypoints.  The
+    // slots' frames have their count on the device (F2_cnt).
+    FrameDev Last = from_slot ? slot_frame_dev(ctx, q->last_slot, nullptr) : staged_frame(s, oL, q->last);
+    if (from_slot) Last.n = n1;   // queries past the slot's count are not valid (k_track_stage 0)
+    const FrameDev Cur = slot_frame_dev(ctx, q->slot, nullptr);
+    SearchArgs jm = motion_job(s, Last, Cur, o_qxyz, o_qv, lm.assigned, q->Tcw_pred, q->cam, g.nlevels, g.scale_factor,
+                               15.f, 1, mm);
     jm.F2_cnt = ctx->out_n + q->slot;
-    if (from_slot) jm.F1.n = n1;   // queries past the slot's count are not valid (k_track_stage 0)
-    jm.q_xyz = reinterpret_cast<const float*>(d + o_qxyz);
-    jm.q_valid = d + o_qv;
-    jm.f2_assigned = d + o_fas;
-    for (int i = 0; i < 12; i++) jm.T[i] = q->Tcw_pred[i];
-    for (int i = 0; i < 4; i++) jm.cam[i] = q->cam[i];
-    std::memcpy(jm.scale, scale, sizeof(scale));
-    jm.th = 15.f;
-    jm.check_ori = 1;
-    jm.out = reinterpret_cast<int32_t*>(d + o_mout);
-    jm.out_n = reinterpret_cast<int32_t*>(d + o_mn);
     // SearchReferencePointsInFrustum (src/Tracking.cc:701-752): the pose and
     // the query count are filled in on the device (k_track_stage 2)
-    SearchArgs jl{};
-    jl.F2 = slot_frame(q->slot);
-    jl.F2_cnt = ctx->out_n + q->slot;
-    jl.nq = 0;
-    jl.q_xyz = reinterpret_cast<const float*>(d + o_pos);
-    jl.mp_normal = reinterpret_cast<const float*>(d + o_nrm);
-    jl.mp_dist = reinterpret_cast<const float*>(d + o_dist);
-    jl.mp_skip = d + o_skip;
-    jl.q_desc = d + o_desc;
-    jl.f2_assigned = d + o_fas;
-    for (int i = 0; i < 4; i++) jl.cam[i] = q->cam[i];
-    std::memcpy(jl.scale, scale, sizeof(scale));
-    jl.nlevels = g.nlevels;
-    jl.view_cos_limit = 0.5f;
-    jl.th = q->th_local;
-    jl.nnratio = 0.8f;
-    jl.fr_in_view = d + o_fiv;
-    jl.fr_proj = reinterpret_cast<float*>(d + o_fpr);
-    jl.fr_pred = reinterpret_cast<int32_t*>(d + o_fpl);
-    jl.fr_cos = reinterpret_cast<float*>(d + o_fcos);
-    jl.fr_count = reinterpret_cast<int32_t*>(d + o_cnt);
-    jl.q_valid = jl.fr_in_view;
-    jl.proj_xy = jl.fr_proj;
-    jl.pred_level = jl.fr_pred;
-    jl.view_cos = jl.fr_cos;
-    jl.out = reinterpret_cast<int32_t*>(d + o_lo);
-    jl.out_n = reinterpret_cast<int32_t*>(d + o_ln);
-    pin.put(o_jm, &jm, sizeof(jm));
-    pin.put(o_jl, &jl, sizeof(jl));
+    SearchArgs jl = local_map_job(s, Cur, lm, q->cam, g.nlevels, g.scale_factor, 0.5f, q->th_local, 0.8f);
+    jl.F2_cnt = jm.F2_cnt;
+    const SearchArgs* dm = put_job(s, o_jm, jm);
+    const SearchArgs* dl = put_job(s, o_jl, jl);
     if (prev) {
         // WindowSearch(mLastFrame, mCurrentFrame, 200, minOctave) and (100, 0),
         // ORBmatcher(0.9, true) (src/Tracking.cc:500-517)
         for (int k = 0; k < 2; k++) {
-            SearchArgs jw{};
-            jw.F1 = jm.F1;
-            jw.F2 = jm.F2;
+            SearchArgs jw = window_job(s, Last, Cur, o_wv, k == 0 ? 200 : 100, k == 0 ? q->min_octave : 0, -1, 0.9f, 1,
+                                       mw[k]);
             jw.F2_cnt = jm.F2_cnt;
-            jw.q_valid = d + o_wv;
-            jw.window = k == 0 ? 200 : 100;
-            jw.min_level = k == 0 ? q->min_octave : 0;
-            jw.max_level = 0x7fffffff;
-            jw.nnratio = 0.9f;
-            jw.check_ori = 1;
-            jw.out = reinterpret_cast<int32_t*>(d + o_wout[k]);
-            jw.out_n = reinterpret_cast<int32_t*>(d + o_wn[k]);
-            pin.put(o_jw + k * sizeof(SearchArgs), &jw, sizeof(jw));
+            put_job(s, o_jw.part(k * sizeof(SearchArgs), 1), jw);
         }
         // SearchByProjection(mLastFrame, mCurrentFrame, 15 or 50) (:544, :547):
         // pose and window set on the device
-        SearchArgs jp{};
-        jp.F1 = jm.F1;
-        jp.F2 = jm.F2;
+        SearchArgs jp = pair_job(s, Last, Cur, o_qxyz, o_pv, lm.assigned, q->cam, 0.9f, mp);
         jp.F2_cnt = jm.F2_cnt;
-        jp.q_xyz = jm.q_xyz;
-        jp.q_valid = d + o_pv;
-        jp.f2_assigned = d + o_fas;
-        for (int i = 0; i < 4; i++) jp.cam[i] = q->cam[i];
-        jp.nnratio = 0.9f;
-        jp.out = reinterpret_cast<int32_t*>(d + o_pout2);
-        jp.out_n = reinterpret_cast<int32_t*>(d + o_pn);
-        pin.put(o_jp, &jp, sizeof(jp));
+        put_job(s, o_jp, jp);
     }
     TrackDev td{};
     td.cur_kps = jm.F2.kps;
     td.cur_cnt = jm.F2_cnt;
-    td.last_mp = reinterpret_cast<const int32_t*>(d + o_lmp);
-    td.last_outlier = d + o_lout;
+    td.last_mp = s.dev(o_lmp);
+    td.last_outlier = s.dev(o_lout);
     td.n_last = n1;
     td.last_cnt = from_slot ? ctx->out_n + q->last_slot : nullptr;
     td.err = ctx->error_flags;
@@ -2092,12 +2012,12 @@ int orbx_track_frame(orbx_ctx* ctx, orbx_track_query* q)
     td.n_local = m_local;
     td.cap = cap;
     td.mp_pos = jl.q_xyz;
-    td.mp_skip_in = q->mp_skip ? d + o_skin : nullptr;
-    td.isig = reinterpret_cast<const float*>(d + o_isig);
+    td.mp_skip_in = q->mp_skip ? s.dev(o_skin) : nullptr;
+    td.isig = s.dev(o_isig);
     for (int i = 0; i < 12; i++) td.Tpred[i] = q->Tcw_pred[i];
     for (int i = 0; i < 4; i++) td.cam[i] = q->cam[i];
-    td.q_xyz = reinterpret_cast<float*>(d + o_qxyz);
-    td.q_valid = d + o_qv;
+    td.q_xyz = s.dev(o_qxyz);
+    td.q_valid = s.dev(o_qv);
     td.motion_out = jm.out;
     td.motion_n = jm.out_n;
     td.local_out = jl.out;
@@ -2106,37 +2026,37 @@ int orbx_track_frame(orbx_ctx* ctx, orbx_track_query* q)
     td.motion_n_w = jm.out_n;
     td.local_out_w = jl.out;
     td.local_n_w = jl.out_n;
-    td.cur_mp = reinterpret_cast<int32_t*>(d + o_cmp);
-    td.f_assigned = d + o_fas;
-    td.mp_skip = d + o_skip;
-    td.local_job = reinterpret_cast<SearchArgs*>(d + o_jl);
-    td.hdr = reinterpret_cast<PoseHdr*>(d + o_hdr);
-    td.edges = reinterpret_cast<float*>(d + o_edg);
-    td.edge_kp = reinterpret_cast<int32_t*>(d + o_ekp);
-    td.flags = d + o_flg;
-    td.pout = reinterpret_cast<const PoseOut*>(d + o_pout);
-    td.st = reinterpret_cast<int32_t*>(d + o_st);
-    td.out = reinterpret_cast<TrackOut*>(d + o_out);
+    td.cur_mp = s.dev(o_cmp);
+    td.f_assigned = s.dev(lm.assigned);
+    td.mp_skip = s.dev(lm.skip);
+    td.local_job = s.dev(o_jl);
+    td.hdr = s.dev(o_hdr);
+    td.edges = s.dev(o_edg);
+    td.edge_kp = s.dev(o_ekp);
+    td.flags = s.dev(o_flg);
+    td.pout = s.dev(o_pout);
+    td.st = s.dev(o_st);
+    td.out = reinterpret_cast<TrackOut*>(s.dev(o_out));
     td.mode = q->mode;
     td.min_octave = q->min_octave;
     if (prev) {
         for (int k = 0; k < 2; k++) {
-            td.win_job[k] = reinterpret_cast<SearchArgs*>(d + o_jw + k * sizeof(SearchArgs));
-            td.win_out[k] = reinterpret_cast<int32_t*>(d + o_wout[k]);
-            td.win_n[k] = reinterpret_cast<int32_t*>(d + o_wn[k]);
+            td.win_job[k] = s.dev(o_jw) + k;
+            td.win_out[k] = s.dev(mw[k].out);
+            td.win_n[k] = s.dev(mw[k].n);
         }
-        td.pair_job = reinterpret_cast<SearchArgs*>(d + o_jp);
-        td.pair_out = reinterpret_cast<int32_t*>(d + o_pout2);
-        td.pair_n = reinterpret_cast<int32_t*>(d + o_pn);
-        td.w_valid = d + o_wv;
-        td.p_valid = d + o_pv;
+        td.pair_job = s.dev(o_jp);
+        td.pair_out = s.dev(mp.out);
+        td.pair_n = s.dev(mp.n);
+        td.w_valid = s.dev(o_wv);
+        td.p_valid = s.dev(o_pv);
     } else {
-        td.pair_job = reinterpret_cast<SearchArgs*>(d + o_jm);   // stage 4 reads its T only for status 3
+        td.pair_job = s.dev(o_jm);   // stage 4 reads its T only for status 3
     }
     // one upload; the image into its slot and the slot's extraction
-    if ((r = pin.upload(in_end)) != ORBX_OK) return r;
+    if ((r = s.upload(in_end)) != ORBX_OK) return r;
     if (q->image) {
-        ORBX_HIP_CHECK(hipMemcpyAsync(ctx->frames + (size_t)q->slot * img_bytes, d + o_img, img_bytes,
+        ORBX_HIP_CHECK(hipMemcpyAsync(ctx->frames + (size_t)q->slot * img_bytes, s.dev(o_img), img_bytes,
                                       hipMemcpyDeviceToDevice, ctx->stream));
         ctx->last_first = q->slot;
         ctx->last_count = 1;
@@ -2153,40 +2073,36 @@ int orbx_track_frame(orbx_ctx* ctx, orbx_track_query* q)
     ed.px = td.edges + 3 * arr;
     ed.py = td.edges + 4 * arr;
     ed.pz = td.edges + 5 * arr;
-    uint8_t* flags = d + o_flg;
-    PoseOut* pout = reinterpret_cast<PoseOut*>(d + o_pout);
-    const SearchArgs* dm = reinterpret_cast<const SearchArgs*>(d + o_jm);
-    const SearchArgs* dl = reinterpret_cast<const SearchArgs*>(d + o_jl);
-    auto stage = [&](int s) { hipLaunchKernelGGL(k_track_stage, dim3(1), dim3(kTrackThreads), 0, ctx->stream, td, s); };
+    uint8_t* flags = s.dev(o_flg);
+    PoseOut* pout = s.dev(o_pout);
+    auto stage = [&](int st) { hipLaunchKernelGGL(k_track_stage, dim3(1), dim3(kTrackThreads), 0, ctx->stream, td, st); };
     if (!prev) {
         stage(0);
-        if ((r = launch_area_search<kQMotion>(ctx, dm, 1, n1, nf, u, am)) != ORBX_OK) return r;
+        if ((r = launch_area_search<kQMotion>(s, dm, 1, n1, nf, am)) != ORBX_OK) return r;
         stage(1);
     } else {
-        const SearchArgs* dw = reinterpret_cast<const SearchArgs*>(d + o_jw);
+        const SearchArgs* dw = s.dev(o_jw);
         stage(10);
-        if ((r = launch_area_search<kQWindow>(ctx, dw, 1, n1, nf, u, am)) != ORBX_OK) return r;
+        if ((r = launch_area_search<kQWindow>(s, dw, 1, n1, nf, am)) != ORBX_OK) return r;
         stage(11);
-        if ((r = launch_area_search<kQWindow>(ctx, dw + 1, 1, n1, nf, u, am)) != ORBX_OK) return r;
+        if ((r = launch_area_search<kQWindow>(s, dw + 1, 1, n1, nf, am)) != ORBX_OK) return r;
         stage(12);
         if ((r = launch_pose_device(ctx, td.hdr + 2, ed, flags, pout + 2, 1)) != ORBX_OK) return r;
         stage(13);
-        if ((r = launch_area_search<kQPair>(ctx, reinterpret_cast<const SearchArgs*>(d + o_jp), 1, n1, nf, u, am)) !=
-            ORBX_OK)
-            return r;
+        if ((r = launch_area_search<kQPair>(s, s.dev(o_jp), 1, n1, nf, am)) != ORBX_OK) return r;
         stage(14);
     }
     if ((r = launch_pose_device(ctx, td.hdr, ed, flags, pout, 1)) != ORBX_OK) return r;
     stage(2);
     if (m_local > 0) hipLaunchKernelGGL(k_frustum, dim3((m_local + 255) / 256, 1), dim3(256), 0, ctx->stream, dl);
-    if ((r = launch_area_search<kQLocal>(ctx, dl, 1, m_local, nf, u, al)) != ORBX_OK) return r;
+    if ((r = launch_area_search<kQLocal>(s, dl, 1, m_local, nf, al)) != ORBX_OK) return r;
     stage(3);
     if ((r = launch_pose_device(ctx, td.hdr + 1, ed, flags, pout + 1, 1)) != ORBX_OK) return r;
     stage(4);
     ORBX_HIP_CHECK(hipGetLastError());
-    if ((r = pin.download(o_out, out_end)) != ORBX_OK) return r;
+    if ((r = s.download(o_out.off, out_end)) != ORBX_OK) return r;
     TrackOut o;
-    pin.get(&o, o_out, sizeof(o));
+    s.get(&o, o_out.part<TrackOut>(0, 1));
     for (int i = 0; i < 12; i++) q->Tcw[i] = o.T[i];
     q->n_cur = o.n_cur;
     q->status = o.status;
@@ -2197,8 +2113,8 @@ int orbx_track_frame(orbx_ctx* ctx, orbx_track_query* q)
     q->n_local = o.n_local;
     q->n_inliers = o.n_inliers;
     const int nc = std::min(o.n_cur, q->cap);
-    pin.get(q->cur_mp, o_out + sizeof(TrackOut), (size_t)nc * 4);
-    pin.get(q->cur_outlier, o_out + sizeof(TrackOut) + (size_t)cap * 4, nc);
+    s.get(q->cur_mp, o_out.part<int32_t>(sizeof(TrackOut), cap), nc);
+    s.get(q->cur_outlier, o_out.part<uint8_t>(sizeof(TrackOut) + (size_t)cap * 4, cap), nc);
     if (o.err) {   // an extraction overflow (k_track_stage read the flags)
         ORBX_HIP_CHECK(hipMemsetAsync(ctx->error_flags, 0, sizeof(int32_t), ctx->stream));
         return ORBX_ERR_CAPACITY;

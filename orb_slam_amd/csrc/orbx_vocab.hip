@@ -23,6 +23,7 @@
 
 #include "orbx_device.h"
 #include "orbx_internal.h"
+#include "orbx_stage.h"
 
 struct orbx_vocab {
     int device = 0;
@@ -274,23 +275,21 @@ extern "C" int orbx_vocab_transform(orbx_ctx* ctx, const orbx_vocab* voc, int n,
         return ORBX_ERR_ARG;
     ctx_enter(ctx);
     if (n > 0) {
-        const size_t o_f = 0, o_w = ((size_t)n * 32 + 255) & ~size_t(255), o_d = o_w + (((size_t)n * 4 + 255) & ~size_t(255)),
-                     o_n = o_d + (((size_t)n * 8 + 255) & ~size_t(255)), total = o_n + (size_t)n * 4;
-        int r = ensure_scratch(ctx, total);
+        ArrayStage s(ctx);
+        const Region<uint8_t> o_f = s.take((size_t)n * 32, desc);
+        const Region<int32_t> o_w = s.take<int32_t>(n);
+        const Region<double> o_d = s.take<double>(n);
+        const Region<int32_t> o_n = s.take<int32_t>(n);
+        int r = s.upload();
         if (r != ORBX_OK) return r;
-        uint8_t* d = static_cast<uint8_t*>(ctx->scratch);
-        ORBX_HIP_CHECK(hipMemcpyAsync(d + o_f, desc, (size_t)n * 32, hipMemcpyHostToDevice, ctx->stream));
         VocabDev v{voc->child_ptr, voc->child_idx, voc->desc, voc->weight, voc->word_id};
         timer_begin(ctx, "vocab");
         hipLaunchKernelGGL(k_vocab_transform, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, v,
-                           reinterpret_cast<const uint4*>(d + o_f), n, voc->L - levelsup,
-                           reinterpret_cast<int32_t*>(d + o_w), reinterpret_cast<double*>(d + o_d),
-                           reinterpret_cast<int32_t*>(d + o_n));
+                           reinterpret_cast<const uint4*>(s.dev(o_f)), n, voc->L - levelsup, s.dev(o_w), s.dev(o_d),
+                           s.dev(o_n));
         timer_end(ctx, "vocab");
         ORBX_HIP_CHECK(hipGetLastError());
-        ORBX_HIP_CHECK(hipMemcpyAsync(word_id, d + o_w, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        ORBX_HIP_CHECK(hipMemcpyAsync(weight, d + o_d, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-        ORBX_HIP_CHECK(hipMemcpyAsync(node_id, d + o_n, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if ((r = s.get(word_id, o_w)) || (r = s.get(weight, o_d)) || (r = s.get(node_id, o_n))) return r;
         ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     }
     // BowVector / FeatureVector in the reference's map order (:1145-1193)
@@ -335,20 +334,23 @@ int ensure_slot_bow(orbx_ctx* ctx)
         ctx->bow_dev = nullptr;
     }
     const size_t S = (size_t)ctx->slots, e = S * nf;
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t o_word = 0, o_w = o_word + al(e * 4), o_node = o_w + al(e * 8), o_fvn = o_node + al(e * 4),
-                 o_fvp = o_fvn + al(e * 4), o_fvf = o_fvp + al(S * (nf + 1) * 4), o_bw = o_fvf + al(e * 4),
-                 o_bv = o_bw + al(e * 4), o_c = o_bv + al(e * 8), total = o_c + al(S * 8);
-    if (hipMalloc(&ctx->bow_dev, total) != hipSuccess) {
+    Layout l;
+    const Region<int32_t> o_word = l.take<int32_t>(e);
+    const Region<double> o_w = l.take<double>(e);
+    const Region<int32_t> o_node = l.take<int32_t>(e);
+    const Region<uint32_t> o_fvn = l.take<uint32_t>(e);
+    const Region<int32_t> o_fvp = l.take<int32_t>(S * (nf + 1)), o_fvf = l.take<int32_t>(e);
+    const Region<uint32_t> o_bw = l.take<uint32_t>(e);
+    const Region<double> o_bv = l.take<double>(e);
+    const Region<int32_t> o_c = l.take<int32_t>(S * 2);
+    if (hipMalloc(&ctx->bow_dev, l.total) != hipSuccess) {
         ctx->bow_dev = nullptr;
         return ORBX_ERR_NOMEM;
     }
-    uint8_t* d = static_cast<uint8_t*>(ctx->bow_dev);
-    ctx->bow = SlotBowDev{reinterpret_cast<int32_t*>(d + o_word), reinterpret_cast<double*>(d + o_w),
-                          reinterpret_cast<int32_t*>(d + o_node), reinterpret_cast<uint32_t*>(d + o_fvn),
-                          reinterpret_cast<int32_t*>(d + o_fvp), reinterpret_cast<int32_t*>(d + o_fvf),
-                          reinterpret_cast<uint32_t*>(d + o_bw), reinterpret_cast<double*>(d + o_bv),
-                          reinterpret_cast<int32_t*>(d + o_c)};
+    void* d = ctx->bow_dev;
+    ctx->bow = SlotBowDev{region_ptr(d, o_word), region_ptr(d, o_w),   region_ptr(d, o_node),
+                          region_ptr(d, o_fvn),  region_ptr(d, o_fvp), region_ptr(d, o_fvf),
+                          region_ptr(d, o_bw),   region_ptr(d, o_bv),  region_ptr(d, o_c)};
     ctx->bow_nf = nf;
     ctx->bow_ready.assign(ctx->slots, 0);
     return ORBX_OK;

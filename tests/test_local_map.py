@@ -166,19 +166,78 @@ def test_oracle_in_frustum_matches_numpy(feats, seed):
     assert q.n_matches > 50
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("seed,th", [(1, 1.0), (2, 5.0), (3, 1.0)])
-def test_search_local_map_matches_oracle(feats, seed, th):
+def empty_case(feats, seed, th, empty):
+    """make_case, with no keypoints in the frame (empty "F") or no map points
+    (empty "n_mp")."""
     (km, dm), (kf, df) = feats
-    ra, rq = make_case(km, dm, kf, df, W, H, seed, th=th)
-    ga, gq = make_case(km, dm, kf, df, W, H, seed, th=th)
+    if empty == "F":
+        kf, df = kf[:0], df[:0]
+    a, q = make_case(km, dm, kf, df, W, H, seed, th=th)
+    if empty == "n_mp":
+        q.n_mp = 0
+    return a, q
+
+
+# the usual cases under their usual ids, then the first one with each side empty
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed,th,empty", [pytest.param(1, 1.0, None, id="1-1.0"), pytest.param(2, 5.0, None, id="2-5.0"),
+                                           pytest.param(3, 1.0, None, id="3-1.0"),
+                                           pytest.param(1, 1.0, "F", id="empty-F"),
+                                           pytest.param(1, 1.0, "n_mp", id="empty-n_mp")])
+def test_search_local_map_matches_oracle(feats, seed, th, empty):
+    ra, rq = empty_case(feats, seed, th, empty)
+    ga, gq = empty_case(feats, seed, th, empty)
     assert ref_lib().orbx_ref_search_local_map(ctypes.byref(rq)) == 0
     ctx = ox.Context(nfeatures=100, max_w=64, max_h=64, slots=1)
     assert ox.lib().orbx_search_local_map(ctx.handle, ctypes.byref(gq)) == 0
     ref, got = outputs(ra, rq), outputs(ga, gq)
     for r, g in zip(ref, got):
         assert same(r, g)
-    assert gq.n_matches > 0
+    if empty:
+        assert gq.n_matches == 0 and (ga["matches"] == -1).all()
+    else:
+        assert gq.n_matches > 0
+    ctx.close()
+
+
+@pytest.mark.gpu
+def test_search_local_map_twice_on_one_context(feats):
+    """The same query twice on one context: the second call starts from the
+    first one's staging buffers and must still equal the oracle on every
+    output, the counts included."""
+    (km, dm), (kf, df) = feats
+    ra, rq = make_case(km, dm, kf, df, W, H, 1)
+    assert ref_lib().orbx_ref_search_local_map(ctypes.byref(rq)) == 0
+    assert rq.n_in_view > 0
+    ctx = ox.Context(nfeatures=100, max_w=64, max_h=64, slots=1)
+    ga, gq = make_case(km, dm, kf, df, W, H, 1)
+    for call in range(2):
+        assert ox.lib().orbx_search_local_map(ctx.handle, ctypes.byref(gq)) == 0
+        for r, g in zip(outputs(ra, rq), outputs(ga, gq)):
+            assert same(r, g), call
+    ctx.close()
+
+
+@pytest.mark.gpu
+def test_search_local_map_batch_twice_on_one_context(feats):
+    """A batch of two, one with every point skipped, twice on one context."""
+    (km, dm), (kf, df) = feats
+    refs = [make_case(km, dm, kf, df, W, H, s) for s in (10, 11)]
+    gots = [make_case(km, dm, kf, df, W, H, s) for s in (10, 11)]
+    for arrs_q in (refs, gots):
+        arrs_q[1][0]["skip"][:] = 1
+    L = ref_lib()
+    for a, q in refs:
+        assert L.orbx_ref_search_local_map(ctypes.byref(q)) == 0
+    assert refs[0][1].n_in_view > 0 and refs[1][1].n_in_view == 0
+    from local_map_data import LocalMapQuery
+    arr = (LocalMapQuery * 2)(*[q for _, q in gots])
+    ctx = ox.Context(nfeatures=100, max_w=64, max_h=64, slots=1)
+    for call in range(2):
+        assert ox.lib().orbx_search_local_map_batch(ctx.handle, 2, arr) == 0
+        for b, ((ra, rq), (ga, _)) in enumerate(zip(refs, gots)):
+            for r, g in zip(outputs(ra, rq), outputs(ga, arr[b])):
+                assert same(r, g), (call, b)
     ctx.close()
 
 

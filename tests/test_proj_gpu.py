@@ -30,10 +30,20 @@ def gpu_fuse(ctx, KF, mps, T, sim3, th):
     return bi, bd
 
 
-@pytest.mark.parametrize("sim3,th,seed", [(0, 3.0, 0), (0, 5.0, 1), (1, 3.0, 2), (1, 10.0, 3), (0, 2.0, 4), (1, 7.5, 5),
-                                          (0, 12.0, 6), (1, 4.0, 7)])
-def test_fuse_candidates_match_oracle(ctx, sim3, th, seed):
+FUSE_CASES = [(0, 3.0, 0), (0, 5.0, 1), (1, 3.0, 2), (1, 10.0, 3), (0, 2.0, 4), (1, 7.5, 5), (0, 12.0, 6), (1, 4.0, 7)]
+
+
+# the usual cases under their usual ids, then the first one with no keypoints
+# in the keyframe and with no map points
+@pytest.mark.parametrize("sim3,th,seed,empty",
+                         [pytest.param(*c, None, id="-".join(str(v) for v in c)) for c in FUSE_CASES] +
+                         [pytest.param(*FUSE_CASES[0], e, id="empty-" + e) for e in ("KF", "n_mp")])
+def test_fuse_candidates_match_oracle(ctx, sim3, th, seed, empty):
     k1, d1, k2, d2, du, dv = pd.keyframes()
+    if empty == "KF":
+        k2, d2 = k2[:0], d2[:0]
+    if empty == "n_mp":
+        k1, d1 = k1[:0], d1[:0]
     rng = np.random.default_rng(seed)
     T2 = pd.pose_T([du * pd.Z0 / pd.CAM[0], dv * pd.Z0 / pd.CAM[1], 0.0])
     mps = pd.mappoints(k1, d1, pd.pose_T([0, 0, 0]), rng)
@@ -46,7 +56,10 @@ def test_fuse_candidates_match_oracle(ctx, sim3, th, seed):
     KF = pd.view(k2, d2)
     rb = ref_fuse(KF, mps, T, sim3, th)
     gb = gpu_fuse(ctx, KF, mps, T, sim3, th)
-    assert (rb[1] <= 50).sum() > 100
+    if empty:
+        assert (rb[0] == -1).all()   # no candidate for any point
+    else:
+        assert (rb[1] <= 50).sum() > 100
     assert np.array_equal(gb[0], rb[0]) and np.array_equal(gb[1], rb[1])
 
 

@@ -53,6 +53,28 @@ def pose(tx=-0.008, ty=-0.004, yaw=0.002):
     return np.array([[c, 0, s, tx], [0, 1, 0, ty], [-s, 0, c, 0.0]], np.float32).reshape(-1).copy()
 
 
+def with_empty(cases, sides):
+    """The cases under their usual ids with empty=None, then the first case
+    once per side in `sides` with that side empty (no keypoints / no points)."""
+    out = [pytest.param(*c, None, id="-".join(str(v) for v in c)) for c in cases]
+    return out + [pytest.param(*cases[0], e, id="empty-" + e) for e in sides]
+
+
+def cut(feats, empty, side):
+    """A frame's (keypoints, descriptors), none of them when `side` is the empty one."""
+    k, d = feats
+    return (k[:0], d[:0]) if empty == side else (k, d)
+
+
+def check_matches(mg, ng, mr, nr, empty):
+    """Equal to the oracle; with an empty side no match: every entry -1."""
+    assert ng.value == nr.value and np.array_equal(mg, mr)
+    if empty:
+        assert nr.value == 0 and (mg == -1).all()
+    else:
+        assert nr.value > 0
+
+
 @pytest.mark.parametrize("check_ori,window", [(True, 100), (False, 60)])
 def test_search_for_initialization(ctx, frames_feats, check_ori, window):
     (k1, d1), (k2, d2) = frames_feats[0], frames_feats[1]
@@ -115,11 +137,11 @@ def test_search_for_initialization_empty(ctx, frames_feats, which):
 # the two-phase searches (k_area_lists + k_area_replay): short sorted lists,
 # lists of 65..128 candidates in index order, and longer ones that the replay
 # evaluates in full (windows of 100 .. 400 pixels)
-@pytest.mark.parametrize("window,minl,maxl,ratio,ori", [(100, 0, -1, 0.9, True), (200, 1, 5, 0.7, False),
-                                                         (30, 0, 2, 1.0, True), (400, 0, -1, 0.8, True),
-                                                         (60, 0, -1, 0.9, False)])
-def test_window_search(ctx, frames_feats, window, minl, maxl, ratio, ori):
-    (k1, d1), (k2, d2) = frames_feats[0], frames_feats[1]
+@pytest.mark.parametrize("window,minl,maxl,ratio,ori,empty",
+                         with_empty([(100, 0, -1, 0.9, True), (200, 1, 5, 0.7, False), (30, 0, 2, 1.0, True),
+                                     (400, 0, -1, 0.8, True), (60, 0, -1, 0.9, False)], ["F1", "F2"]))
+def test_window_search(ctx, frames_feats, window, minl, maxl, ratio, ori, empty):
+    (k1, d1), (k2, d2) = cut(frames_feats[0], empty, "F1"), cut(frames_feats[1], empty, "F2")
     F1, F2 = views(k1, d1, k2, d2)
     rng = np.random.default_rng(window)
     mp = (rng.random(len(k1)) < 0.7).astype(np.uint8)
@@ -129,13 +151,12 @@ def test_window_search(ctx, frames_feats, window, minl, maxl, ratio, ori):
                                          int(ori), ptr(mr), ctypes.byref(nr)) == 0
     assert ox.lib().orbx_window_search(ctx.handle, ctypes.byref(F1), ctypes.byref(F2), ox._ptr(mp), window, minl,
                                        maxl, ratio, int(ori), ox._ptr(mg), ctypes.byref(ng)) == 0
-    assert ng.value == nr.value and nr.value > 0
-    assert np.array_equal(mg, mr)
+    check_matches(mg, ng, mr, nr, empty)
 
 
-@pytest.mark.parametrize("window", [15, 50, 150, 300])
-def test_search_by_projection_pair(ctx, frames_feats, window):
-    (k1, d1), (k2, d2) = frames_feats[0], frames_feats[1]
+@pytest.mark.parametrize("window,empty", with_empty([(15,), (50,), (150,), (300,)], ["F1", "F2"]))
+def test_search_by_projection_pair(ctx, frames_feats, window, empty):
+    (k1, d1), (k2, d2) = cut(frames_feats[0], empty, "F1"), cut(frames_feats[1], empty, "F2")
     F1, F2 = views(k1, d1, k2, d2)
     rng = np.random.default_rng(window)
     xyz = backproject(k1, rng)
@@ -150,13 +171,14 @@ def test_search_by_projection_pair(ctx, frames_feats, window):
     assert ox.lib().orbx_search_by_projection_pair(ctx.handle, ctypes.byref(F1), ctypes.byref(F2), ox._ptr(xyz),
                                                    ox._ptr(valid), ox._ptr(assigned), ox._ptr(T), ox._ptr(CAM),
                                                    window, 0.9, ox._ptr(mg), ctypes.byref(ng)) == 0
-    assert ng.value == nr.value and nr.value > 0
-    assert np.array_equal(mg, mr)
+    check_matches(mg, ng, mr, nr, empty)
 
 
-@pytest.mark.parametrize("th,ori", [(15.0, True), (7.0, False), (40.0, True), (120.0, False), (2.0, True)])
-def test_search_by_projection_motion(ctx, frames_feats, th, ori):
-    (kl, dl), (kc, dc) = frames_feats[1], frames_feats[2]
+@pytest.mark.parametrize("th,ori,empty", with_empty([(15.0, True), (7.0, False), (40.0, True), (120.0, False),
+                                                     (2.0, True)], ["F1", "F2"]))
+def test_search_by_projection_motion(ctx, frames_feats, th, ori, empty):
+    # F1: the last frame (the queries), F2: the current one
+    (kl, dl), (kc, dc) = cut(frames_feats[1], empty, "F1"), cut(frames_feats[2], empty, "F2")
     C, Lv = views(kc, dc, kl, dl)
     rng = np.random.default_rng(int(th))
     xyz = backproject(kl, rng)
@@ -171,13 +193,12 @@ def test_search_by_projection_motion(ctx, frames_feats, th, ori):
     assert ox.lib().orbx_search_by_projection_motion(ctx.handle, ctypes.byref(C), ctypes.byref(Lv), ox._ptr(xyz),
                                                      ox._ptr(valid), ox._ptr(assigned), ox._ptr(T), ox._ptr(CAM),
                                                      th, int(ori), ox._ptr(mg), ctypes.byref(ng)) == 0
-    assert ng.value == nr.value and nr.value > 0
-    assert np.array_equal(mg, mr)
+    check_matches(mg, ng, mr, nr, empty)
 
 
-@pytest.mark.parametrize("th", [1.0, 5.0, 12.0, 30.0])
-def test_search_by_projection_local(ctx, frames_feats, th):
-    (km, dm), (kf, df) = frames_feats[0], frames_feats[1]
+@pytest.mark.parametrize("th,empty", with_empty([(1.0,), (5.0,), (12.0,), (30.0,)], ["n_mp", "F2"]))
+def test_search_by_projection_local(ctx, frames_feats, th, empty):
+    (km, dm), (kf, df) = cut(frames_feats[0], empty, "n_mp"), cut(frames_feats[1], empty, "F2")
     F = ox.frame_view(kf, df, W, H)
     rng = np.random.default_rng(int(th * 10))
     n = len(km)
@@ -195,8 +216,7 @@ def test_search_by_projection_local(ctx, frames_feats, th):
     assert ox.lib().orbx_search_by_projection_local(ctx.handle, ctypes.byref(F), n, ox._ptr(in_view), ox._ptr(proj),
                                                     ox._ptr(pred), ox._ptr(vcos), ox._ptr(mpd), ox._ptr(assigned),
                                                     th, 0.8, ox._ptr(mg), ctypes.byref(ng)) == 0
-    assert ng.value == nr.value and nr.value > 0
-    assert np.array_equal(mg, mr)
+    check_matches(mg, ng, mr, nr, empty)
 
 
 @pytest.mark.parametrize("na,nb", [(1000, 1000), (2000, 1999), (1, 300), (257, 0), (0, 100), (65, 63), (3000, 4500),
