@@ -26,6 +26,15 @@ the list length.  The reference's loop gives chain query k chain candidate
 k; the parallel rounds settle one more member per round, N + 1 rounds in
 all.  `expect` records what each query must take by construction.
 
+Posed scenes.  Scene.posed(R, t) moves the query points to Rcw^T (xyz - tcw)
+(float64, rounded to float32) and passes [Rcw | tcw] in place of the identity,
+so the projection searches see a full rotation while every query still
+projects to its centre within 1e-3 px; candidates stay 2 px inside or
+outside every box, so `expect` is unchanged.  The posed local-map kind runs
+through isInFrustum (orbx_search_local_map) with normals and distance ranges
+rotated along; isInFrustum cannot predict level 0 away from ratio == 1, so
+its band-0 queries predict level 1 (levels 0 .. 1, radius 12 px).
+
 Also the white-box mirror of launch_area_search's LDS decisions and of the
 replay's claim rounds (mirror()), shared by the CPU and the GPU tests, and
 track_chain(): a chain of displacement among a tracked frame's natural
@@ -217,6 +226,28 @@ class Scene:
         self.vcos = np.full(self.nq, 0.9, np.float32)    # <= 0.998: RadiusByViewingCos gives 4.0
         self.th_local = F32(R0 / 4.0)
         self.th_motion = F32(R0)
+        self.T, self.pose = T_IDENTITY, None
+
+    def posed(self, R, t):
+        """The same scene seen from the pose Xc = R Xw + t."""
+        import copy
+        s = copy.copy(self)
+        R, t = np.asarray(R, np.float64), np.asarray(t, np.float64)
+        Xc = self.xyz.astype(np.float64)
+        s.xyz = np.ascontiguousarray(((Xc - t) @ R).astype(np.float32))       # rows of R^T (Xc - t)
+        s.T = np.ascontiguousarray(np.concatenate([R, t[:, None]], 1).astype(np.float32).reshape(-1))
+        s.pose, s.name = (R, t), self.name + "-posed"
+        if self.kind == "local":
+            s.pred = np.ascontiguousarray(np.maximum(self.pred, 1))
+            dist = np.linalg.norm(Xc, axis=1)
+            e = Xc / dist[:, None]
+            o = np.cross(e, [0.3, -0.5, 0.8])
+            o /= np.linalg.norm(o, axis=1, keepdims=True)
+            s.normal = np.ascontiguousarray(((0.9 * e + np.sqrt(1 - 0.81) * o) @ R).astype(np.float32))
+            ratio = scale_factors()[s.pred].astype(np.float64) * 0.93          # between scale[pred - 1] and scale[pred]
+            s.mp_dist = np.ascontiguousarray(np.stack([dist / ratio, dist * 1.5], 1).astype(np.float32))
+            s.Ow = (-(R.T @ t)).astype(np.float32)
+        return s
 
     def centres(self):
         """Search centre and radius of every query, as the search computes them."""
@@ -227,9 +258,11 @@ class Scene:
         if self.kind == "local":
             r = F32(F32(4.0) * self.th_local) * sf[self.pred]
             return self.proj[:, 0].copy(), self.proj[:, 1].copy(), r.astype(np.float32)
-        x, y = self.xyz[:, 0], self.xyz[:, 1]     # identity pose, depth 1: xc = x, invz = 1
-        u = (CAM[0] * x) * F32(1.0) + CAM[2]
-        v = (CAM[1] * y) * F32(1.0) + CAM[3]
+        T, X = self.T.reshape(3, 4), self.xyz     # as the searches project (unposed: xc = x, invz = 1)
+        c = [((T[r, 0] * X[:, 0] + T[r, 1] * X[:, 1]) + T[r, 2] * X[:, 2]) + T[r, 3] for r in range(3)]
+        inv = (1.0 / c[2].astype(np.float64)).astype(np.float32)
+        u = (CAM[0] * c[0]) * inv + CAM[2]
+        v = (CAM[1] * c[1]) * inv + CAM[3]
         r = np.full(self.nq, F32(R0)) if self.kind == "pair" else self.th_motion * sf[k1["octave"]]
         return u.astype(np.float32), v.astype(np.float32), r.astype(np.float32)
 
@@ -239,7 +272,8 @@ class Scene:
             return o, o
         if self.kind == "motion":
             return o - 1, o + 1
-        return o - 1, o
+        p = self.pred.astype(np.int64)
+        return p - 1, p
 
 
 # ---------------------------------------------------------------------------
@@ -733,9 +767,26 @@ def search(s, fns, handle=None):
     if s.kind == "window":
         a = (r1, r2, ptr(s.valid), R0, 0, -1, s.nnratio, s.check_ori)
     elif s.kind == "pair":
-        a = (r1, r2, ptr(s.xyz), ptr(s.valid), ptr(s.assigned), ptr(T_IDENTITY), ptr(CAM), R0, s.nnratio)
+        a = (r1, r2, ptr(s.xyz), ptr(s.valid), ptr(s.assigned), ptr(s.T), ptr(CAM), R0, s.nnratio)
     elif s.kind == "motion":
-        a = (r2, r1, ptr(s.xyz), ptr(s.valid), ptr(s.assigned), ptr(T_IDENTITY), ptr(CAM), s.th_motion, s.check_ori)
+        a = (r2, r1, ptr(s.xyz), ptr(s.valid), ptr(s.assigned), ptr(s.T), ptr(CAM), s.th_motion, s.check_ori)
+    elif s.pose is not None:
+        # the posed local-map kind: isInFrustum of the map points, then the search (fns["local_map"])
+        from local_map_data import LocalMapQuery
+        T = s.T.reshape(3, 4)
+        keep = dict(Rcw=np.ascontiguousarray(T[:, :3]).reshape(-1), tcw=np.ascontiguousarray(T[:, 3]), Ow=s.Ow,
+                    cam=CAM, mp_pos=s.xyz, mp_normal=s.normal, mp_dist=s.mp_dist,
+                    mp_skip=(s.valid == 0).astype(np.uint8), mp_desc=s.d1, f_assigned=s.assigned,
+                    in_view=np.zeros(max(s.nq, 1), np.uint8), proj_xy=np.zeros((max(s.nq, 1), 2), np.float32),
+                    pred_level=np.zeros(max(s.nq, 1), np.int32), view_cos=np.zeros(max(s.nq, 1), np.float32), matches_f=m)
+        q = LocalMapQuery()
+        q.frame = ctypes.addressof(F2)
+        for field, arr in keep.items():
+            setattr(q, field, arr.ctypes.data)
+        q.n_mp, q.view_cos_limit, q.th, q.nnratio = s.nq, 0.5, float(s.th_local), float(s.nnratio)
+        rc = fns["local_map"](*head, ctypes.byref(q))
+        s.frustum = (keep["in_view"], keep["proj_xy"], keep["pred_level"])
+        return rc, m[:s.n2].astype(np.int64), q.n_matches
     else:
         a = (r2, s.nq, ptr(s.valid), ptr(s.proj), ptr(s.pred), ptr(s.vcos), ptr(s.d1), ptr(s.assigned), s.th_local,
              s.nnratio)

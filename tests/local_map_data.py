@@ -27,14 +27,31 @@ def pose(tx=-0.008, ty=-0.004, yaw=0.002):
     return np.ascontiguousarray(R.reshape(-1)), t, Ow
 
 
-def make_case(km, dm, kf, df, w, h, seed, nlevels=8, scale=1.2, extra=300, th=1.0):
+def general_pose(t=(0.21, -0.13, 0.34)):
+    """A general pose: 0.4 rad about y, then 0.2 about x (float64; of the
+    nine entries of R only R[0][1] is zero, and R[1][0] is not), and a
+    translation of three unequal components."""
+    cy, sy, cx, sx = np.cos(0.4), np.sin(0.4), np.cos(0.2), np.sin(0.2)
+    Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+    Rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
+    return Rx @ Ry, np.array(t, np.float64)
+
+
+def world_from_camera(Xc, R, t):
+    """Xw = R^T (Xc - t) in float64 (rows of Xc)."""
+    return (np.asarray(Xc, np.float64) - t) @ R
+
+
+def make_case(km, dm, kf, df, w, h, seed, nlevels=8, scale=1.2, extra=300, th=1.0, general=False):
     """Local map points: the map frame's keypoints back-projected from the
     identity pose (with their descriptors, noisy normals and the distance
     range ORB-SLAM derives from the observing level,
     MapPoint::UpdateNormalAndDepth), plus `extra` random points of which
     some lie behind the camera, outside the image, outside their distance
-    range or at a grazing viewing angle.  Returns the numpy arrays that keep
-    a LocalMapQuery alive and the query itself."""
+    range or at a grazing viewing angle.  general: the same camera-frame
+    points, normals and ranges seen through general_pose() composed with the
+    usual small motion, so isInFrustum works with a full Rcw.  Returns the
+    numpy arrays that keep a LocalMapQuery alive and the query itself."""
     r = np.random.default_rng(seed)
     n0 = len(km)
     z = r.uniform(2.0, 6.0, n0)
@@ -46,6 +63,10 @@ def make_case(km, dm, kf, df, w, h, seed, nlevels=8, scale=1.2, extra=300, th=1.
     normal = P / np.maximum(dist[:, None], 1e-9)
     normal = normal + r.normal(0, 0.3, normal.shape) * (r.random((n, 1)) < 0.2)   # some grazing views
     normal = (normal / np.linalg.norm(normal, axis=1, keepdims=True)).astype(np.float32)
+    if general:
+        Rg, tg = general_pose()
+        P = world_from_camera(P, Rg, tg).astype(np.float32)
+        normal = (normal.astype(np.float64) @ Rg).astype(np.float32)
     level = np.concatenate([km["octave"], r.integers(0, nlevels, extra)]).astype(np.int64)
     sf = scale ** np.arange(nlevels)
     dmax = dist * sf[level] * r.uniform(0.7, 1.3, n)
@@ -55,6 +76,11 @@ def make_case(km, dm, kf, df, w, h, seed, nlevels=8, scale=1.2, extra=300, th=1.
     skip = (r.random(n) < 0.05).astype(np.uint8)
     assigned = (r.random(len(kf)) < 0.05).astype(np.uint8)
     Rcw, tcw, Ow = pose(yaw=float(r.uniform(-0.004, 0.004)))
+    if general:     # the small motion after the general pose: Xc = Rs (Rg Xw + tg) + ts
+        Rs, ts = Rcw.reshape(3, 3).astype(np.float64), tcw.astype(np.float64)
+        R, t = Rs @ Rg, Rs @ tg + ts
+        Rcw, tcw = np.ascontiguousarray(R.astype(np.float32).reshape(-1)), t.astype(np.float32)
+        Ow = (-(R.T @ t)).astype(np.float32)
     F = ox.frame_view(kf, df, w, h, nlevels, scale)
     arrs = dict(F=F, kf=kf, df=df, Rcw=Rcw, tcw=tcw, Ow=Ow, cam=CAM.copy(), pos=np.ascontiguousarray(P),
                 normal=np.ascontiguousarray(normal), dist=mp_dist, skip=skip, desc=np.ascontiguousarray(desc),

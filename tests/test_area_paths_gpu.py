@@ -43,14 +43,17 @@ def ctx():
 
 def oracle_fns():
     L = load()
+    L.orbx_ref_search_local_map.argtypes = [ctypes.c_void_p]
     return {"window": L.orbx_ref_window_search, "pair": L.orbx_ref_search_by_projection_pair,
-            "motion": L.orbx_ref_search_by_projection_motion, "local": L.orbx_ref_search_by_projection_local}
+            "motion": L.orbx_ref_search_by_projection_motion, "local": L.orbx_ref_search_by_projection_local,
+            "local_map": L.orbx_ref_search_local_map}
 
 
 def gpu_fns():
     L = ox.lib()
     return {"window": L.orbx_window_search, "pair": L.orbx_search_by_projection_pair,
-            "motion": L.orbx_search_by_projection_motion, "local": L.orbx_search_by_projection_local}
+            "motion": L.orbx_search_by_projection_motion, "local": L.orbx_search_by_projection_local,
+            "local_map": L.orbx_search_local_map}
 
 
 def counters():
@@ -79,6 +82,31 @@ def test_area_search_equals_oracle(ctx, name, kind):
     assert delta == want, (delta, want)
     if name in NAMED:
         assert delta == NAMED[name]
+
+
+def posed_cases():
+    from test_area_paths_numpy import POSED, POSED_IDS
+    return dict(argvalues=POSED, ids=POSED_IDS)
+
+
+@pytest.mark.parametrize("name,kind,pose", **posed_cases())
+def test_area_search_under_a_general_pose(ctx, name, kind, pose):
+    """The small, tie and extras scenes of the three projection kinds from a
+    rotated and translated camera (the local-map kind through isInFrustum):
+    the oracle's matches, the construction's, and the unposed scene's rounds."""
+    from test_area_paths_numpy import posed_scene
+    s, m = posed_scene(name, kind, pose)
+    rc, om, on = A.search(s, oracle_fns())
+    assert rc == 0
+    before = counters()
+    rc, gm, gn = A.search(s, gpu_fns(), ctx.handle)
+    delta = tuple(int(v) for v in counters() - before)
+    assert rc == 0, ox.ERRORS.get(rc, rc)
+    print(f"{name}/{kind}/{pose}: matches {gn} (oracle {on}) rounds +{delta[0]} fallbacks +{delta[1]}")
+    assert gn == on and np.array_equal(gm, om)
+    for q, c in s.expect.items():
+        assert np.nonzero(gm == q)[0].tolist() == ([c] if c >= 0 else []), (q, c)
+    assert delta == ((0, 1) if m["fallback"] else (m["rounds"], 0))
 
 
 def test_track_frame_falls_back_inside_its_chain_of_kernels(ctx, ref):

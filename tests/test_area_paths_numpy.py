@@ -23,9 +23,30 @@ from test_proj_numpy import motion_search, pair_search
 
 
 def oracle_fns():
+    import ctypes
     L = load()
+    L.orbx_ref_search_local_map.argtypes = [ctypes.c_void_p]
     return {"window": L.orbx_ref_window_search, "pair": L.orbx_ref_search_by_projection_pair,
-            "motion": L.orbx_ref_search_by_projection_motion, "local": L.orbx_ref_search_by_projection_local}
+            "motion": L.orbx_ref_search_by_projection_motion, "local": L.orbx_ref_search_by_projection_local,
+            "local_map": L.orbx_ref_search_local_map}
+
+
+# general poses (pose_scenes.POSES) for the scenes that are run posed: the smallest chain scene, the ties
+# and the extras.  The posed local kind is another entry point than the unposed one: isInFrustum and the
+# search behind it (orbx_search_local_map), band 0 at predicted level 1; its id says so.
+POSED = [(name, kind, pose) for name in ("chain10x3", "ties", "extras") for kind in ("pair", "motion", "local")
+         for pose in ("y0.4", "axis0.9")]
+POSED_IDS = [f"{name}-{'local_map_via_frustum' if kind == 'local' else kind}-{pose}" for name, kind, pose in POSED]
+
+
+def posed_scene(name, kind, pose):
+    """The scene under a general pose and its own mirror, built once."""
+    import pose_scenes as ps
+    key = (name, kind, pose)
+    if key not in A._built:
+        s = A.scene(name, kind)[0].posed(*ps.POSES[pose])
+        A._built[key] = (s, A.mirror(s))
+    return A._built[key]
 
 
 def classes(m, ids):
@@ -131,6 +152,43 @@ def test_references_agree(name, kind):
         nm, nn = motion_search(s.k2, s.d2, s.k1, s.d1, s.xyz, s.valid, s.assigned, A.T_IDENTITY, s.th_motion,
                                s.check_ori)
     else:
+        return
+    assert nn == on and np.array_equal(nm, om)
+
+
+@pytest.mark.parametrize("name,kind,pose", POSED, ids=POSED_IDS)
+def test_references_agree_under_a_general_pose(name, kind, pose):
+    """The same scenes seen from a rotated and translated camera: every entry
+    of Rcw is used, and construction, oracle, mirror and numpy restatement
+    still agree."""
+    s, m = posed_scene(name, kind, pose)
+    base, bm = A.scene(name, kind)
+    R = s.T.reshape(3, 4)[:, :3]
+    assert (np.abs(R) > 1e-2).all() and all(abs(R[i, j] - R[j, i]) > 1e-2 for i in range(3) for j in range(i))
+    # every query still projects to its centre, so the lists are the unposed scene's
+    u, v, _ = s.centres()
+    if kind != "local":
+        assert np.abs(u - base.k1["x"]).max() < 1e-3 and np.abs(v - base.k1["y"]).max() < 1e-3
+    for a, b in zip(m["lists"], bm["lists"]):
+        assert (a is None) == (b is None) and (a is None or np.array_equal(a[0], b[0]))
+    assert s.expect == base.expect and (m["rounds"], m["fallback"]) == (bm["rounds"], bm["fallback"])
+    rc, om, on = A.search(s, oracle_fns())
+    assert rc == 0
+    for q, c in s.expect.items():
+        want = np.nonzero(om == q)[0].tolist()
+        assert want == ([c] if c >= 0 else []), (q, c, want)
+    assert sum(c >= 0 for c in s.expect.values()) >= 6
+    mm, mn = A.expected_matches(s, m["state"])
+    assert mn == on and np.array_equal(mm, om)
+    if kind == "pair":
+        nm, nn = pair_search(s.k1, s.d1, s.k2, s.d2, s.xyz, s.valid, s.assigned, s.T, A.R0, s.nnratio)
+    elif kind == "motion":
+        nm, nn = motion_search(s.k2, s.d2, s.k1, s.d1, s.xyz, s.valid, s.assigned, s.T, s.th_motion, s.check_ori)
+    else:
+        # isInFrustum saw every valid point, at its centre and at the level the scene asks for
+        in_view, proj, pred = s.frustum
+        assert np.array_equal(in_view != 0, s.valid != 0) and np.array_equal(pred[s.valid != 0], s.pred[s.valid != 0])
+        assert np.abs(proj[s.valid != 0] - s.proj[s.valid != 0]).max() < 1e-3
         return
     assert nn == on and np.array_equal(nm, om)
 

@@ -80,6 +80,32 @@ def test_dev_fuse_matches_oracle(slots, sim3, th, with_bounds):
     assert (bds[1] <= 50).sum() > 100   # the points fused back into their own keyframe
 
 
+@pytest.mark.parametrize("sim3", [0, 1])
+def test_dev_fuse_general_pose(slots, sim3):
+    """The device-resident form under proj_data.general_T(): slot 0's map
+    points, back-projected through a full rotation, fused into slot 1 and
+    back into slot 0.  On the CPU the oracle accepts (distance <= TH_LOW) 841
+    / 844 of them in slot 1 and all 1000 in slot 0; half of that is the floor."""
+    c, feats = slots
+    (k0, d0), (k1, d1) = feats[0], feats[1]
+    _, _, _, _, sdu, sdv = pd.keyframes()
+    Tg = pd.general_T()
+    T1 = pd.general_T([sdu * pd.Z0 / pd.CAM[0], sdv * pd.Z0 / pd.CAM[1], 0.0])
+    assert (np.abs(Tg[:3, :3]) > 1e-2).sum() == 8
+    mps = pd.mappoints(k0, d0, Tg, np.random.default_rng(7 + sim3))
+    Ts = [T1.copy(), Tg.copy()]
+    if sim3:
+        for T in Ts:
+            T[:3, :] *= np.float32(1.3)
+    r, bis, bds = dev_fuse(c, [1, 0], None, [mps[0], mps[0]], Ts, sim3, 5.0)
+    assert r == 0, r
+    for k, sl in enumerate([1, 0]):
+        kk, kd = feats[sl]
+        rb = ref_fuse(ox.frame_view(kk, kd, pd.W, pd.H), mps, Ts[k], sim3, 5.0)
+        assert np.array_equal(bis[k], rb[0]) and np.array_equal(bds[k], rb[1]), k
+    assert (bds[0] <= 50).sum() >= 420 and (bds[1] <= 50).sum() >= 500
+
+
 def test_dev_fuse_errors(slots):
     c, feats = slots
     k0, d0 = feats[0]

@@ -166,6 +166,46 @@ def test_oracle_in_frustum_matches_numpy(feats, seed):
     assert q.n_matches > 50
 
 
+# the oracle's count on the general-pose case is 272 matches of 819 points in view; half of it is the floor
+GENERAL_MATCHES_FLOOR = 136
+
+
+def test_oracle_general_pose_matches_numpy(feats):
+    """isInFrustum and the local-map search under local_map_data.
+    general_pose(): Rcw has eight non-zero entries, so a transposed index or
+    Ow = -R t for -R^T t changes what is in view."""
+    (km, dm), (kf, df) = feats
+    a, q = make_case(km, dm, kf, df, W, H, 1, general=True)
+    R = a["Rcw"].reshape(3, 3)
+    assert (np.abs(R) > 1e-4).sum() == 9 and (np.abs(R) > 1e-2).sum() == 8 and abs(R[1, 0]) > 0.05
+    assert np.abs(a["Ow"] + R @ a["tcw"]).max() > 0.1          # -R t is not the camera centre
+    assert ref_lib().orbx_ref_search_local_map(ctypes.byref(q)) == 0
+    want = numpy_in_frustum(a)
+    for m, w in enumerate(want):
+        assert bool(a["in_view"][m]) == (w is not None), m
+        if w is not None:
+            assert a["proj"][m][0] == w[0] and a["proj"][m][1] == w[1] and a["pred"][m] == w[2] and a["cos"][m] == w[3]
+    got, n = numpy_search_local(a, want, 1.0)
+    assert n == q.n_matches >= GENERAL_MATCHES_FLOOR
+    assert np.array_equal(got, a["matches"].astype(np.int64))
+    assert 100 < q.n_in_view < len(want) - int(a["skip"].sum()) - 50
+
+
+@pytest.mark.gpu
+def test_search_local_map_general_pose(feats):
+    """k_frustum and k_proj_local_jobs with a full Rcw, against the oracle."""
+    (km, dm), (kf, df) = feats
+    ra, rq = make_case(km, dm, kf, df, W, H, 1, general=True)
+    ga, gq = make_case(km, dm, kf, df, W, H, 1, general=True)
+    assert ref_lib().orbx_ref_search_local_map(ctypes.byref(rq)) == 0
+    ctx = ox.Context(nfeatures=100, max_w=64, max_h=64, slots=1)
+    assert ox.lib().orbx_search_local_map(ctx.handle, ctypes.byref(gq)) == 0
+    for r, g in zip(outputs(ra, rq), outputs(ga, gq)):
+        assert same(r, g)
+    assert gq.n_matches >= GENERAL_MATCHES_FLOOR
+    ctx.close()
+
+
 def empty_case(feats, seed, th, empty):
     """make_case, with no keypoints in the frame (empty "F") or no map points
     (empty "n_mp")."""

@@ -53,6 +53,18 @@ def pose(tx=-0.008, ty=-0.004, yaw=0.002):
     return np.array([[c, 0, s, tx], [0, 1, 0, ty], [-s, 0, c, 0.0]], np.float32).reshape(-1).copy()
 
 
+def general(xyz, T):
+    """The same camera-frame geometry through local_map_data.general_pose():
+    world points R^T (xyz - t) and the pose T composed with it, so the
+    kernels multiply by a full rotation matrix."""
+    from local_map_data import general_pose, world_from_camera
+    Rg, tg = general_pose()
+    S = T.reshape(3, 4).astype(np.float64)
+    Tg = np.concatenate([S[:, :3] @ Rg, (S[:, :3] @ tg + S[:, 3])[:, None]], 1)
+    return (np.ascontiguousarray(world_from_camera(xyz, Rg, tg).astype(np.float32)),
+            np.ascontiguousarray(Tg.astype(np.float32).reshape(-1)))
+
+
 def with_empty(cases, sides):
     """The cases under their usual ids with empty=None, then the first case
     once per side in `sides` with that side empty (no keypoints / no points)."""
@@ -172,6 +184,51 @@ def test_search_by_projection_pair(ctx, frames_feats, window, empty):
                                                    ox._ptr(valid), ox._ptr(assigned), ox._ptr(T), ox._ptr(CAM),
                                                    window, 0.9, ox._ptr(mg), ctypes.byref(ng)) == 0
     check_matches(mg, ng, mr, nr, empty)
+
+
+def test_search_by_projection_pair_general_pose(ctx, frames_feats):
+    """Window 50 under a general pose; the oracle finds 645 matches on the
+    CPU, half of it is the floor."""
+    (k1, d1), (k2, d2) = frames_feats[0], frames_feats[1]
+    F1, F2 = views(k1, d1, k2, d2)
+    rng = np.random.default_rng(50)
+    xyz = backproject(k1, rng)
+    valid = (rng.random(len(k1)) < 0.8).astype(np.uint8)
+    assigned = (rng.random(len(k2)) < 0.1).astype(np.uint8)
+    xyz, T = general(xyz, pose())
+    assert (np.abs(T.reshape(3, 4)[:, :3]) > 1e-2).sum() == 8
+    mr, mg = np.zeros(len(k2), np.int32), np.zeros(len(k2), np.int32)
+    nr, ng = ctypes.c_int(), ctypes.c_int()
+    assert load().orbx_ref_search_by_projection_pair(ctypes.byref(F1), ctypes.byref(F2), ptr(xyz), ptr(valid),
+                                                     ptr(assigned), ptr(T), ptr(CAM), 50, 0.9, ptr(mr),
+                                                     ctypes.byref(nr)) == 0
+    assert ox.lib().orbx_search_by_projection_pair(ctx.handle, ctypes.byref(F1), ctypes.byref(F2), ox._ptr(xyz),
+                                                   ox._ptr(valid), ox._ptr(assigned), ox._ptr(T), ox._ptr(CAM),
+                                                   50, 0.9, ox._ptr(mg), ctypes.byref(ng)) == 0
+    check_matches(mg, ng, mr, nr, None)
+    assert nr.value >= 322
+
+
+def test_search_by_projection_motion_general_pose(ctx, frames_feats):
+    """th 15 with the rotation filter under a general pose; the oracle finds
+    732 matches on the CPU, half of it is the floor."""
+    (kl, dl), (kc, dc) = frames_feats[1], frames_feats[2]
+    C, Lv = views(kc, dc, kl, dl)
+    rng = np.random.default_rng(15)
+    xyz = backproject(kl, rng)
+    valid = (rng.random(len(kl)) < 0.85).astype(np.uint8)
+    assigned = np.zeros(len(kc), np.uint8)
+    xyz, T = general(xyz, pose())
+    mr, mg = np.zeros(len(kc), np.int32), np.zeros(len(kc), np.int32)
+    nr, ng = ctypes.c_int(), ctypes.c_int()
+    assert load().orbx_ref_search_by_projection_motion(ctypes.byref(C), ctypes.byref(Lv), ptr(xyz), ptr(valid),
+                                                       ptr(assigned), ptr(T), ptr(CAM), 15.0, 1, ptr(mr),
+                                                       ctypes.byref(nr)) == 0
+    assert ox.lib().orbx_search_by_projection_motion(ctx.handle, ctypes.byref(C), ctypes.byref(Lv), ox._ptr(xyz),
+                                                     ox._ptr(valid), ox._ptr(assigned), ox._ptr(T), ox._ptr(CAM),
+                                                     15.0, 1, ox._ptr(mg), ctypes.byref(ng)) == 0
+    check_matches(mg, ng, mr, nr, None)
+    assert nr.value >= 366
 
 
 @pytest.mark.parametrize("th,ori,empty", with_empty([(15.0, True), (7.0, False), (40.0, True), (120.0, False),
