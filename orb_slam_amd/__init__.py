@@ -316,6 +316,8 @@ def _declare(L):
         "orbx_debug_lba_split": ([vp, i, i, i, i], i),
         "orbx_debug_describe_patch": ([vp, i, i, i, i, vp], i),
         "orbx_debug_level0_direct": ([vp], i),
+        "orbx_debug_fast_instance": ([vp, vp], i),
+        "orbx_debug_fast_lists": ([vp, i, vp, i, vp, i, vp], i),
         "orbx_pose_set_exact": ([vp, i], i),
         "orbx_pose_get_exact": ([vp], i),
         "orbx_dev_set_image_bounds": ([vp, vp], i),
@@ -557,6 +559,33 @@ class Context:
         if r < 0:
             raise OrbxError(r, "orbx_debug_level0_direct")
         return bool(r)
+
+    def fast_instance(self):
+        """The FAST kernel instance of the last extraction: (tile pitch, 0 for
+        the runtime-pitch instance; workgroup threads; band rows, 0 for whole
+        cells) (orbx_debug_fast_instance)."""
+        out = np.zeros(3, np.int32)
+        _check(lib().orbx_debug_fast_instance(self._h, _ptr(out)), "orbx_debug_fast_instance")
+        return tuple(int(v) for v in out)
+
+    def fast_lists(self, slot, cells_cap=1 << 14, lists_cap=1 << 22):
+        """FAST's output for a slot before retainBest (orbx_debug_fast_lists):
+        a list of (level, ini_x, ini_y, hx, hy, valid, corners) per cell,
+        corners an (n, 3) int array of (level x, level y, score) in raster
+        order."""
+        cells = np.zeros(10 * cells_cap, np.int32)
+        lists = np.zeros(lists_cap, np.uint32)
+        ne = ctypes.c_int(0)
+        n = lib().orbx_debug_fast_lists(self._h, slot, _ptr(cells), cells.size, _ptr(lists), lists.size,
+                                        ctypes.byref(ne))
+        _check(min(n, 0), "orbx_debug_fast_lists")
+        out = []
+        for level, ini_x, ini_y, hx, hy, valid, off, cap, cnt, _ in cells[:10 * n].reshape(n, 10):
+            assert 0 <= cnt <= cap and off + cnt <= ne.value, (cnt, cap, off, ne.value)
+            e = lists[off:off + cnt]
+            xy = np.stack([e & 0xFFF, (e >> 12) & 0xFFF, e >> 24], axis=1).astype(np.int64)
+            out.append((int(level), int(ini_x), int(ini_y), int(hx), int(hy), bool(valid), xy))
+        return out
 
     def timing(self, enable=True, only=None):
         """Kernel timing with hipEvents around every launch, or only around

@@ -39,7 +39,7 @@ __constant__ __attribute__((aligned(4))) int8_t c_pattern[256][4] = {
 };
 
 #ifdef ORBX_FAST_PROFILE
-__device__ unsigned long long g_fast_prof[16];
+__device__ unsigned long long g_fast_prof[24];
 __device__ inline unsigned long long fp_stamp()
 {
     unsigned long long t;
@@ -56,7 +56,7 @@ __device__ inline unsigned long long fp_stamp()
 #define FP_ADD(k, v) atomicAdd(&g_fast_prof[k], (unsigned long long)(v))
 extern "C" int orbx_debug_fast_prof(unsigned long long* out)
 {
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fast_prof), sizeof(unsigned long long) * 16) == hipSuccess ? 0 : -2;
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fast_prof), sizeof(unsigned long long) * 24) == hipSuccess ? 0 : -2;
 }
 #else
 #define FP_T0()
@@ -139,31 +139,6 @@ __device__ __forceinline__ T cget(const T* p, int i)
 
 __device__ inline uint8_t sat_u8(int v) { return (uint8_t)min(max(v, 0), 255); }
 __device__ inline int sat_s16(int v) { return min(max(v, -32768), 32767); }
-
-// (row, column) walk of a row-major index advancing by a fixed stride,
-// without a division per step.
-struct RowWalk {
-    int r, q, dr, dq, nq;
-    __device__ RowWalk(int start, int stride, int n_q) : nq(n_q)
-    {
-        // callers never pass n_q == 0 (integer division by zero is undefined
-        // behaviour, which the compiler may assume away)
-        r = start / n_q;
-        q = start - r * n_q;
-        dr = stride / n_q;
-        dq = stride - dr * n_q;
-    }
-    __device__ void next()
-    {
-        r += dr;
-        q += dq;
-        if (q >= nq) {
-            q -= nq;
-            r++;
-        }
-    }
-};
-
 
 // Copy n items into LDS, kBatch per thread per round: the loads are
 // unconditional (index clamped to n - 1, whose entry out-of-range lanes
@@ -893,14 +868,26 @@ __global__ __launch_bounds__(T) void k_pyr_cascade(ExtractArgs a, const int4* pl
 // exactly S (OpenCV 2.4 fast.cpp / fast_score.cpp).  A pixel whose compass
 // pre-test passes in one direction only has S = that direction's arc - 1.
 // ---------------------------------------------------------------------------
-// Two candidates per lane (a, b) on packed fp16 halves: the 8-bit pixels
-// become the exact fp16 integers 1024 + p (bits 0x6400 | p), so the ring
-// differences d_k = v - p_k (|d| <= 255) are exact in fp16 and the 3-way
+// Two candidates per lane (a, b) on packed fp16 halves: the 8-bit pixels are
+// used as they are loaded, as the fp16 subnormals p * 2^-24 (bits 0x00pp;
+// the kernels run with fp16 denormals on, the compiler's default for this
+// target).  Every quantity below is k * 2^-24 with |k| <= 255, so the ring
+// differences d_k = v - p_k, their minima and maxima are exact and the 3-way
 // windows are single v_pk_minimum3_f16 / v_pk_maximum3_f16 instructions
-// (gfx950) for both candidates.  Returns max(dark, bright) (= S + 1) per
-// candidate.
+// (gfx950) for both candidates.  Returns r = max(dark, -bright) as bits, low
+// half candidate a, high half b: a non-negative half is the integer S + 1;
+// a half with its sign bit set (a negative int16) is a pixel with S < 0.
+//
+// The (a, b) pairs are packed by one v_lshl_or_b32 per ring point (two
+// ds_read_u8): gfx950's 16-bit-half LDS loads clear the other half of the
+// register, so they cannot assemble a pair.
+//
+// Arc reduction as OpenCV's cornerScore pairs it: with W_k = min d[k .. k+8]
+// and, for even k, A_k = min d[k+1 .. k+8] (four pair minima q_j = min(d[2j+1],
+// d[2j+2])), max(W_k, W_k+1) = min(A_k, max(d[k], d[k+9])): 8 + 8 + 8 + 8
+// packed instructions and a 4-instruction max tree per polarity, the same
+// max-of-min value as the 16 windows one by one.
 typedef _Float16 orbx_h2 __attribute__((ext_vector_type(2)));
-typedef unsigned short orbx_u16x2 __attribute__((ext_vector_type(2)));
 __device__ inline orbx_h2 h2_min3(orbx_h2 a, orbx_h2 b, orbx_h2 c)
 {
     return __builtin_elementwise_minimum(__builtin_elementwise_minimum(a, b), c);
@@ -909,7 +896,7 @@ __device__ inline orbx_h2 h2_max3(orbx_h2 a, orbx_h2 b, orbx_h2 c)
 {
     return __builtin_elementwise_maximum(__builtin_elementwise_maximum(a, b), c);
 }
-__device__ inline void fast_arc2(const uint8_t* t, int pa, int pb, int pitch, int& Sa, int& Sb)
+__device__ inline uint32_t fast_arc2(const uint8_t* t, int pa, int pb, int pitch)
 {
     const int off[16] = {3 * pitch,      1 + 3 * pitch, 2 + 2 * pitch,  3 + pitch,
                          3,              3 - pitch,     2 - 2 * pitch,  1 - 3 * pitch,
@@ -922,45 +909,37 @@ __device__ inline void fast_arc2(const uint8_t* t, int pa, int pb, int pitch, in
     asm("" : "+v"(ba), "+v"(bb));   // opaque: keeps the constant offsets out of the bases
     const uint8_t* ta = t + ba;
     const uint8_t* tb = t + bb;
-    // (a, b) byte pairs assembled as 16-bit halves (ds_read_u8_d16 /
-    // _d16_hi), then the fp16 exponent bits
-    auto pair = [&](int k) {
-        orbx_u16x2 pv;
-        pv.x = ta[k];
-        pv.y = tb[k];
-        return __builtin_bit_cast(uint32_t, pv) | 0x64006400u;
-    };
-    const orbx_h2 v = __builtin_bit_cast(orbx_h2, pair(o));
+    auto pair = [&](int k) { return __builtin_bit_cast(orbx_h2, (uint32_t)ta[k] | ((uint32_t)tb[k] << 16)); };
+    const orbx_h2 v = pair(o);
     orbx_h2 d[16];
 #pragma unroll
-    for (int k = 0; k < 16; k++) {
-        const uint32_t w = pair(off[k] + o);
-        d[k] = v - __builtin_bit_cast(orbx_h2, w);
-    }
-    orbx_h2 lo3[16], hi3[16];
+    for (int k = 0; k < 16; k++) d[k] = v - pair(off[k] + o);
+    orbx_h2 qn[8], qx[8];
 #pragma unroll
-    for (int k = 0; k < 16; k++) {
-        lo3[k] = h2_min3(d[k], d[(k + 1) & 15], d[(k + 2) & 15]);
-        hi3[k] = h2_max3(d[k], d[(k + 1) & 15], d[(k + 2) & 15]);
+    for (int j = 0; j < 8; j++) {
+        qn[j] = __builtin_elementwise_minimum(d[2 * j + 1], d[(2 * j + 2) & 15]);
+        qx[j] = __builtin_elementwise_maximum(d[2 * j + 1], d[(2 * j + 2) & 15]);
     }
-    orbx_h2 m9[16], x9[16];
+    // m[j] = max(W_2j, W_2j+1); x[j] the same for the bright arcs (min of the
+    // 9-arc maxima)
+    orbx_h2 m[8], x[8];
 #pragma unroll
-    for (int k = 0; k < 16; k++) {
-        m9[k] = h2_min3(lo3[k], lo3[(k + 3) & 15], lo3[(k + 6) & 15]);
-        x9[k] = h2_max3(hi3[k], hi3[(k + 3) & 15], hi3[(k + 6) & 15]);
+    for (int j = 0; j < 8; j++) {
+        const orbx_h2 e0 = d[2 * j], e9 = d[(2 * j + 9) & 15];
+        m[j] = h2_min3(h2_min3(qn[j], qn[(j + 1) & 7], qn[(j + 2) & 7]), qn[(j + 3) & 7],
+                       __builtin_elementwise_maximum(e0, e9));
+        x[j] = h2_max3(h2_max3(qx[j], qx[(j + 1) & 7], qx[(j + 2) & 7]), qx[(j + 3) & 7],
+                       __builtin_elementwise_minimum(e0, e9));
     }
-    // dark = max_k m9[k], bright = min_k x9[k] (3-way trees)
-    orbx_h2 dk = h2_max3(m9[0], m9[1], m9[2]), br = h2_min3(x9[0], x9[1], x9[2]);
-#pragma unroll
-    for (int k = 3; k < 15; k += 2) {
-        dk = h2_max3(dk, m9[k], m9[k + 1]);
-        br = h2_min3(br, x9[k], x9[k + 1]);
-    }
-    dk = __builtin_elementwise_maximum(dk, m9[15]);
-    br = __builtin_elementwise_minimum(br, x9[15]);
-    const orbx_h2 r = __builtin_elementwise_maximum(dk, -br);
-    Sa = (int)(float)r.x;
-    Sb = (int)(float)r.y;
+    // dark = max_j m[j], bright = min_j x[j] (3-way trees)
+    orbx_h2 dk = h2_max3(m[0], m[1], m[2]), br = h2_min3(x[0], x[1], x[2]);
+    dk = h2_max3(dk, m[3], m[4]);
+    br = h2_min3(br, x[3], x[4]);
+    dk = h2_max3(dk, m[5], m[6]);
+    br = h2_min3(br, x[5], x[6]);
+    dk = __builtin_elementwise_maximum(dk, m[7]);
+    br = __builtin_elementwise_minimum(br, x[7]);
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_maximum(dk, -br));
 }
 
 // One workgroup per (cell, frame).  LDS (dynamic): the cell ROI with
@@ -1032,7 +1011,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(kThrea
     // Per-wave queue of compass survivors (tile positions): u16 for the
     // templated pitches (the host sends tiles over 64 KB to kP = 0), u32 for
     // kP = 0.  Linear, not a ring: after each scoring round the < 128 left
-    // over move to the front, so an iteration's <= 256 new entries always fit.
+    // over move to the front, so an iteration's <= 256 new entries always fit
+    // (a wave's partial last iteration is not followed by a scoring round:
+    // up to 127 + 252 entries are left for the pooled pass).
     using QEntry = typename std::conditional<kP != 0, uint16_t, uint32_t>::type;
     constexpr int kQueue = 128 + 256;
     constexpr int kQueueWords = kWaves * kQueue * (int)sizeof(QEntry) / 4;
@@ -1115,26 +1096,24 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(kThrea
     // degenerate cell of a tiny level, where c_hi < c_lo and, with a large
     // alignment shift, (c_hi >> 2) - q0 + 1 would go negative)
     const int q0 = c_lo >> 2, nqe = c_hi >= c_lo ? (c_hi >> 2) - q0 + 1 : 0;
-    const int q_last = q0 + nqe - 1;
-    const int j_lo = c_lo & 3, j_hi = c_hi & 3;           // pixels j >= j_lo of dword q0, j <= j_hi of q_last
+    // pixels j >= j_lo of dword q0, j <= j_hi of the last dword q_last = q0 + nqe - 1
+    const int j_lo = c_lo & 3, j_hi = c_hi & 3;
     const uint32_t k64 = 0x64646464u;
     // S' map at threshold tmin over the window rows [sr0, sr0 + nrows):
     // S' = S where S >= tmin, else 0
     auto score_pass = [&](const int tmin, const int sr0, const int nrows) {
         const int nunits = max(nrows, 0) * nqe;
         // no interior dwords (a degenerate cell of a tiny level): nothing to
-        // score, and RowWalk must not divide by nqe == 0
+        // score, and the row walk below must not divide by nqe == 0
         if (nunits <= 0) return;
         // per-wave queue cand[0, qt) of compass survivors, scored 128 at a
         // time (two per lane) with every lane busy
-        int qt = 0;
         auto set_nz = [&](int p) { atomicOr(&nz[p >> 7], 1u << ((p >> 2) & 31)); };
         auto score_pair = [&](int pa, int pb, bool has_a, bool has_b) {
             if (!has_a) return;
-            int Sa, Sb;
-            fast_arc2(tile, pa, pb, P, Sa, Sb);
-            Sa -= 1;
-            Sb -= 1;
+            // S + 1 from the bit pattern (a set sign bit: a negative int16)
+            const uint32_t rb = fast_arc2(tile, pa, pb, P);
+            const int Sa = (int)(int16_t)rb - 1, Sb = ((int32_t)rb >> 16) - 1;
             if (Sa >= tmin) {
                 sm[pa] = (uint8_t)Sa;
                 set_nz(pa);
@@ -1149,88 +1128,159 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(kThrea
         // on the fp16 integers 1024 + p; the sign bit of the difference
         // is clear exactly when the test passes)
         const orbx_h2 T1 = {(_Float16)(tmin + 1), (_Float16)(tmin + 1)};
-        RowWalk cw_(wv * 64 + lane, kBlock, nqe);
-        for (int u0 = wv * 64; u0 < nunits; u0 += kBlock, cw_.next()) {
-            const int u = u0 + lane;
-            const int r = sr0 + cw_.r, q = q0 + cw_.q;
+        // Pixel j of dword q0 lies outside the interior columns when j < j_lo,
+        // of dword q_last when j > j_hi: uniform all-or-nothing masks, AND-ed
+        // with the lane masks of the two dwords.
+        // (opaque scalar pairs: else each use is rebuilt as a compare and
+        // two selects inside the loop)
+        auto cut_mask = [](bool c) {
+            const uint32_t m = __builtin_amdgcn_readfirstlane(c ? ~0u : 0u);
+            uint64_t r = ((uint64_t)m << 32) | m;
+            asm("" : "+s"(r));
+            return r;
+        };
+        const uint64_t cutA0 = cut_mask(j_lo > 0), cutA1 = cut_mask(j_lo > 1), cutA2 = cut_mask(j_lo > 2);
+        const uint64_t cutB1 = cut_mask(j_hi < 1), cutB2 = cut_mask(j_hi < 2), cutB3 = cut_mask(j_hi < 3);
+        // the wave's queue as a uniform LDS byte address, and the address of
+        // its end (cand[qt]), which the loop keeps in place of qt
+        typedef __attribute__((address_space(3))) QEntry LdsEntry;
+        const uint32_t cand_lds = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(LdsEntry*)cand);
+        constexpr int kEsh = sizeof(QEntry) == 2 ? 1 : 2;   // log2 of an entry's bytes
+        uint32_t qe = cand_lds;
+        // One compass unit per lane: the tile dword at byte offset `pos` (4
+        // pixels), whose interior dword number in its row is qr (0 .. nqe - 1).
+        // Survivors of the lanes in `live` are appended to the queue in
+        // plane-major order.
+        auto compass = [&](const int pos, const int qr, const uint64_t live) {
+            const uint32_t* row = reinterpret_cast<const uint32_t*>(tile + pos);
+            const uint32_t mid = row[0];
+            // row[-1] / row[1] past the row ends are the neighbouring rows'
+            // dwords (an interior row): only pixels outside the interior
+            // columns read them, and those are masked below
+            const uint32_t lo = row[-1], hi = row[1];
+            const uint32_t up = row[-3 * nq], dn = row[3 * nq];
+            // 4 pixels at once: even / odd bytes as two packed fp16 halves
+            const uint32_t p4w = __builtin_amdgcn_alignbyte(hi, mid, 3);    // bytes j+3
+            const uint32_t p12w = __builtin_amdgcn_alignbyte(mid, lo, 1);   // bytes j-3
             // per pixel j: the sign bit of x_j = max(v - A, B - v) - tmin - 1
             // is set where the pixel fails (even half: j = 0, 2; odd: 1, 3)
-            uint32_t xw0 = 0xBC00BC00u, xw1 = 0xBC00BC00u;   // -1.0: fails both tests (not -0)
-            if (u < nunits) {
-                const uint32_t* row = tile32 + r * nq + q;
-                const uint32_t mid = row[0];
-                // row[-1] / row[1] past the row ends are the neighbouring rows'
-                // dwords (r is an interior row): only pixels outside the
-                // interior columns read them, and those are masked below
-                const uint32_t lo = row[-1], hi = row[1];
-                const uint32_t up = row[-3 * nq], dn = row[3 * nq];
-                // 4 pixels at once: even / odd bytes as two packed fp16 halves
-                const uint32_t p4w = __builtin_amdgcn_alignbyte(hi, mid, 3);    // bytes j+3
-                const uint32_t p12w = __builtin_amdgcn_alignbyte(mid, lo, 1);   // bytes j-3
-                uint32_t xw[2];
+            uint32_t xw[2];
 #pragma unroll
-                for (int hf = 0; hf < 2; hf++) {
-                    const uint32_t sel = hf ? 0x04030401u : 0x04020400u;   // bytes 1,3 or 0,2 | 0x64
-                    const orbx_h2 v = h2_bytes(mid, k64, sel);
-                    // compass points in ring order 0, 4, 8, 12
-                    const orbx_h2 p0 = h2_bytes(dn, k64, sel), p4 = h2_bytes(p4w, k64, sel);
-                    const orbx_h2 p8 = h2_bytes(up, k64, sel), p12 = h2_bytes(p12w, k64, sel);
-                    // IEEE maximum / minimum: no canonicalising moves (the
-                    // operands are finite).  A = min over the adjacent pairs
-                    // (0,4), (4,8), (8,12), (12,0) of the pair maximum; by
-                    // distributivity min(max(a, x), max(b, x)) = max(x, min(a, b))
-                    // that is max(min(p4, p12), min(p0, p8)); likewise
-                    // B = max over the pairs of the pair minimum
-                    // = min(max(p4, p12), max(p0, p8)).
-                    const orbx_h2 A = __builtin_elementwise_maximum(__builtin_elementwise_minimum(p4, p12),
-                                                                    __builtin_elementwise_minimum(p0, p8));
-                    const orbx_h2 B = __builtin_elementwise_minimum(__builtin_elementwise_maximum(p4, p12),
-                                                                    __builtin_elementwise_maximum(p0, p8));
-                    const orbx_h2 x = __builtin_elementwise_maximum(v - A, B - v) - T1;
-                    xw[hf] = __builtin_bit_cast(uint32_t, x);
-                }
-                xw0 = xw[0];
-                xw1 = xw[1];
+            for (int hf = 0; hf < 2; hf++) {
+                const uint32_t sel = hf ? 0x04030401u : 0x04020400u;   // bytes 1,3 or 0,2 | 0x64
+                const orbx_h2 v = h2_bytes(mid, k64, sel);
+                // compass points in ring order 0, 4, 8, 12
+                const orbx_h2 p0 = h2_bytes(dn, k64, sel), p4 = h2_bytes(p4w, k64, sel);
+                const orbx_h2 p8 = h2_bytes(up, k64, sel), p12 = h2_bytes(p12w, k64, sel);
+                // IEEE maximum / minimum: no canonicalising moves (the
+                // operands are finite).  A = min over the adjacent pairs
+                // (0,4), (4,8), (8,12), (12,0) of the pair maximum; by
+                // distributivity min(max(a, x), max(b, x)) = max(x, min(a, b))
+                // that is max(min(p4, p12), min(p0, p8)); likewise
+                // B = max over the pairs of the pair minimum
+                // = min(max(p4, p12), max(p0, p8)).
+                const orbx_h2 A = __builtin_elementwise_maximum(__builtin_elementwise_minimum(p4, p12),
+                                                                __builtin_elementwise_minimum(p0, p8));
+                const orbx_h2 B = __builtin_elementwise_minimum(__builtin_elementwise_maximum(p4, p12),
+                                                                __builtin_elementwise_maximum(p0, p8));
+                const orbx_h2 x = __builtin_elementwise_maximum(v - A, B - v) - T1;
+                xw[hf] = __builtin_bit_cast(uint32_t, x);
             }
-            // pass flags as lane masks (bit 15 / 31 clear: a 16-bit and a
-            // 32-bit signed compare each); the partial dwords q0 and q_last
-            // drop the pixels outside the interior columns (uniform j tests;
-            // bitwise on the lane masks, no short-circuit branches)
-            const bool at_q0 = q == q0, at_ql = q == q_last;
-            const bool cut0 = at_q0 & (j_lo > 0), cut1 = (at_q0 & (j_lo > 1)) | (at_ql & (j_hi < 1));
-            const bool cut2 = (at_q0 & (j_lo > 2)) | (at_ql & (j_hi < 2)), cut3 = at_ql & (j_hi < 3);
-            // (low halves as fp16 >= 0: no -0 or NaN arises from these exact
-            // integer differences)
-            const bool ok0 = (__builtin_bit_cast(orbx_h2, xw0).x >= (_Float16)0) & !cut0;
-            const bool ok1 = (__builtin_bit_cast(orbx_h2, xw1).x >= (_Float16)0) & !cut1;
-            const bool ok2 = ((int32_t)xw0 >= 0) & !cut2, ok3 = ((int32_t)xw1 >= 0) & !cut3;
-            const uint64_t b0 = __builtin_amdgcn_ballot_w64(ok0), b1 = __builtin_amdgcn_ballot_w64(ok1);
-            const uint64_t b2 = __builtin_amdgcn_ballot_w64(ok2), b3 = __builtin_amdgcn_ballot_w64(ok3);
-            const int n0 = __popcll(b0), n1 = __popcll(b1), n2 = __popcll(b2);
-            const int ntot = n0 + n1 + n2 + __popcll(b3);
+            // pass flags as lane masks straight from the compares (bit 15 /
+            // 31 clear: a 16-bit and a 32-bit signed compare each; low halves
+            // as fp16 >= 0: no -0 or NaN arises from these exact integer
+            // differences); the cuts and `live` are 64-bit scalar operations
+            const uint64_t at0 = __builtin_amdgcn_ballot_w64(qr == 0), atl = __builtin_amdgcn_ballot_w64(qr == nqe - 1);
+            const uint64_t b0 = __builtin_amdgcn_ballot_w64(__builtin_bit_cast(orbx_h2, xw[0]).x >= (_Float16)0) &
+                                ~(at0 & cutA0) & live;
+            const uint64_t b1 = __builtin_amdgcn_ballot_w64(__builtin_bit_cast(orbx_h2, xw[1]).x >= (_Float16)0) &
+                                ~((at0 & cutA1) | (atl & cutB1)) & live;
+            const uint64_t b2 = __builtin_amdgcn_ballot_w64((int32_t)xw[0] >= 0) & ~((at0 & cutA2) | (atl & cutB2)) & live;
+            const uint64_t b3 = __builtin_amdgcn_ballot_w64((int32_t)xw[1] >= 0) & ~(atl & cutB3) & live;
+            const int n0 = __popcll(b0), n1 = __popcll(b1), n2 = __popcll(b2), n3 = __popcll(b3);
+            // plane-major order: each plane's survivors at their lane rank
+            // after the earlier planes'; the plane's start is part of the
+            // scalar base of the address (opaque: the compiler would move it
+            // into a vector add per plane)
+            auto slot = [&](uint64_t bm, uint32_t base) {
+                asm("" : "+s"(base));
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(bm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm, 0u));
+                return (rank << kEsh) + base;
+            };
+            const uint32_t s1 = qe + ((uint32_t)n0 << kEsh), s2 = s1 + ((uint32_t)n1 << kEsh);
+            const uint32_t s3 = s2 + ((uint32_t)n2 << kEsh);
+            const uint32_t a0 = slot(b0, qe), a1 = slot(b1, s1), a2 = slot(b2, s2), a3 = slot(b3, s3);
+            const uint32_t e0 = (uint32_t)pos, e1 = e0 | 1u, e2 = e0 | 2u, e3 = e0 | 3u;
+            // the four stores under their planes' lane masks, with one save
+            // and one restore of exec (as `if (pass_j) queue[slot_j] = e_j`
+            // the compiler wraps each store in an exec region with a branch).
+            // LDS operations of a wave complete in order, so the queue reads
+            // below see these stores; the compiler's lgkmcnt waits do not
+            // count them, which only makes a later wait conservative.
+            uint64_t saved;
+            if constexpr (sizeof(QEntry) == 2)
+                asm volatile("s_mov_b64 %0, exec\n\t"
+                             "s_mov_b64 exec, %1\n\tds_write_b16 %5, %9\n\t"
+                             "s_mov_b64 exec, %2\n\tds_write_b16 %6, %10\n\t"
+                             "s_mov_b64 exec, %3\n\tds_write_b16 %7, %11\n\t"
+                             "s_mov_b64 exec, %4\n\tds_write_b16 %8, %12\n\t"
+                             "s_mov_b64 exec, %0"
+                             : "=&s"(saved)
+                             : "s"(b0), "s"(b1), "s"(b2), "s"(b3), "v"(a0), "v"(a1), "v"(a2), "v"(a3), "v"(e0), "v"(e1),
+                               "v"(e2), "v"(e3)
+                             : "memory");
+            else
+                asm volatile("s_mov_b64 %0, exec\n\t"
+                             "s_mov_b64 exec, %1\n\tds_write_b32 %5, %9\n\t"
+                             "s_mov_b64 exec, %2\n\tds_write_b32 %6, %10\n\t"
+                             "s_mov_b64 exec, %3\n\tds_write_b32 %7, %11\n\t"
+                             "s_mov_b64 exec, %4\n\tds_write_b32 %8, %12\n\t"
+                             "s_mov_b64 exec, %0"
+                             : "=&s"(saved)
+                             : "s"(b0), "s"(b1), "s"(b2), "s"(b3), "v"(a0), "v"(a1), "v"(a2), "v"(a3), "v"(e0), "v"(e1),
+                               "v"(e2), "v"(e3)
+                             : "memory");
+            qe = __builtin_amdgcn_readfirstlane(s3 + ((uint32_t)n3 << kEsh));   // wave-uniform
 #ifdef ORBX_FAST_PROFILE
-            if (lane == 0) FP_ADD(10 + (tmin < 10), ntot);
+            if (lane == 0) FP_ADD(10 + (tmin < 10), n0 + n1 + n2 + n3);
             if (lane == 0) FP_ADD(12, 1);
 #endif
-            // plane-major order: each plane's survivors at their lane rank
-            // (mbcnt, which adds the plane's start) after the earlier planes'
-            const int pbase = r * P + 4 * q;
-            auto slot = [&](uint64_t bm, int start) {
-                return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bm >> 32),
-                                                      __builtin_amdgcn_mbcnt_lo((uint32_t)bm, (uint32_t)start));
-            };
-            if (ok0) cand[slot(b0, qt)] = (QEntry)pbase;
-            if (ok1) cand[slot(b1, qt + n0)] = (QEntry)(pbase + 1);
-            if (ok2) cand[slot(b2, qt + n0 + n1)] = (QEntry)(pbase + 2);
-            if (ok3) cand[slot(b3, qt + n0 + n1 + n2)] = (QEntry)(pbase + 3);
-            qt = __builtin_amdgcn_readfirstlane(qt + ntot);   // wave-uniform
-            if (qt >= 128) {   // uniform: score full batches, move the rest to the front
+        };
+        // The lane's unit u = u0 + lane as (tile dword, dword number in its
+        // row), kept incrementally: a step of kBlock units is dr rows and dq
+        // dwords, with at most one wrap into the next row (dq < nqe).  nqe
+        // ranges from 1 (dq = 0: never wraps) to more than kBlock (dr = 0).
+        const int wvu = __builtin_amdgcn_readfirstlane(wv);   // the loop count is wave-uniform
+        const int start = wvu * 64 + lane, row0 = start / nqe;
+        uint32_t qr = start - row0 * nqe;
+        int pos = 4 * ((sr0 + row0) * nq + q0 + (int)qr);
+        const int dr = kBlock / nqe, dq = kBlock - dr * nqe;
+        const int step = 4 * (dr * nq + dq);
+        int wrap_pos = 4 * (nq - nqe);
+        asm("" : "+v"(wrap_pos));   // a register operand of the select below
+        int u0 = wvu * 64;
+        // full iterations (every lane has a unit), then at most one partial
+        // one, the wave's last
+        for (; u0 + 64 <= nunits; u0 += kBlock) {
+            compass(pos, (int)qr, ~0ull);
+            // qr + dq < 2 nqe: where it reaches nqe the unsigned minimum picks
+            // the wrapped value (else qr - nqe is huge)
+            qr += dq;
+            const uint32_t qw = qr - (uint32_t)nqe;
+            pos += step + ((int32_t)qw >= 0 ? wrap_pos : 0);
+            qr = min(qr, qw);
+            if (qe - cand_lds >= (128u << kEsh)) {   // uniform: score full batches, move the rest to the front
+                const int qt = (int)((qe - cand_lds) >> kEsh);
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                 int qh = 0;
-                for (; qt - qh >= 128; qh += 128)
+                for (; qt - qh >= 128; qh += 128) {
+#ifdef ORBX_FAST_PROFILE
+                    if (lane == 0) FP_ADD(13, 1);
+#endif
                     score_pair(cand[qh + lane], cand[qh + 64 + lane], true, true);
+                }
                 const int rest = qt - qh;   // < 128
                 const QEntry e0 = lane < rest ? cand[qh + lane] : (QEntry)0;
                 const QEntry e1 = lane + 64 < rest ? cand[qh + 64 + lane] : (QEntry)0;
@@ -1239,16 +1289,24 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(kThrea
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                 if (lane < rest) cand[lane] = e0;
                 if (lane + 64 < rest) cand[lane + 64] = e1;
-                qt = __builtin_amdgcn_readfirstlane(rest);
+                qe = cand_lds + ((uint32_t)__builtin_amdgcn_readfirstlane(rest) << kEsh);
             }
             // no fence here: the next iteration appends at >= qt (the moved
             // rest lies below it), and the queue is read only after the
             // fence above
         }
-        // the waves' leftovers (< 128 each) scored together, in full batches
+        if (u0 < nunits) {
+            // lanes past the last unit read lane 0's dwords (inside the tile)
+            // and append nothing; the queue then holds < 128 + 256 entries,
+            // all scored with the leftovers below
+            const int rem = nunits - u0;   // 1 .. 63
+            const int pos0 = __builtin_amdgcn_readfirstlane(pos);
+            compass(lane < rem ? pos : pos0, (int)qr, (1ull << rem) - 1);
+        }
+        // the waves' leftovers (< kQueue each) scored together, in full batches
         // of 128 where they add up (one partly filled batch per wave would
         // run the whole scoring code for a few pixels)
-        if (lane == 0) s_left[wv] = qt;
+        if (lane == 0) s_left[wv] = (int)((qe - cand_lds) >> kEsh);
         __syncthreads();
         int pre[kWaves + 1];
         pre[0] = 0;
@@ -1263,6 +1321,10 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(kThrea
         };
         for (int b0 = wv * 128; b0 < T; b0 += kWaves * 128) {
             const int ga = b0 + lane, gb = b0 + 64 + lane;
+#ifdef ORBX_FAST_PROFILE
+            if (lane == 0) FP_ADD(14, 1);
+            if (lane == 0) FP_ADD(15, min(128, T - b0));
+#endif
             score_pair(ga < T ? entry(ga) : 0, gb < T ? entry(gb) : 0, ga < T, gb < T);
         }
     };
@@ -1334,6 +1396,10 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(kThrea
             }
             __syncthreads();
             const int n = min(total - base, kUnitCap);
+#ifdef ORBX_FAST_PROFILE
+            if (tid == 0) FP_ADD(16, n);
+            if (tid == 0) FP_ADD(17, (n + kBlock - 1) / kBlock);
+#endif
             for (int i = tid; i < n; i += kBlock) nms_unit((int)ulist[i]);
         }
         return c1;
@@ -1348,6 +1414,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(kThrea
         const int per = (nkw + kBlock - 1) / kBlock;
         const int ka = min(tid * per, nkw), kb = min(ka + per, nkw);
         const bool all_kept = t == tmin;
+#ifdef ORBX_FAST_PROFILE
+        if (tid == 0) FP_ADD(18, per);
+#endif
         int cnt = 0;
         for (int k = ka; k < kb; k++) {
             uint32_t b = kept[k];
@@ -2483,6 +2552,47 @@ extern "C" int orbx_debug_level0_direct(orbx_ctx* ctx)
     return ctx->last_l0_direct ? 1 : 0;
 }
 
+/* Diagnostics (not in include/orbx.h): the k_fast_cells instance that the last
+ * extraction launched on the context: out[0] the compile-time tile pitch (0:
+ * the runtime-pitch instance), out[1] the workgroup's threads, out[2] the band
+ * rows (0: whole cells).  ORBX_ERR_ARG before the first extraction. */
+extern "C" int orbx_debug_fast_instance(orbx_ctx* ctx, int* out)
+{
+    if (!ctx || !out || ctx->last_fast[0] < 0) return ORBX_ERR_ARG;
+    for (int k = 0; k < 3; k++) out[k] = ctx->last_fast[k];
+    return ORBX_OK;
+}
+
+/* Diagnostics (not in include/orbx.h): FAST's output for slot `slot` of the
+ * last extraction, before retainBest: per cell 10 ints in `cells` (level,
+ * ini_x, ini_y, hx, hy, valid, list offset, list capacity, corner count, 0)
+ * and the slot's corner arena in `lists` (entry: S << 24 | level y << 12 |
+ * level x, each cell's corners in raster order from its list offset).
+ * Returns the number of cells; *entries gets the arena's length. */
+extern "C" int orbx_debug_fast_lists(orbx_ctx* ctx, int slot, int32_t* cells, int cells_cap, uint32_t* lists,
+                                     int lists_cap, int* entries)
+{
+    using namespace orbx;
+    if (!ctx || !cells || !lists || !entries || slot < 0 || slot >= ctx->slots) return ORBX_ERR_ARG;
+    ctx_enter(ctx);
+    const Geometry& g = ctx->geom;
+    const int n = (int)g.cells.size();
+    if (cells_cap < 10 * n || lists_cap < g.list_entries) return ORBX_ERR_CAPACITY;
+    std::vector<int32_t> cnt(n);
+    if (hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(cnt.data(), ctx->cell_count + (size_t)slot * n, 4 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(lists, ctx->cell_lists + (size_t)slot * g.list_entries, 4 * (size_t)g.list_entries,
+                  hipMemcpyDeviceToHost) != hipSuccess)
+        return ORBX_ERR_HIP;
+    for (int c = 0; c < n; c++) {
+        const CellGeom& C = g.cells[c];
+        const int32_t v[10] = {C.level, C.ini_x, C.ini_y, C.hx, C.hy, C.valid ? 1 : 0, C.list_off, C.list_cap, cnt[c], 0};
+        for (int k = 0; k < 10; k++) cells[10 * c + k] = v[k];
+    }
+    *entries = g.list_entries;
+    return n;
+}
+
 namespace orbx {
 
 // ---------------------------------------------------------------------------
@@ -2647,8 +2757,11 @@ int launch_extract(orbx_ctx* ctx, int first, int count, const MatchSpec* m)
                 band_rows = (nint + nbands - 1) / nbands;
                 return fast_tile_bytes(std::min(hmax, band_rows + 8), P);
             };
-            auto fast = [&](auto kern, int bytes, int band_rows, int threads) {
+            auto fast = [&](auto kern, int pitch, int bytes, int band_rows, int threads) {
                 const int lds = fast_lds_bytes(bytes);
+                ctx->last_fast[0] = pitch;
+                ctx->last_fast[1] = threads;
+                ctx->last_fast[2] = band_rows;
                 hipLaunchKernelGGL(kern, grid, dim3(threads), lds, st, x, bytes, band_rows);
             };
             // the templated instances queue u16 tile positions: windows of up
@@ -2667,14 +2780,15 @@ int launch_extract(orbx_ctx* ctx, int first, int count, const MatchSpec* m)
                 bytes = plan(P, fast_static_lds(false), br);
                 return bytes <= 65536;
             };
-            if (fits(96)) fast(k_fast_cells<96>, bytes, 0, 256);
+            if (fits(96)) fast(k_fast_cells<96>, 96, bytes, 0, 256);
             else if (fits(144)) {
-                for (int rep = 0; rep < kDiagRepeat[3]; rep++) fast(k_fast_cells<144>, bytes, 0, 256);
-            } else if (fits(208)) fast(k_fast_cells<208>, bytes, 0, 256);
-            else if (fits_banded(336)) fast(k_fast_cells<336, kFastWideThreads, true>, bytes, br, kFastWideThreads);
+                for (int rep = 0; rep < kDiagRepeat[3]; rep++) fast(k_fast_cells<144>, 144, bytes, 0, 256);
+            } else if (fits(208)) fast(k_fast_cells<208>, 208, bytes, 0, 256);
+            else if (fits_banded(336))
+                fast(k_fast_cells<336, kFastWideThreads, true>, 336, bytes, br, kFastWideThreads);
             else {
                 bytes = plan(wmax, fast_static_lds(true), br);
-                fast(k_fast_cells<0, kFastWideThreads, true>, bytes, br, kFastWideThreads);
+                fast(k_fast_cells<0, kFastWideThreads, true>, 0, bytes, br, kFastWideThreads);
             }
         }
         timer_end(ctx, "fast", st);

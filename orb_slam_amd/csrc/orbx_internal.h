@@ -285,6 +285,9 @@ struct orbx_ctx {
     int blur_tiles_n = 0;
     int last_first = 0, last_count = 0;   // batch of the most recent extract
     bool last_l0_direct = false;          // the last launch_extract read level 0 from the frame store
+    // the k_fast_cells instance of the last launch_extract: tile pitch (0: the
+    // runtime-pitch instance), workgroup threads, band rows (0: whole cells)
+    int last_fast[3] = {-1, 0, 0};
     // Frame::ComputeImageBounds of the slots' keypoints (orbx_dev_set_image_bounds;
     // has_bounds 0: 0..w x 0..h, the undistorted case) for the device matchers
     int has_bounds = 0;
