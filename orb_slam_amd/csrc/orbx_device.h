@@ -607,35 +607,200 @@ __device__ inline int wave_hoare_partition(E* a, int lo, int hi, int* pos)
     return (m == 0) ? l1 : min(lm1, rm);
 }
 
+// --------------------------------------------------------------------------
+// Register-resident introselect rounds for a range of at most 64 entries:
+// lane i holds entry i of the window, first / last / nth are positions in
+// it and, like depth, wave-uniform (scalar registers, scalar control flow).
+// A round is the pivot step and the partition of wave_nth_element below on
+// the same entries, so it leaves the same permutation; it touches no memory.
+// --------------------------------------------------------------------------
+__device__ inline uint32_t lane_get(uint32_t v, int i) { return __builtin_amdgcn_readlane(v, i); }
+__device__ inline uint64_t lane_get(uint64_t v, int i)
+{
+    return (uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)(v >> 32), i) << 32 |
+           (uint32_t)__builtin_amdgcn_readlane((uint32_t)v, i);
+}
+// v with lane i's entry replaced by the uniform s (a compare and a select
+// per word: this toolchain has no v_writelane builtin)
+template <typename E>
+__device__ inline E lane_set(E v, E s, int i) { return (int)(threadIdx.x & 63) == i ? s : v; }
+// the value lane `src` holds (src: any lane, per lane)
+__device__ inline uint32_t lane_pull(uint32_t v, int src) { return __builtin_amdgcn_ds_bpermute(src << 2, v); }
+__device__ inline uint64_t lane_pull(uint64_t v, int src)
+{
+    return (uint64_t)(uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (uint32_t)(v >> 32)) << 32 |
+           (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (uint32_t)v);
+}
+// set bits of a wave mask below this lane
+__device__ inline int lane_rank(unsigned long long m)
+{
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+}
+
+// Runs the rounds of introselect on [first, last) of the window in v until
+// the range is down to 3 entries, and sorts those.  Returns false with depth
+// == 0 and the range still longer (the caller's heap_select fallback).
+template <typename E>
+__device__ inline bool wave_nth_rounds_reg(E& v, int& first_io, int& last_io, int& depth_io, int nth, int pivot_mode)
+{
+    const int lane = threadIdx.x & 63;
+    int first = __builtin_amdgcn_readfirstlane(first_io), last = __builtin_amdgcn_readfirstlane(last_io);
+    int depth = __builtin_amdgcn_readfirstlane(depth_io);
+    nth = __builtin_amdgcn_readfirstlane(nth);
+    bool done = true;
+    while (last - first > 3) {
+        if (depth == 0) {
+            done = false;
+            break;
+        }
+        --depth;
+        // nth_pivot_step: three keys at uniform lanes, scalar median, one swap
+        {
+            const uint32_t key = kp_key(v);
+            const int x = pivot_mode == 1 ? first : first + 1, y = first + (last - first) / 2, z = last - 1;
+            const uint32_t kx = __builtin_amdgcn_readlane(key, x), ky = __builtin_amdgcn_readlane(key, y),
+                           kz = __builtin_amdgcn_readlane(key, z);
+            int t;
+            if (kx > ky) t = ky > kz ? y : (kx > kz ? z : x);
+            else t = kx > kz ? x : (ky > kz ? z : y);
+            if (t != first) {
+                const E ef = lane_get(v, first), et = lane_get(v, t);
+                v = lane_set(v, et, first);
+                v = lane_set(v, ef, t);
+            }
+        }
+        // wave_hoare_partition: L_k = the k-th entry of [first + 1, last) from
+        // the left with key <= P, R_k = the k-th from the right with key >= P
+        const uint32_t key = kp_key(v);
+        const uint32_t P = __builtin_amdgcn_readlane(key, first);
+        const bool inr = (unsigned)(lane - first - 1) < (unsigned)(last - first - 1);
+        const bool is_le = inr && key <= P, is_ge = inr && key >= P;
+        const unsigned long long le = __ballot(is_le), ge = __ballot(is_ge);
+        const int n_le = __builtin_popcountll(le);
+        const int cl = lane_rank(le);                                // #le below this lane
+        const int cr = __builtin_popcountll(ge) - lane_rank(ge);     // #ge at or above it
+        // m = max over splits of min(cl, cr): cl rises and cr falls with the
+        // lane, so the maximum lies at the crossing or just before it
+        const unsigned long long cross = __ballot(cl >= cr) & ~((2ull << first) - 1);
+        const int sx = cross ? (int)__builtin_ctzll(cross) : 64;
+        const int m = max(sx < 64 ? __builtin_amdgcn_readlane(cr, sx) : 0, __builtin_amdgcn_readlane(cl, sx - 1));
+        // ranks compact to lanes: lane k - 1 learns L_k and R_k (at most 63
+        // entries in the range, so lane 63 takes the lanes that send nothing)
+        const int posL = __builtin_amdgcn_ds_permute((is_le ? cl : 63) << 2, lane);
+        const int posR = __builtin_amdgcn_ds_permute((is_ge ? cr - 1 : 63) << 2, lane);
+        // the swaps (L_k, R_k), k = 1..m: disjoint pairs, each lane of a pair
+        // takes its partner's entry
+        const bool isL = is_le && cl < m, isR = is_ge && cr <= m;
+        const int pk = __builtin_amdgcn_ds_bpermute((isL ? cl : cr - 1) << 2, posL | (posR << 8));
+        const int partner = isL ? (pk >> 8) & 0xff : (isR ? pk & 0xff : lane);
+        v = lane_pull(v, partner);
+        int cut;
+        if (m == 0) {
+            cut = le ? (int)__builtin_ctzll(le) : last;   // L_1 (never absent: the pivot is a median of three)
+        } else {
+            const int lm1 = m < n_le ? __builtin_amdgcn_readlane(posL, m) : 0x7fffffff;
+            cut = min(lm1, __builtin_amdgcn_readlane(posR, m - 1));
+        }
+        if (cut <= nth) first = cut;
+        else last = cut;
+    }
+    if (done && last - first >= 2) {
+        // insertion_sort of the last 2 or 3 entries
+        E e0 = lane_get(v, first), e1 = lane_get(v, first + 1);
+        if (kp_greater(e1, e0)) {
+            const E t = e0;
+            e0 = e1;
+            e1 = t;
+        }
+        if (last - first == 3) {
+            E e2 = lane_get(v, first + 2);
+            if (kp_greater(e2, e0)) {
+                const E t = e2;
+                e2 = e1;
+                e1 = e0;
+                e0 = t;
+            } else if (kp_greater(e2, e1)) {
+                const E t = e2;
+                e2 = e1;
+                e1 = t;
+            }
+            v = lane_set(v, e2, first + 2);
+        }
+        v = lane_set(v, e0, first);
+        v = lane_set(v, e1, first + 1);
+    }
+    first_io = first;
+    last_io = last;
+    depth_io = depth;
+    return done;
+}
+
+// introselect's depth-exhausted branch on [first, last) of a (lane 0 alone)
+template <bool kGlobal, typename E>
+__device__ inline void wave_nth_heap_fallback(E* a, int first, int last, int nth)
+{
+    if ((threadIdx.x & 63) == 0) {
+        heap_select(a + first, nth + 1 - first, last - first);
+        const E t = a[first];
+        a[first] = a[nth];
+        a[nth] = t;
+    }
+    nth_sync<kGlobal>();
+}
+
 // std::nth_element(a, a + nth, a + n, greater-by-response), one wave.
 // kGlobal: list and scratch in global memory (lists too long for LDS).
+// Rounds on more than 64 entries partition in memory; once the range is down
+// to 64 it moves into registers (one entry per lane) for the rest.
 template <bool kGlobal = false, typename E>
 __device__ inline void wave_nth_element(E* a, int n, int nth, int* pos, int pivot_mode = 0)
 {
+    n = __builtin_amdgcn_readfirstlane(n);
+    nth = __builtin_amdgcn_readfirstlane(nth);
     if (n == 0 || nth == n) return;
     const int lane = threadIdx.x & 63;
     int first = 0, last = n;
     int depth = 2 * floor_log2(n);
-    while (last - first > 3) {
+    while (last - first > 64) {
         if (depth == 0) {
-            if (lane == 0) {
-                heap_select(a + first, nth + 1 - first, last - first);
-                const E t = a[first];
-                a[first] = a[nth];
-                a[nth] = t;
-            }
-            nth_sync<kGlobal>();
+            wave_nth_heap_fallback<kGlobal>(a, first, last, nth);
             return;
         }
         --depth;
         if (lane == 0) nth_pivot_step(a, first, last, pivot_mode);
         nth_sync<kGlobal>();
-        const int cut = wave_hoare_partition<kGlobal>(a, first, last, pos);
+        const int cut = __builtin_amdgcn_readfirstlane(wave_hoare_partition<kGlobal>(a, first, last, pos));
         if (cut <= nth) first = cut;
         else last = cut;
     }
-    if (lane == 0) insertion_sort(a, first, last);
+    const int base = first, cnt = last - first;
+    E v = lane < cnt ? a[base + lane] : E(0);
+    int f = 0, l = cnt;
+    const bool done = wave_nth_rounds_reg(v, f, l, depth, nth - base, pivot_mode);
+    if (lane < cnt) a[base + lane] = v;
     nth_sync<kGlobal>();
+    if (!done) wave_nth_heap_fallback<kGlobal>(a, base + f, base + l, nth);
+}
+
+// The same for a list of n <= 64 entries that never went to memory: lane i
+// holds entry i in v and gets entry i of the result.  spill: n entries of LDS,
+// written only by the heap_select fallback.
+template <typename E>
+__device__ inline E wave_nth_element_small(E v, int n, int nth, E* spill, int pivot_mode = 0)
+{
+    n = __builtin_amdgcn_readfirstlane(n);
+    nth = __builtin_amdgcn_readfirstlane(nth);
+    if (n == 0 || nth == n) return v;
+    const int lane = threadIdx.x & 63;
+    int f = 0, l = n;
+    int depth = 2 * floor_log2(n);
+    if (!wave_nth_rounds_reg(v, f, l, depth, nth, pivot_mode)) {
+        if (lane < n) spill[lane] = v;
+        lds_wave_sync();
+        wave_nth_heap_fallback<false>(spill, f, l, nth);
+        if (lane < n) v = spill[lane];
+    }
+    return v;
 }
 
 }  // namespace orbx

@@ -1538,8 +1538,10 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(kThrea
 // retainBest, in two launches (src/ORBextractor.cc:622-701):
 //  k_retain_cells   one wave per (cell, frame): the level's quota
 //                   redistribution (:622-670, wave-parallel over cells),
-//                   nth_element of the cell list in a wave-private LDS
-//                   buffer (:683-685), and the retained prefix written to
+//                   nth_element of the cell list (:683-685; in registers
+//                   up to 64 corners and once the range is down to 64, in
+//                   a wave-private LDS buffer before that, in global memory
+//                   beyond kRetainCellCap), and the retained prefix written to
 //                   the cell's slot of the level list (cell order, :687-694);
 //  k_retain_levels  one wave per (level, frame): nth_element of the level
 //                   list when it exceeds the level quota (:697-701).
@@ -1726,7 +1728,11 @@ __global__ __launch_bounds__(256) void k_retain_cells(ExtractArgs a, int waves_p
     const int take = min(n, k);
     E* src = cell_entries<E>(a) + (size_t)f * a.list_entries + C.list_off;
     E* dst = level_entries<E>(a) + (size_t)f * a.level_entries + L.level_off + pre;
-    if (n > k && n <= kRetainCellCap) {
+    if (n > k && n <= 64) {
+        // one entry per lane from the start: no staging
+        const E v = wave_nth_element_small(lane < n ? src[lane] : E(0), n, k, list, a.nth_pivot);
+        if (lane < take) dst[lane] = v;
+    } else if (n > k && n <= kRetainCellCap) {
         stage_to_lds<8>(list, n, lane, 64, [&](int i) { return src[i]; });
         lds_wave_sync();
         wave_nth_element(list, n, k, pos, a.nth_pivot);
@@ -2389,13 +2395,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k
     }
 }
 
-// Diagnostics: the LDS introselect replay of k_retain_cells on one list of
-// u32 entries (key << 24 | payload), one wavefront; also the global-memory
-// replay of long lists (out_glb).
-__global__ __launch_bounds__(64) void k_debug_nth(const uint32_t* in, int n, int nth, uint32_t* out_glb,
-                                                  uint32_t* out_lds, int* gpos, int pivot_mode)
+// Diagnostics: the LDS introselect replay of k_retain_cells on one list
+// of u32 entries (key << 24 | payload) or u64 entries (key << 32 |
+// payload), one wavefront; also the global-memory replay of long lists
+// (out_glb).
+template <typename E>
+__global__ __launch_bounds__(64) void k_debug_nth(const E* in, int n, int nth, E* out_glb, E* out_lds, int* gpos,
+                                                  int pivot_mode)
 {
-    __shared__ uint32_t list[kRetainCellCap];
+    __shared__ E list[kRetainCellCap];
     __shared__ int pos[kRetainCellCap + 8];
     const int lane = threadIdx.x;
     for (int i = lane; i < n; i += 64) out_glb[i] = in[i];
@@ -2407,29 +2415,46 @@ __global__ __launch_bounds__(64) void k_debug_nth(const uint32_t* in, int n, int
     for (int i = lane; i < n; i += 64) out_lds[i] = list[i];
 }
 
+// One list of n <= kRetainCellCap entries through both replays; host arrays.
+template <typename E>
+int debug_nth(const E* entries, int n, int nth, int pivot_mode, E* out_glb, E* out_lds)
+{
+    if (!entries || !out_glb || !out_lds || n < 0 || n > kRetainCellCap || nth < 0 || nth > n ||
+        (pivot_mode != 0 && pivot_mode != 1))
+        return ORBX_ERR_ARG;
+    E* d = nullptr;
+    if (hipMalloc(&d, 4 * sizeof(E) * (n + 8)) != hipSuccess) return ORBX_ERR_NOMEM;
+    int r = ORBX_OK;
+    if (hipMemcpy(d, entries, sizeof(E) * n, hipMemcpyHostToDevice) != hipSuccess) r = ORBX_ERR_HIP;
+    if (r == ORBX_OK) {
+        hipLaunchKernelGGL(k_debug_nth<E>, dim3(1), dim3(64), 0, 0, d, n, nth, d + (n + 8), d + 2 * (n + 8),
+                           reinterpret_cast<int*>(d + 3 * (n + 8)), pivot_mode);
+        if (hipDeviceSynchronize() != hipSuccess ||
+            hipMemcpy(out_glb, d + (n + 8), sizeof(E) * n, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(out_lds, d + 2 * (n + 8), sizeof(E) * n, hipMemcpyDeviceToHost) != hipSuccess)
+            r = ORBX_ERR_HIP;
+    }
+    (void)hipFree(d);
+    return r;
+}
+
 }  // namespace orbx
 
 extern "C" int orbx_debug_nth_pivot(const uint32_t* entries, int n, int nth, int pivot_mode, uint32_t* out_glb,
                                     uint32_t* out_lds)
 {
-    using namespace orbx;
-    if (!entries || !out_glb || !out_lds || n < 0 || n > kRetainCellCap || nth < 0 || nth > n ||
-        (pivot_mode != 0 && pivot_mode != 1))
-        return ORBX_ERR_ARG;
-    uint32_t* d = nullptr;
-    if (hipMalloc(&d, 4 * sizeof(uint32_t) * (n + 8)) != hipSuccess) return ORBX_ERR_NOMEM;
-    int r = ORBX_OK;
-    if (hipMemcpy(d, entries, sizeof(uint32_t) * n, hipMemcpyHostToDevice) != hipSuccess) r = ORBX_ERR_HIP;
-    if (r == ORBX_OK) {
-        hipLaunchKernelGGL(k_debug_nth, dim3(1), dim3(64), 0, 0, d, n, nth, d + (n + 8), d + 2 * (n + 8),
-                           reinterpret_cast<int*>(d + 3 * (n + 8)), pivot_mode);
-        if (hipDeviceSynchronize() != hipSuccess ||
-            hipMemcpy(out_glb, d + (n + 8), sizeof(uint32_t) * n, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(out_lds, d + 2 * (n + 8), sizeof(uint32_t) * n, hipMemcpyDeviceToHost) != hipSuccess)
-            r = ORBX_ERR_HIP;
-    }
-    (void)hipFree(d);
-    return r;
+    return orbx::debug_nth(entries, n, nth, pivot_mode, out_glb, out_lds);
+}
+
+// Harris-keyed entries, as k_harris_cells builds them: harris_key(response) << 32 | index
+extern "C" int orbx_debug_nth64(const float* responses, int n, int nth, int pivot_mode, uint64_t* out_glb,
+                                uint64_t* out_lds)
+{
+    if (!responses || n < 0 || n > orbx::kRetainCellCap) return ORBX_ERR_ARG;
+    std::vector<uint64_t> e((size_t)n);
+    for (int i = 0; i < n; i++) e[i] = (uint64_t)orbx::harris_key(responses[i]) << 32 | (uint32_t)i;
+    static const uint64_t none = 0;
+    return orbx::debug_nth(n ? e.data() : &none, n, nth, pivot_mode, out_glb, out_lds);
 }
 
 extern "C" int orbx_debug_nth(const uint32_t* entries, int n, int nth, uint32_t* out_glb, uint32_t* out_lds)
