@@ -53,8 +53,11 @@ extern "C" {
  *   8: the end of map initialisation (orbx_reconstruct_query,
  *      orbx_init_reconstruct, orbx_init_reconstruct_batch,
  *      orbx_dev_init_reconstruct, orbx_dev_read_init_reconstruct);
+ *      additions only.
+ *   9: the Sim3 solver of loop closing (orbx_sim3_query, orbx_sim3_ransac,
+ *      orbx_sim3_ransac_batch, orbx_sim3_kf, orbx_dev_sim3_candidates);
  *      additions only. */
-#define ORBX_ABI_VERSION 8
+#define ORBX_ABI_VERSION 9
 int orbx_abi_version(void);
 
 #define ORBX_OK               0
@@ -269,7 +272,10 @@ int orbx_dev_read_matches(orbx_ctx* ctx, int slot, int32_t* matches12, int cap,
  * "resize", "fast", "retain", "blur", "describe", "match", "init" (the three kernels of
  * orbx_init_models / orbx_dev_init_models, one timed region per call),
  * "triangulate" (k_triangulate: one launch per orbx_triangulate_matches or
- * unchained create_new_map_points call, one per neighbour when chained).  Returns the number of
+ * unchained create_new_map_points call, one per neighbour when chained),
+ * "sim3" (the three kernels of orbx_sim3_ransac / _batch /
+ * orbx_dev_sim3_candidates, one timed region per call; "sim3.prepare",
+ * "sim3.solve", "sim3.check": each kernel on its own).  Returns the number of
  * timed launches; *avg_ms receives the mean duration. */
 int orbx_dev_kernel_time(orbx_ctx* ctx, const char* name, double* avg_ms,
                          double* total_ms);
@@ -938,6 +944,124 @@ int orbx_dev_create_new_map_points(orbx_ctx* ctx, int slot1, const uint8_t* mp1,
                                    const float* F12s, int check_ori, int chain, int32_t* const* matches12,
                                    int* n_matches, float* const* xyz, uint8_t* const* status, int* n_created,
                                    float* const* v4, int cap);
+
+/* Sim3Solver (src/Sim3Solver.cc): Horn's closed-form similarity inside a
+ * RANSAC over the matches of two keyframes, step 2 of
+ * LoopClosing::ComputeSim3 (src/LoopClosing.cc:231-344) between
+ * orbx_search_by_bow_kf_batch and orbx_search_by_sim3.  One call is one
+ * Sim3Solver::iterate(n_iter, ...) (:140-207) of a solver built by the
+ * constructor (:37-112) and SetRansacParameters (:114-138): the
+ * correspondences compacted in i1 order, the camera coordinates, their
+ * projections and the integer error limits, then every iteration of the
+ * call at once -- its minimal set from the caller's rand() values (with the
+ * reference's removal at the drawn value's position, :175), computeT
+ * (:226-332) and CheckInliers (:335-359) -- and the replay of the loop's
+ * sequential bookkeeping over the inlier counts.
+ * A correspondence is kept for i1 when matches12[i1] >= 0, k1 = idx1 ?
+ * idx1[i1] : i1 lies in [0, n1) (GetIndexInKeyFrame(pKF1) >= 0), valid1[k1]
+ * and valid2[matches12[i1]] are set (a map point that is not isBad()); it
+ * reads pos1[k1], keys1[k1].octave, pos2[i2], keys2[i2].octave.
+ * The float arithmetic the reference writes itself is followed operation by
+ * operation (fx*x+cx follows orbx_set_fp_contract); the places that go
+ * through OpenCV, and the quaternion -- the unit eigenvector of N for its
+ * largest eigenvalue, FP64 from the float entries, rounded once, q0 >= 0 --
+ * are defined in DESIGN.md section 4.
+ * The iterations of a call are [iter_done, iter_done + n_iter) of the
+ * solver, cut at ransac_max_its.  The call returns like iterate: at the first
+ * iteration whose count reaches the running best (which starts at
+ * best_inliers) and exceeds min_inliers -- found = 1, found_iter its index in
+ * this call, iters_run = found_iter + 1; the caller continues a solver with
+ * iter_done + iters_run, best_inliers_out and the draws that follow.
+ * Arguments are checked before any device work.  ORBX_ERR_ARG: a null
+ * context, query or required pointer, n_iter outside 1..1024, a draw < 0,
+ * min_inliers < 3, max_iterations < 1, iter_done or best_inliers < 0, a
+ * probability outside (0,1), nlevels outside 1..16, an octave outside
+ * [0, nlevels), a level sigma2 that is negative, not finite or whose limit
+ * 9.210 * sigma2 does not fit an int, a match index >= n2, an idx1 entry >= n1;
+ * ORBX_ERR_UNSUPPORTED: more than 4096 keypoints; ORBX_ERR_CAPACITY: cap <
+ * n1.  N < min_inliers returns ORBX_OK with no_more = 1, found = 0 and no
+ * iteration run (:146-150). */
+typedef struct {
+    /* in */
+    const orbx_keypoint* keys1; int n1;   /* pKF1's mvKeysUn (the octave is read)             */
+    const orbx_keypoint* keys2; int n2;   /* pKF2's                                           */
+    const int32_t* matches12;             /* n1: KF2 keypoint of vpMatched12[i1], or < 0      */
+    const int32_t* idx1;                  /* n1: GetIndexInKeyFrame(pKF1) of pKF1's map point
+                                             at i1 (< 0: none); NULL: i1                      */
+    const float* pos1; const uint8_t* valid1;   /* n1 x 3 GetWorldPos(), n1: 1 = a good map point */
+    const float* pos2; const uint8_t* valid2;   /* n2 x 3, n2                                     */
+    const float* T1w; const float* T2w;   /* 16 each: the keyframes' Tcw, row-major           */
+    const float* cam1; const float* cam2; /* fx, fy, cx, cy                                   */
+    const float* sigma2_1; const float* sigma2_2; int nlevels;   /* mvLevelSigma2 of each     */
+    double probability; int min_inliers; int max_iterations;     /* 0.99, 20, 300 (LoopClosing.cc:276) */
+    /* iterate state (in) */
+    int iter_done;                        /* mnIterations on entry                            */
+    int best_inliers;                     /* mnBestInliers on entry                           */
+    int n_iter;                           /* iterate's nIterations (find(): the cap)          */
+    const int32_t* draws;                 /* n_iter x 3 successive rand() values              */
+    /* out */
+    int N;                                /* correspondences                                  */
+    int ransac_max_its;                   /* mRansacMaxIts (0 when N < min_inliers, where the
+                                             reference converts a NaN)                        */
+    int iters_run;                        /* iterations executed by this call                 */
+    int no_more;                          /* bNoMore                                          */
+    int found, found_iter;                /* a non-empty return; its iteration or -1          */
+    int n_inliers;                        /* nInliers (0 when !found)                         */
+    float T12[16];                        /* the returned mBestT12 (untouched when !found)    */
+    uint8_t* inliers; int cap;            /* vbInliers by i1 (n1 written, all 0 when !found)  */
+    int best_inliers_out;                 /* mnBestInliers at return                          */
+    int best_iter;                        /* the iteration of this call that holds the mBest*
+                                             state at return, -1: none reached best_inliers   */
+    float R12[9], t12[3], s12;            /* mBestRotation / Translation / Scale (untouched
+                                             when best_iter is -1)                            */
+    /* optional taps (may be NULL), leading dimension n_iter */
+    int32_t* sets;                        /* x 3: indices into the correspondences            */
+    float* q;                             /* x 4: the quaternion (w, x, y, z)                 */
+    float* R; float* scale;               /* x 9: mR12i; ms12i                                */
+    float* T12_all; float* T21_all;       /* x 16                                             */
+    int32_t* count;                       /* mnInliersi                                       */
+    /* optional taps per correspondence (cap >= n1 entries each, N written) */
+    float* x3dc1; float* x3dc2;           /* x 3: mvX3Dc1 / 2                                 */
+    float* p1im1; float* p2im2;           /* x 2: mvP1im1 / mvP2im2                           */
+    int32_t* max_err1; int32_t* max_err2; /* mvnMaxError1 / 2                                 */
+    int32_t* indices1;                    /* mvnIndices1                                      */
+} orbx_sim3_query;
+
+int orbx_sim3_ransac(orbx_ctx* ctx, orbx_sim3_query* q);   /* one upload, one read-back */
+/* ComputeSim3's candidates in one upload, one launch set and one read-back;
+ * results as B single calls. */
+int orbx_sim3_ransac_batch(orbx_ctx* ctx, int B, orbx_sim3_query* qs);
+
+/* A device-resident keyframe as the solver reads it: what does not live in
+ * the slot. */
+typedef struct {
+    const uint8_t* mp;       /* per keypoint: 0 none, 1 map point, 2 isBad() (as orbx_dev_search_by_bow_kf) */
+    const float* pos;        /* per keypoint x 3: GetWorldPos() (read where mp is 1)                          */
+    const float* Tcw;        /* 16                                                                            */
+    const float* cam;        /* fx, fy, cx, cy                                                                */
+    const float* sigma2;     /* nlevels: mvLevelSigma2                                                        */
+    int nlevels;             /* the extractor's                                                               */
+} orbx_sim3_kf;
+
+/* Steps 1 and 2 of ComputeSim3 between device-resident frames: SearchByBoW
+ * (KF1 in slot1, KF2 in slots2[k]) as orbx_dev_search_by_bow_kf queues it,
+ * and on the match vectors where the search left them a fresh Sim3Solver per
+ * candidate (idx1 = i1; the iterate state is read from out[k]: iter_done,
+ * best_inliers) running n_iter iterations from draws (n x n_iter x 3).  A
+ * candidate with n_matches[k] < min_matches (20, LoopClosing.cc:268) is
+ * discarded[k] = 1 and runs no RANSAC (its out fields read N = 0, found = 0,
+ * no_more = 0).  One synchronisation and one read-back: matches12[k] (cap >=
+ * nfeatures entries), n_matches[k], discarded[k] and out[k]'s out fields and
+ * taps (out[k].inliers / cap >= nfeatures and the tap pointers are read from
+ * it; its other in fields are ignored).  Results as
+ * orbx_dev_search_by_bow_kf followed by orbx_sim3_ransac_batch on the
+ * read-back matches.  A match whose index or octave is out of range is
+ * dropped.  The mp / pos arrays hold one entry per keypoint of the slot. */
+int orbx_dev_sim3_candidates(orbx_ctx* ctx, int slot1, const orbx_sim3_kf* kf1, int n, const int* slots2,
+                             const orbx_sim3_kf* kf2s, float nnratio, int check_ori, int min_matches,
+                             double probability, int min_inliers, int max_iterations, int n_iter,
+                             const int32_t* draws, int32_t* const* matches12, int cap, int* n_matches,
+                             int* discarded, orbx_sim3_query* out);
 
 /* ------------------------------------------------------------------------ */
 /* C. Local bundle adjustment                                                */

@@ -173,6 +173,110 @@ def reconstruct_result(q, keep, taps=False, n1=None, n_matches=None):
     return r
 
 
+class Sim3Query(ctypes.Structure):
+    """orbx_sim3_query (include/orbx.h)."""
+    _fields_ = [("keys1", ctypes.c_void_p), ("n1", ctypes.c_int), ("keys2", ctypes.c_void_p), ("n2", ctypes.c_int),
+                ("matches12", ctypes.c_void_p), ("idx1", ctypes.c_void_p),
+                ("pos1", ctypes.c_void_p), ("valid1", ctypes.c_void_p),
+                ("pos2", ctypes.c_void_p), ("valid2", ctypes.c_void_p),
+                ("T1w", ctypes.c_void_p), ("T2w", ctypes.c_void_p), ("cam1", ctypes.c_void_p), ("cam2", ctypes.c_void_p),
+                ("sigma2_1", ctypes.c_void_p), ("sigma2_2", ctypes.c_void_p), ("nlevels", ctypes.c_int),
+                ("probability", ctypes.c_double), ("min_inliers", ctypes.c_int), ("max_iterations", ctypes.c_int),
+                ("iter_done", ctypes.c_int), ("best_inliers", ctypes.c_int), ("n_iter", ctypes.c_int),
+                ("draws", ctypes.c_void_p),
+                ("N", ctypes.c_int), ("ransac_max_its", ctypes.c_int), ("iters_run", ctypes.c_int),
+                ("no_more", ctypes.c_int), ("found", ctypes.c_int), ("found_iter", ctypes.c_int),
+                ("n_inliers", ctypes.c_int), ("T12", ctypes.c_float * 16),
+                ("inliers", ctypes.c_void_p), ("cap", ctypes.c_int),
+                ("best_inliers_out", ctypes.c_int), ("best_iter", ctypes.c_int),
+                ("R12", ctypes.c_float * 9), ("t12", ctypes.c_float * 3), ("s12", ctypes.c_float),
+                ("sets", ctypes.c_void_p), ("q", ctypes.c_void_p), ("R", ctypes.c_void_p), ("scale", ctypes.c_void_p),
+                ("T12_all", ctypes.c_void_p), ("T21_all", ctypes.c_void_p), ("count", ctypes.c_void_p),
+                ("x3dc1", ctypes.c_void_p), ("x3dc2", ctypes.c_void_p), ("p1im1", ctypes.c_void_p),
+                ("p2im2", ctypes.c_void_p), ("max_err1", ctypes.c_void_p), ("max_err2", ctypes.c_void_p),
+                ("indices1", ctypes.c_void_p)]
+
+
+class Sim3Kf(ctypes.Structure):
+    """orbx_sim3_kf (include/orbx.h)."""
+    _fields_ = [("mp", ctypes.c_void_p), ("pos", ctypes.c_void_p), ("Tcw", ctypes.c_void_p), ("cam", ctypes.c_void_p),
+                ("sigma2", ctypes.c_void_p), ("nlevels", ctypes.c_int)]
+
+
+_SIM3_ITER_TAPS = (("sets", np.int32, 3), ("q", np.float32, 4), ("R", np.float32, 9), ("scale", np.float32, 0),
+                   ("T12_all", np.float32, 16), ("T21_all", np.float32, 16), ("count", np.int32, 0))
+_SIM3_CORR_TAPS = (("x3dc1", np.float32, 3), ("x3dc2", np.float32, 3), ("p1im1", np.float32, 2),
+                   ("p2im2", np.float32, 2), ("max_err1", np.int32, 0), ("max_err2", np.int32, 0),
+                   ("indices1", np.int32, 0))
+_SIM3_KF_KEYS = ("keys", "pos", "valid", "Tcw", "cam", "sigma2")
+
+
+def sim3_query(kf1, kf2, matches12, draws, n_iter=None, idx1=None, probability=0.99, min_inliers=20,
+               max_iterations=300, iter_done=0, best_inliers=0, taps=False, cap=None):
+    """A Sim3Query over numpy arrays and the arrays it points to (keep both
+    alive while the query is used): (query, keep).  kf1 / kf2: dicts of keys
+    (KEYPOINT), pos (n x 3), valid (n), Tcw (4 x 4), cam (fx, fy, cx, cy) and
+    sigma2 (the level table).  kf1 None: an output-only query of a
+    device-resident candidate (cap keypoints)."""
+    keep = {}
+    q = Sim3Query()
+    if kf1 is not None:
+        for side, kf in (("1", kf1), ("2", kf2)):
+            keep["keys" + side] = np.ascontiguousarray(kf["keys"], KEYPOINT)
+            keep["pos" + side] = np.ascontiguousarray(kf["pos"], np.float32).reshape(-1, 3)
+            keep["valid" + side] = np.ascontiguousarray(kf["valid"], np.uint8)
+            keep["T" + side + "w"] = np.ascontiguousarray(kf["Tcw"], np.float32).reshape(-1)
+            keep["cam" + side] = np.ascontiguousarray(kf["cam"], np.float32).reshape(-1)
+            keep["sigma2_" + side] = np.ascontiguousarray(kf["sigma2"], np.float32).reshape(-1)
+            for name in ("keys", "pos", "valid"):
+                setattr(q, name + side, keep[name + side].ctypes.data)
+            for name in ("T" + side + "w", "cam" + side, "sigma2_" + side):
+                setattr(q, name, keep[name].ctypes.data)
+        q.n1, q.n2 = len(keep["keys1"]), len(keep["keys2"])
+        q.nlevels = min(len(keep["sigma2_1"]), len(keep["sigma2_2"]))
+        keep["matches12"] = np.ascontiguousarray(matches12, np.int32)
+        keep["draws"] = np.ascontiguousarray(draws, np.int32)
+        q.matches12, q.draws = keep["matches12"].ctypes.data, keep["draws"].ctypes.data
+        if idx1 is not None:
+            keep["idx1"] = np.ascontiguousarray(idx1, np.int32)
+            q.idx1 = keep["idx1"].ctypes.data
+        if n_iter is None:
+            n_iter = keep["draws"].size // 3
+        if cap is None:
+            cap = q.n1
+    q.probability, q.min_inliers, q.max_iterations = probability, min_inliers, max_iterations
+    q.iter_done, q.best_inliers, q.n_iter = iter_done, best_inliers, int(n_iter)
+    q.cap = max(int(cap), 0)
+    keep["inliers"] = np.zeros(max(q.cap, 1), np.uint8)
+    q.inliers = keep["inliers"].ctypes.data
+    if taps:
+        m = max(int(n_iter), 1)
+        for name, dt, k in _SIM3_ITER_TAPS:
+            keep[name] = np.zeros((m, k) if k else m, dt)
+            setattr(q, name, keep[name].ctypes.data)
+        for name, dt, k in _SIM3_CORR_TAPS:
+            keep[name] = np.zeros((max(q.cap, 1), k) if k else max(q.cap, 1), dt)
+            setattr(q, name, keep[name].ctypes.data)
+    return q, keep
+
+
+def sim3_result(q, keep, taps=False, n1=None):
+    """The out fields (and taps) of a filled Sim3Query as a dict."""
+    n1 = q.n1 if n1 is None else n1
+    r = dict(N=q.N, ransac_max_its=q.ransac_max_its, iters_run=q.iters_run, no_more=q.no_more, found=q.found,
+             found_iter=q.found_iter, n_inliers=q.n_inliers, best_inliers_out=q.best_inliers_out, best_iter=q.best_iter,
+             T12=np.array(q.T12, np.float32) if q.found else None,
+             R12=np.array(q.R12, np.float32) if q.best_iter >= 0 else None,
+             t12=np.array(q.t12, np.float32) if q.best_iter >= 0 else None,
+             s12=np.float32(q.s12) if q.best_iter >= 0 else None, inliers=keep["inliers"][:n1].copy())
+    if taps:
+        for name, _, _ in _SIM3_ITER_TAPS:
+            r[name] = keep[name]
+        for name, _, _ in _SIM3_CORR_TAPS:
+            r[name] = keep[name][:q.N]
+    return r
+
+
 class KfGeom(ctypes.Structure):
     """orbx_kf_geom (include/orbx.h)."""
     _fields_ = [("Rcw", ctypes.c_void_p), ("tcw", ctypes.c_void_p), ("Ow", ctypes.c_void_p), ("cam", ctypes.c_void_p),
@@ -339,6 +443,9 @@ def _declare(L):
         "orbx_triangulate_matches": ([vp, vp, i, vp, i, vp, vp, vp, vp, vp, vp, vp, vp], i),
         "orbx_create_new_map_points": ([vp, vp, vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp], i),
         "orbx_dev_create_new_map_points": ([vp, i, vp, vp, i, vp, vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp, i], i),
+        "orbx_sim3_ransac": ([vp, vp], i),
+        "orbx_sim3_ransac_batch": ([vp, i, vp], i),
+        "orbx_dev_sim3_candidates": ([vp, i, vp, i, vp, vp, f, i, i, ctypes.c_double, i, i, i, vp, vp, i, vp, vp, vp], i),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(L, name)
@@ -832,6 +939,69 @@ class Context:
                                                     cap), "orbx_dev_create_new_map_points")
         out["n_created"], out["n_matches"] = out["n_created"][:n], out["n_matches"][:n]
         return out
+
+    # --- LoopClosing::ComputeSim3: Sim3Solver --------------------------------
+    def sim3_ransac(self, kf1, kf2, matches12, draws, taps=False, **kw):
+        """One Sim3Solver::iterate call on the device (orbx_sim3_ransac):
+        arguments as sim3_query, a dict of the query's out fields (T12 None
+        when nothing was returned, R12 / t12 / s12 None when no iteration of
+        the call reached best_inliers) and, with taps, its tap arrays."""
+        q, keep = sim3_query(kf1, kf2, matches12, draws, taps=taps, **kw)
+        _check(lib().orbx_sim3_ransac(self._h, ctypes.byref(q)), "orbx_sim3_ransac")
+        return sim3_result(q, keep, taps)
+
+    def sim3_ransac_batch(self, queries, taps=False):
+        """orbx_sim3_ransac_batch over (kf1, kf2, matches12, draws, kwargs)
+        tuples: one upload, one launch set, one read-back; a list of dicts."""
+        built = [sim3_query(*a[:4], taps=taps, **(a[4] if len(a) > 4 else {})) for a in queries]
+        arr = (Sim3Query * len(built))(*[b[0] for b in built])
+        _check(lib().orbx_sim3_ransac_batch(self._h, len(built), arr), "orbx_sim3_ransac_batch")
+        return [sim3_result(arr[k], built[k][1], taps) for k in range(len(built))]
+
+    def dev_sim3_candidates(self, slot1, kf1, slots2, kf2s, draws, n_iter=None, nnratio=0.75, check_ori=True,
+                            min_matches=20, probability=0.99, min_inliers=20, max_iterations=300, states=None,
+                            taps=False, cap=None):
+        """orbx_dev_sim3_candidates: SearchByBoW of the keyframe in slot1
+        against those in slots2 and a Sim3Solver per candidate on the matches
+        the search left on the device.  kf1 / kf2s: dicts of mp (states 0, 1,
+        2 per keypoint), pos, Tcw, cam, sigma2; draws (n, n_iter, 3); states:
+        per candidate (iter_done, best_inliers), default (0, 0).  A dict of
+        matches12 (list), n_matches, discarded and results (list of dicts as
+        sim3_ransac)."""
+        n = len(slots2)
+        cap = self.nfeatures if cap is None else int(cap)
+        d = np.ascontiguousarray(draws, np.int32)
+        if n_iter is None:
+            n_iter = d.size // (3 * max(n, 1))
+        if d.size != n * n_iter * 3:
+            raise ValueError(f"draws: {d.size} values, expected n x n_iter x 3 = {n * n_iter * 3}")
+
+        def kf(g):
+            keep = dict(mp=np.ascontiguousarray(g["mp"], np.uint8), pos=np.ascontiguousarray(g["pos"], np.float32),
+                        Tcw=np.ascontiguousarray(g["Tcw"], np.float32).reshape(-1),
+                        cam=np.ascontiguousarray(g["cam"], np.float32).reshape(-1),
+                        sigma2=np.ascontiguousarray(g["sigma2"], np.float32).reshape(-1))
+            k = Sim3Kf()
+            for name, a in keep.items():
+                setattr(k, name, a.ctypes.data)
+            k.nlevels = int(g.get("nlevels", len(keep["sigma2"])))
+            return k, keep
+        K1, keep1 = kf(kf1)
+        built2 = [kf(g) for g in kf2s]
+        K2 = (Sim3Kf * max(n, 1))(*[b[0] for b in built2])
+        outs = [sim3_query(None, None, None, None, n_iter=n_iter, taps=taps, cap=cap,
+                           iter_done=states[k][0] if states else 0, best_inliers=states[k][1] if states else 0)
+                for k in range(n)]
+        arr = (Sim3Query * max(n, 1))(*[o[0] for o in outs])
+        m12 = [np.full(max(cap, 1), -1, np.int32) for _ in range(n)]
+        nm, disc = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        s2 = np.ascontiguousarray(list(slots2) + [0], np.int32)
+        _check(lib().orbx_dev_sim3_candidates(self._h, slot1, ctypes.byref(K1), n, _ptr(s2), K2, nnratio,
+                                              int(check_ori), min_matches, probability, min_inliers, max_iterations,
+                                              n_iter, _ptr(d), _ptr_array(m12), cap, _ptr(nm), _ptr(disc), arr),
+               "orbx_dev_sim3_candidates")
+        return dict(matches12=m12, n_matches=nm[:n], discarded=disc[:n],
+                    results=[sim3_result(arr[k], outs[k][1], taps, n1=max(cap, 1)) for k in range(n)])
 
     @property
     def handle(self):

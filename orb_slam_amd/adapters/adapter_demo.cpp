@@ -2,7 +2,8 @@
 // and LocalMapping would: extract two frames of a shifted synthetic image,
 // SearchForInitialization between them, the initialisation models of those
 // matches (Initializer::FindModels beside the plain C call fed the same rand()
-// sequence), the whole Initializer::Initialize beside orbx_init_reconstruct, brute-force matching, and one local BA on a tiny synthetic problem.  Prints one JSON line.  Exit codes: 0 ok,
+// sequence), the whole Initializer::Initialize beside orbx_init_reconstruct, brute-force matching, one local BA on a tiny synthetic problem, and
+// Sim3Solver::iterate in chunks of five beside orbx_sim3_ransac fed the same rand() sequence.  Prints one JSON line.  Exit codes: 0 ok,
 // 3 device path unavailable (orbx_error), 1 other failure.
 #include <cmath>
 #include <cstdio>
@@ -188,6 +189,91 @@ int main()
         const double tn = std::sqrt(tt[0] * tt[0] + tt[1] * tt[1] + tt[2] * tt[2]);
         const double t_cos = scene_ok ? (st[0] * tt[0] + st[1] * tt[1] + st[2] * tt[2]) / tn : 0.0;
         const double r_trace = scene_ok ? (sR[0] * ca + sR[2] * sa + sR[4] - sR[6] * sa + sR[8] * ca) : 0.0;
+        // Sim3Solver on a synthetic pair of maps: 80 points seen by both keyframes, the second map a similarity of
+        // the first (scale 1.25), every fifth partner unrelated; iterate(5) until it returns, as ComputeSim3 does,
+        // beside the plain C call fed the same rand() sequence
+        Sim3KeyFrame sk[2];
+        const double s_true = 1.25, sang = 0.1, sca = std::cos(sang), ssa = std::sin(sang), stt[3] = {0.3, -0.2, 0.4};
+        for (int i = 0; i < 80; i++) {
+            const double X2[3] = {-2.0 + 4.0 * rnd(), -1.5 + 3.0 * rnd(), 4.0 + 5.0 * rnd()};
+            double X1[3] = {s_true * (sca * X2[0] + ssa * X2[2]) + stt[0], s_true * X2[1] + stt[1],
+                            s_true * (-ssa * X2[0] + sca * X2[2]) + stt[2]};
+            if (i % 5 == 4) X1[0] += 1.0 + rnd();
+            KeyPoint kp;
+            std::memset(&kp, 0, sizeof(kp));
+            kp.size = 31.f;
+            kp.class_id = -1;
+            for (int side = 0; side < 2; side++) {
+                kp.octave = (i + 3 * side) % 8;
+                sk[side].keys.push_back(kp);
+                const double* X = side ? X2 : X1;
+                sk[side].pos.insert(sk[side].pos.end(), {(float)X[0], (float)X[1], (float)X[2]});
+                sk[side].valid.push_back(1);
+            }
+        }
+        for (int side = 0; side < 2; side++) {
+            const float I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+            std::memcpy(sk[side].Tcw, I4, sizeof(I4));
+            std::memcpy(sk[side].cam, camK, sizeof(camK));
+            float lv = 1.f;
+            for (int l = 0; l < 8; l++, lv *= 1.2f) sk[side].sigma2.push_back(lv * lv);
+        }
+        std::vector<int> sim3_m(80);
+        for (int i = 0; i < 80; i++) sim3_m[i] = i;
+        Sim3Solver solver(sk[0], sk[1], sim3_m, ex.context());
+        solver.SetRansacParameters(0.99, 20, 300);
+        std::srand(1);
+        bool sim3_no_more = false;
+        std::vector<bool> sim3_inl;
+        int sim3_n_inl = 0, sim3_calls = 0;
+        std::vector<float> sim3_T;
+        while (sim3_T.empty() && !sim3_no_more) {
+            sim3_T = solver.iterate(5, sim3_no_more, sim3_inl, sim3_n_inl);
+            sim3_calls++;
+        }
+        std::srand(1);
+        std::vector<int32_t> sim3_m32(sim3_m.begin(), sim3_m.end()), sim3_draws(15);
+        std::vector<uint8_t> sim3_ci(81);
+        orbx_sim3_query sq;
+        std::memset(&sq, 0, sizeof(sq));
+        sq.keys1 = sk[0].keys.data();
+        sq.keys2 = sk[1].keys.data();
+        sq.n1 = sq.n2 = 80;
+        sq.matches12 = sim3_m32.data();
+        sq.pos1 = sk[0].pos.data();
+        sq.pos2 = sk[1].pos.data();
+        sq.valid1 = sk[0].valid.data();
+        sq.valid2 = sk[1].valid.data();
+        sq.T1w = sk[0].Tcw;
+        sq.T2w = sk[1].Tcw;
+        sq.cam1 = sk[0].cam;
+        sq.cam2 = sk[1].cam;
+        sq.sigma2_1 = sk[0].sigma2.data();
+        sq.sigma2_2 = sk[1].sigma2.data();
+        sq.nlevels = 8;
+        sq.probability = 0.99;
+        sq.min_inliers = 20;
+        sq.max_iterations = 300;
+        sq.n_iter = 5;
+        sq.draws = sim3_draws.data();
+        sq.inliers = sim3_ci.data();
+        sq.cap = 80;
+        int sim3_ccalls = 0;
+        do {
+            for (auto& d : sim3_draws) d = (int32_t)std::rand();
+            check(orbx_sim3_ransac(ex.context(), &sq), "orbx_sim3_ransac");
+            sq.iter_done += sq.iters_run;
+            sq.best_inliers = sq.best_inliers_out;
+            sim3_ccalls++;
+        } while (!sq.found && !sq.no_more);
+        bool sim3_same = sim3_ccalls == sim3_calls && (sq.found != 0) == !sim3_T.empty() && sq.n_inliers == sim3_n_inl &&
+                         sq.iter_done == solver.mnIterations && sq.N == solver.N && (int)sim3_inl.size() == 80;
+        if (sq.found && sim3_same)
+            sim3_same = std::memcmp(sq.T12, sim3_T.data(), sizeof(sq.T12)) == 0 &&
+                        std::memcmp(sq.R12, solver.GetEstimatedRotation(), sizeof(sq.R12)) == 0 &&
+                        std::memcmp(sq.t12, solver.GetEstimatedTranslation(), sizeof(sq.t12)) == 0 &&
+                        sq.s12 == solver.GetEstimatedScale();
+        for (int i = 0; i < 80 && sim3_same; i++) sim3_same = sim3_inl[i] == (sim3_ci[i] != 0);
         std::vector<int> mbf;
         const int n_bf = matcher.MatchBruteForce(F1.desc, F2.desc, mbf);
         // tiny BA: 3 keyframes (first fixed) observing 60 points
@@ -246,13 +332,16 @@ int main()
                     "\"init_n\": %d, \"init_best\": [%d, %d], \"init_rh\": %.6g, \"init_inliers\": [%d, %d], "
                     "\"rec_same\": %d, \"rec_model\": %d, \"rec_ok\": %d, \"rec_hyp\": %d, \"rec_good\": %d, "
                     "\"rec_triangulated\": %d, \"scene_ok\": %d, \"scene_model\": %d, \"scene_triangulated\": %d, "
-                    "\"scene_in_front\": %d, \"scene_t_cos\": %.6f, \"scene_r_trace\": %.6f}\n",
+                    "\"scene_in_front\": %d, \"scene_t_cos\": %.6f, \"scene_r_trace\": %.6f, ",
                     F1.keys_un.size(), F2.keys_un.size(), ex.GetLevels(), ex.GetScaleFactor(), n_init, n_bf,
                     P.stats.iterations[0], P.stats.iterations[1], P.stats.chi2_initial[0], P.stats.chi2_final[1],
                     n_pose_inliers, n_mp, PF.Tcw[3], init_same ? 1 : 0, q.n_matches, q.best_h, q.best_f, (double)q.RH,
                     n_in_h, n_in_f, rec_same ? 1 : 0, rq.model, init_ok ? 1 : 0, rq.n_hyp,
                     rq.n_hyp > 0 && rq.best >= 0 ? rq.n_good[rq.best] : 0, n_tri, scene_ok ? 1 : 0, scene_init.mModel,
                     scene_tri, scene_front, t_cos, r_trace);
+        std::printf("\"sim3_same\": %d, \"sim3_n\": %d, \"sim3_found\": %d, \"sim3_inliers\": %d, "
+                    "\"sim3_iterations\": %d, \"sim3_scale\": %.6f}\n",
+                    sim3_same ? 1 : 0, sq.N, sq.found, sq.n_inliers, sq.iter_done, (double)solver.GetEstimatedScale());
         return 0;
     } catch (const orbx_error& e) {
         std::fprintf(stderr, "%s\n", e.what());

@@ -472,11 +472,13 @@ int queue_bow_batch(orbx_ctx* ctx, const orbx_bow_view* V1, int n, const orbx_bo
         q->extra = s.dev(o_extra);
         q->k2.resize(n);
         q->n2.resize(n);
+        q->mp2.resize(n);
         q->out.resize(n);
         q->out_n.resize(n);
         for (int k = 0; k < n; k++) {
             q->k2[k] = s.dev(o[k].s2.k);
             q->n2[k] = V2s[k].n;
+            q->mp2[k] = s.dev(o[k].s2.m);
             q->out[k] = s.dev(o[k].oo.out);
             q->out_n[k] = s.dev(o[k].oo.n);
         }
@@ -714,11 +716,13 @@ int queue_bow_slots(orbx_ctx* ctx, int mode, int slot1, const uint8_t* mp1, int 
         q->extra = s.dev(o_extra);
         q->k2.resize(n);
         q->n2.resize(n);
+        q->mp2.resize(n);
         q->out.resize(n);
         q->out_n.resize(n);
         for (int k = 0; k < n; k++) {
             q->k2[k] = slot_frame_dev(ctx, slots2[k], nullptr).kps;
             q->n2[k] = count(slots2[k]);
+            q->mp2[k] = s.dev(o[k].m2);
             q->out[k] = s.dev(o[k].oo.out);
             q->out_n[k] = s.dev(o[k].oo.n);
         }

@@ -17,6 +17,7 @@ struct BowQueued {
     uint8_t* mp1 = nullptr;                  // KF1's map-point states, read by each search launch
     std::vector<const orbx_keypoint*> k2;    // per neighbour: keypoints, their number,
     std::vector<int> n2;
+    std::vector<const uint8_t*> mp2;         // its map-point states,
     std::vector<int32_t*> out, out_n;        // the match vector (out_len entries) and its count
     int n1 = 0;                              // KF1's keypoints
     int out_len = 0;
