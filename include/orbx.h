@@ -56,8 +56,10 @@ extern "C" {
  *      additions only.
  *   9: the Sim3 solver of loop closing (orbx_sim3_query, orbx_sim3_ransac,
  *      orbx_sim3_ransac_batch, orbx_sim3_kf, orbx_dev_sim3_candidates);
- *      additions only. */
-#define ORBX_ABI_VERSION 9
+ *      additions only.
+ *  10: the PnP solver of relocalisation (orbx_pnp_query, orbx_pnp_ransac,
+ *      orbx_pnp_ransac_batch, orbx_dev_pnp_candidates); additions only. */
+#define ORBX_ABI_VERSION 10
 int orbx_abi_version(void);
 
 #define ORBX_OK               0
@@ -275,7 +277,10 @@ int orbx_dev_read_matches(orbx_ctx* ctx, int slot, int32_t* matches12, int cap,
  * unchained create_new_map_points call, one per neighbour when chained),
  * "sim3" (the three kernels of orbx_sim3_ransac / _batch /
  * orbx_dev_sim3_candidates, one timed region per call; "sim3.prepare",
- * "sim3.solve", "sim3.check": each kernel on its own).  Returns the number of
+ * "sim3.solve", "sim3.check": each kernel on its own), "pnp" (the kernels of
+ * orbx_pnp_ransac / _batch / orbx_dev_pnp_candidates, one timed region per
+ * call; "pnp.prepare", "pnp.solve", "pnp.check", "pnp.refine": the parts on
+ * their own, the last with the final selection).  Returns the number of
  * timed launches; *avg_ms receives the mean duration. */
 int orbx_dev_kernel_time(orbx_ctx* ctx, const char* name, double* avg_ms,
                          double* total_ms);
@@ -1062,6 +1067,109 @@ int orbx_dev_sim3_candidates(orbx_ctx* ctx, int slot1, const orbx_sim3_kf* kf1, 
                              double probability, int min_inliers, int max_iterations, int n_iter,
                              const int32_t* draws, int32_t* const* matches12, int cap, int* n_matches,
                              int* discarded, orbx_sim3_query* out);
+
+/* PnPsolver (src/PnPsolver.cc): EPnP inside a RANSAC over the map-point
+ * matches of a frame, the step of Tracking::Relocalisation
+ * (src/Tracking.cc:921-947) between SearchByBoW and PoseOptimization.  One
+ * call is one PnPsolver::iterate(n_iter, ...) (:137-230) of a solver built by
+ * the constructor (:39-82) and SetRansacParameters (:93-129): the
+ * correspondences compacted in i order, then every iteration the call can run
+ * at once -- its minimal set from the caller's rand() values (four per
+ * iteration; the removal writes at the drawn value, :171), compute_pose on
+ * four points and CheckInliers -- Refine (:232-277) of the incoming best set
+ * and of every strict record holder among the iterations with count >=
+ * ransac_min_inliers, and the replay of the loop's sequential bookkeeping.
+ * The loop's condition is an or (:154): a call runs max(n_iter,
+ * ransac_max_its - iter_done) iterations unless a Refine returns first.
+ * EPnP is FP64 and follows the reference operation by operation (never
+ * contracted); CheckInliers' mixed float / double expressions follow
+ * orbx_set_fp_contract; the five places that go through OpenCV are defined
+ * in DESIGN.md section 4.
+ * The caller continues a solver by passing the state fields back: iter_done,
+ * best_inliers, best_mask and best_Tcw are read on entry and written at
+ * return, with the draws that follow the iters_run * 4 consumed ones.
+ * Arguments are checked before any device work.  ORBX_ERR_ARG: a null
+ * context, query or required pointer, n_iter < 1, n_draws outside
+ * [max(n_iter, max_iterations - iter_done), 1024], a draw < 0, min_inliers < 1,
+ * max_iterations < 1, iter_done or best_inliers < 0, a probability outside
+ * (0,1), an epsilon outside [0,1] or th2 not positive and finite, nlevels
+ * outside 1..16, an octave outside [0, nlevels), a level sigma2 that is
+ * negative or not finite; ORBX_ERR_UNSUPPORTED: min_set other than 4, more
+ * than 4096 keypoints; ORBX_ERR_CAPACITY: cap < n.  N < ransac_min_inliers
+ * returns ORBX_OK with no_more = 1, found = 0 and no iteration run
+ * (:145-149). */
+#define ORBX_PNP_DEC 135   /* doubles of decomposition taps per hypothesis */
+#define ORBX_PNP_REC 232   /* doubles of one hypothesis record             */
+typedef struct {
+    /* in */
+    const orbx_keypoint* keys; int n;     /* the frame's mvKeysUn (x, y and octave are read)   */
+    const float* pos; const uint8_t* valid;   /* n x 3 GetWorldPos() of vpMapPointMatches[i];
+                                                 n: 0 = NULL or isBad()                         */
+    const float* cam;                     /* fx, fy, cx, cy                                    */
+    const float* sigma2; int nlevels;     /* mvLevelSigma2                                     */
+    double probability; int min_inliers; int max_iterations; int min_set;   /* 0.99, 8, 300, 4 */
+    float epsilon; float th2;             /* 0.4, 5.991 (Relocalisation: 0.99,10,300,4,0.5,5.991) */
+    /* iterate state (in and out) */
+    int iter_done;                        /* mnIterations                                      */
+    int best_inliers;                     /* mnBestInliers                                     */
+    uint8_t* best_mask;                   /* cap >= n: mvbBestInliers by keypoint index        */
+    float best_Tcw[16];                   /* mBestTcw                                          */
+    /* draws */
+    int n_iter;                           /* iterate's nIterations                             */
+    int n_draws; const int32_t* draws;    /* n_draws x 4 successive rand() values              */
+    /* out */
+    int N;                                /* correspondences                                   */
+    int ransac_min_inliers;               /* mRansacMinInliers after SetRansacParameters       */
+    int ransac_max_its;                   /* mRansacMaxIts (0 when N < ransac_min_inliers)     */
+    int iters_run;                        /* iterations executed by this call                  */
+    int no_more;                          /* bNoMore                                           */
+    int found, found_iter;                /* a non-empty return; the iteration whose Refine
+                                             returned, -1 for the mBest* exit (:213-227)       */
+    int n_inliers;                        /* nInliers (0 when !found)                          */
+    int refined;                          /* 1: the return came from Refine                    */
+    float Tcw[16];                        /* the returned pose (untouched when !found)         */
+    uint8_t* inliers; int cap;            /* vbInliers by keypoint index (n written)           */
+    int n_records;                        /* strict record holders among the call's iterations */
+    int best_slot;                        /* the refit that belongs to the best state at
+                                             return: 0 the incoming one, k the k-th record     */
+    /* optional taps per correspondence (cap entries each, N written) */
+    float* p2d; float* p3d; float* max_err; int32_t* kp_index;   /* x 2, x 3, mvMaxError, mvKeyPointIndices */
+    /* optional taps per iteration (n_draws entries each) */
+    int32_t* sets;                        /* x 4: indices into the correspondences             */
+    double* rec;                          /* x ORBX_PNP_REC, FP64: [0,135) the decompositions
+                                             (dc 3, UCt 9, CC_inv 9, rows 8..11 of Ut 48, the
+                                             three cvSolve results 4 + 3 + 5, U and V of ABt per
+                                             beta set 3 x 18), L_6x10 60, rho 6, the betas after
+                                             gauss_newton 3 x 4, R 9, t 3, rep_errors 3, the
+                                             chosen set (1..3), the number of points           */
+    int32_t* count;                       /* mnInliersi                                        */
+    /* optional taps per refit (n_draws + 1 entries: the incoming state, then each record) */
+    double* refit_rec; int32_t* refit_count; int32_t* record_iter;
+} orbx_pnp_query;
+
+int orbx_pnp_ransac(orbx_ctx* ctx, orbx_pnp_query* q);   /* one upload, one read-back */
+/* Relocalisation's candidates in one upload, one launch set and one
+ * read-back; results as B single calls. */
+int orbx_pnp_ransac_batch(orbx_ctx* ctx, int B, orbx_pnp_query* qs);
+
+/* Relocalisation's loop over n candidate keyframes with the frame resident in
+ * `slot` (after orbx_dev_compute_bow): SearchByBoW(pKF, F) as
+ * orbx_dev_search_by_bow queues it, and on the match vectors where the search
+ * left them a solver per candidate: the correspondence at frame keypoint i is
+ * the map point of keyframe keypoint matches_f[k][i] (KFs[k].mp must read 1
+ * there), its position pos[k] (KFs[k].n x 3).  cam, sigma2 and nlevels are
+ * the frame's.  A candidate with n_matches[k] < min_matches (15,
+ * Tracking.cc:914) gets discarded[k] = 1 and runs no RANSAC (N = 0, found =
+ * 0, no_more = 0).  The RANSAC parameters, n_iter, n_draws and the iterate
+ * state are read from out[k] (its keys, pos, valid, cam and sigma2 are
+ * ignored), draws from out[k].draws; out[k].inliers / best_mask hold cap >=
+ * nfeatures entries.  One synchronisation and one read-back.  Results as
+ * orbx_dev_search_by_bow followed by orbx_pnp_ransac_batch on the read-back
+ * matches.  A match whose index or octave is out of range is dropped. */
+int orbx_dev_pnp_candidates(orbx_ctx* ctx, int slot, int n, const orbx_bow_view* KFs, const float* const* pos,
+                            const float* cam, const float* sigma2, int nlevels, float nnratio, int check_ori,
+                            int min_matches, int32_t* const* matches_f, int cap, int* n_matches, int* discarded,
+                            orbx_pnp_query* out);
 
 /* ------------------------------------------------------------------------ */
 /* C. Local bundle adjustment                                                */

@@ -277,6 +277,98 @@ def sim3_result(q, keep, taps=False, n1=None):
     return r
 
 
+class PnpQuery(ctypes.Structure):
+    """orbx_pnp_query (include/orbx.h)."""
+    _fields_ = [("keys", ctypes.c_void_p), ("n", ctypes.c_int), ("pos", ctypes.c_void_p), ("valid", ctypes.c_void_p),
+                ("cam", ctypes.c_void_p), ("sigma2", ctypes.c_void_p), ("nlevels", ctypes.c_int),
+                ("probability", ctypes.c_double), ("min_inliers", ctypes.c_int), ("max_iterations", ctypes.c_int),
+                ("min_set", ctypes.c_int), ("epsilon", ctypes.c_float), ("th2", ctypes.c_float),
+                ("iter_done", ctypes.c_int), ("best_inliers", ctypes.c_int), ("best_mask", ctypes.c_void_p),
+                ("best_Tcw", ctypes.c_float * 16),
+                ("n_iter", ctypes.c_int), ("n_draws", ctypes.c_int), ("draws", ctypes.c_void_p),
+                ("N", ctypes.c_int), ("ransac_min_inliers", ctypes.c_int), ("ransac_max_its", ctypes.c_int),
+                ("iters_run", ctypes.c_int), ("no_more", ctypes.c_int), ("found", ctypes.c_int),
+                ("found_iter", ctypes.c_int), ("n_inliers", ctypes.c_int), ("refined", ctypes.c_int),
+                ("Tcw", ctypes.c_float * 16), ("inliers", ctypes.c_void_p), ("cap", ctypes.c_int),
+                ("n_records", ctypes.c_int), ("best_slot", ctypes.c_int),
+                ("p2d", ctypes.c_void_p), ("p3d", ctypes.c_void_p), ("max_err", ctypes.c_void_p),
+                ("kp_index", ctypes.c_void_p),
+                ("sets", ctypes.c_void_p), ("rec", ctypes.c_void_p), ("count", ctypes.c_void_p),
+                ("refit_rec", ctypes.c_void_p), ("refit_count", ctypes.c_void_p), ("record_iter", ctypes.c_void_p)]
+
+
+PNP_REC = 232
+_PNP_CORR_TAPS = (("p2d", np.float32, 2), ("p3d", np.float32, 3), ("max_err", np.float32, 0), ("kp_index", np.int32, 0))
+_PNP_ITER_TAPS = (("sets", np.int32, 4), ("rec", np.float64, PNP_REC), ("count", np.int32, 0))
+_PNP_REFIT_TAPS = (("refit_rec", np.float64, PNP_REC), ("refit_count", np.int32, 0), ("record_iter", np.int32, 0))
+
+
+def pnp_query(frame, draws, n_iter=5, probability=0.99, min_inliers=8, max_iterations=300, min_set=4, epsilon=0.4,
+              th2=5.991, state=None, taps=False, cap=None):
+    """A PnpQuery over numpy arrays and the arrays it points to (keep both
+    alive while the query is used): (query, keep).  frame: a dict of keys
+    (KEYPOINT), pos (n x 3), valid (n), cam (fx, fy, cx, cy) and sigma2 (the
+    level table); None: the query of a device-resident candidate (cap
+    keypoints; only the parameters, the state and the draws are read).
+    draws: k x 4 rand() values.  state: the dict pnp_result returned for the
+    solver's previous call (iter_done, best_inliers, best_mask, best_Tcw), or
+    None for a fresh solver."""
+    keep = {}
+    q = PnpQuery()
+    if frame is not None:
+        keep["keys"] = np.ascontiguousarray(frame["keys"], KEYPOINT)
+        keep["pos"] = np.ascontiguousarray(frame["pos"], np.float32).reshape(-1, 3)
+        keep["valid"] = np.ascontiguousarray(frame["valid"], np.uint8)
+        keep["cam"] = np.ascontiguousarray(frame["cam"], np.float32).reshape(-1)
+        keep["sigma2"] = np.ascontiguousarray(frame["sigma2"], np.float32).reshape(-1)
+        for name in ("keys", "pos", "valid", "cam", "sigma2"):
+            setattr(q, name, keep[name].ctypes.data)
+        q.n, q.nlevels = len(keep["keys"]), len(keep["sigma2"])
+        if cap is None:
+            cap = q.n
+    q.cap = max(int(cap), 0)
+    keep["draws"] = np.ascontiguousarray(draws, np.int32).reshape(-1, 4)
+    q.draws, q.n_draws, q.n_iter = keep["draws"].ctypes.data, len(keep["draws"]), int(n_iter)
+    q.probability, q.min_inliers, q.max_iterations, q.min_set = probability, min_inliers, max_iterations, min_set
+    q.epsilon, q.th2 = epsilon, th2
+    keep["inliers"] = np.zeros(max(q.cap, 1), np.uint8)
+    keep["best_mask"] = np.zeros(max(q.cap, 1), np.uint8)
+    if state is not None:
+        q.iter_done, q.best_inliers = int(state["iter_done"]), int(state["best_inliers"])
+        m = np.asarray(state["best_mask"], np.uint8)
+        keep["best_mask"][:len(m)] = m
+        q.best_Tcw = (ctypes.c_float * 16)(*np.asarray(state["best_Tcw"], np.float32).reshape(-1))
+    q.inliers, q.best_mask = keep["inliers"].ctypes.data, keep["best_mask"].ctypes.data
+    if taps:
+        m = max(q.n_draws, 1)
+        for name, dt, k in _PNP_CORR_TAPS:
+            keep[name] = np.zeros((max(q.cap, 1), k) if k else max(q.cap, 1), dt)
+        for name, dt, k in _PNP_ITER_TAPS:
+            keep[name] = np.zeros((m, k) if k else m, dt)
+        for name, dt, k in _PNP_REFIT_TAPS:
+            keep[name] = np.zeros((m + 1, k) if k else m + 1, dt)
+        for name, _, _ in _PNP_CORR_TAPS + _PNP_ITER_TAPS + _PNP_REFIT_TAPS:
+            setattr(q, name, keep[name].ctypes.data)
+    return q, keep
+
+
+def pnp_result(q, keep, taps=False, n=None):
+    """The out and state fields (and taps) of a filled PnpQuery as a dict."""
+    n = q.n if n is None else n
+    r = dict(N=q.N, ransac_min_inliers=q.ransac_min_inliers, ransac_max_its=q.ransac_max_its, iters_run=q.iters_run,
+             no_more=q.no_more, found=q.found, found_iter=q.found_iter, n_inliers=q.n_inliers, refined=q.refined,
+             n_records=q.n_records, best_slot=q.best_slot,
+             Tcw=np.array(q.Tcw, np.float32) if q.found else None, inliers=keep["inliers"][:n].copy(),
+             iter_done=q.iter_done, best_inliers=q.best_inliers, best_mask=keep["best_mask"][:n].copy(),
+             best_Tcw=np.array(q.best_Tcw, np.float32))
+    if taps:
+        for name, _, _ in _PNP_CORR_TAPS:
+            r[name] = keep[name][:q.N]
+        for name, _, _ in _PNP_ITER_TAPS + _PNP_REFIT_TAPS:
+            r[name] = keep[name]
+    return r
+
+
 class KfGeom(ctypes.Structure):
     """orbx_kf_geom (include/orbx.h)."""
     _fields_ = [("Rcw", ctypes.c_void_p), ("tcw", ctypes.c_void_p), ("Ow", ctypes.c_void_p), ("cam", ctypes.c_void_p),
@@ -445,6 +537,9 @@ def _declare(L):
         "orbx_dev_create_new_map_points": ([vp, i, vp, vp, i, vp, vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp, i], i),
         "orbx_sim3_ransac": ([vp, vp], i),
         "orbx_sim3_ransac_batch": ([vp, i, vp], i),
+        "orbx_pnp_ransac": ([vp, vp], i),
+        "orbx_pnp_ransac_batch": ([vp, i, vp], i),
+        "orbx_dev_pnp_candidates": ([vp, i, i, vp, vp, vp, vp, i, f, i, i, vp, i, vp, vp, vp], i),
         "orbx_dev_sim3_candidates": ([vp, i, vp, i, vp, vp, f, i, i, ctypes.c_double, i, i, i, vp, vp, i, vp, vp, vp], i),
     }
     for name, (args, res) in sigs.items():
@@ -939,6 +1034,50 @@ class Context:
                                                     cap), "orbx_dev_create_new_map_points")
         out["n_created"], out["n_matches"] = out["n_created"][:n], out["n_matches"][:n]
         return out
+
+    # --- Tracking::Relocalisation: PnPsolver --------------------------------
+    def pnp_ransac(self, frame, draws, taps=False, **kw):
+        """One PnPsolver::iterate call on the device (orbx_pnp_ransac):
+        arguments as pnp_query, a dict of the query's out and state fields
+        (Tcw None when nothing was returned); pass it back as state= to
+        continue the solver."""
+        q, keep = pnp_query(frame, draws, taps=taps, **kw)
+        _check(lib().orbx_pnp_ransac(self._h, ctypes.byref(q)), "orbx_pnp_ransac")
+        return pnp_result(q, keep, taps)
+
+    def pnp_ransac_batch(self, queries, taps=False):
+        """orbx_pnp_ransac_batch over (frame, draws, kwargs) tuples: one
+        upload, one launch set, one read-back."""
+        built = [pnp_query(*a[:2], taps=taps, **(a[2] if len(a) > 2 else {})) for a in queries]
+        arr = (PnpQuery * len(built))(*[b[0] for b in built])
+        _check(lib().orbx_pnp_ransac_batch(self._h, len(built), arr), "orbx_pnp_ransac_batch")
+        return [pnp_result(arr[k], built[k][1], taps) for k in range(len(built))]
+
+    def dev_pnp_candidates(self, slot, kf_views, pos, cam, sigma2, draws, min_matches=15, nnratio=0.75,
+                           check_ori=True, states=None, taps=False, **params):
+        """orbx_dev_pnp_candidates: SearchByBoW(pKF, F) of the keyframe views
+        (orbx_bow_view structures) against the frame in `slot` and a PnPsolver
+        per candidate on the matches where the search left them.  pos: per
+        candidate the keyframe's n x 3 GetWorldPos(); draws: per candidate
+        k x 4 rand() values; states: per candidate None or the previous
+        result; params as pnp_query.  Returns a dict: matches_f, n_matches,
+        discarded, results (one dict per candidate, as pnp_ransac)."""
+        n = len(kf_views)
+        cap = self.nfeatures
+        pos = [np.ascontiguousarray(p, np.float32).reshape(-1, 3) for p in pos]
+        cam = np.ascontiguousarray(cam, np.float32).reshape(-1)
+        sigma2 = np.ascontiguousarray(sigma2, np.float32).reshape(-1)
+        outs = [pnp_query(None, draws[k], state=states[k] if states else None, taps=taps, cap=cap, **params)
+                for k in range(n)]
+        arr = (PnpQuery * max(n, 1))(*[o[0] for o in outs])
+        views = (type(kf_views[0]) * n)(*kf_views) if n else None
+        m = [np.zeros(max(cap, 1), np.int32) for _ in range(n)]
+        nm, disc = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        _check(lib().orbx_dev_pnp_candidates(self._h, slot, n, views, _ptr_array(pos), _ptr(cam), _ptr(sigma2),
+                                             len(sigma2), nnratio, int(check_ori), int(min_matches), _ptr_array(m),
+                                             cap, _ptr(nm), _ptr(disc), arr), "orbx_dev_pnp_candidates")
+        return dict(matches_f=m, n_matches=nm[:n], discarded=disc[:n],
+                    results=[pnp_result(arr[k], outs[k][1], taps, n=max(cap, 1)) for k in range(n)])
 
     # --- LoopClosing::ComputeSim3: Sim3Solver --------------------------------
     def sim3_ransac(self, kf1, kf2, matches12, draws, taps=False, **kw):

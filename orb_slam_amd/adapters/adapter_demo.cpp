@@ -5,6 +5,7 @@
 // sequence), the whole Initializer::Initialize beside orbx_init_reconstruct, brute-force matching, one local BA on a tiny synthetic problem, and
 // Sim3Solver::iterate in chunks of five beside orbx_sim3_ransac fed the same rand() sequence.  Prints one JSON line.  Exit codes: 0 ok,
 // 3 device path unavailable (orbx_error), 1 other failure.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -274,6 +275,105 @@ int main()
                         std::memcmp(sq.t12, solver.GetEstimatedTranslation(), sizeof(sq.t12)) == 0 &&
                         sq.s12 == solver.GetEstimatedScale();
         for (int i = 0; i < 80 && sim3_same; i++) sim3_same = sim3_inl[i] == (sim3_ci[i] != 0);
+        // PnPsolver on a synthetic frame: 80 keypoints with a map point each, seen from a known pose, every fifth
+        // partner unrelated; iterate(5) as Relocalisation drives it until it returns, beside the plain C call fed
+        // the same rand() sequence
+        PnPFrame pf;
+        std::memcpy(pf.cam, camK, sizeof(camK));
+        {
+            float lv = 1.f;
+            for (int l = 0; l < 8; l++, lv *= 1.2f) pf.sigma2.push_back(lv * lv);
+        }
+        std::vector<float> pnp_pos;
+        std::vector<uint8_t> pnp_valid;
+        const double pang = 0.15, pca = std::cos(pang), psa = std::sin(pang), ptt[3] = {0.2, -0.1, 0.3};
+        for (int i = 0; i < 80; i++) {
+            const double Xc[3] = {-2.0 + 4.0 * rnd(), -1.5 + 3.0 * rnd(), 4.0 + 5.0 * rnd()};
+            // Xc = R Xw + t with R a rotation about y: Xw = R^T (Xc - t)
+            const double dx = Xc[0] - ptt[0], dy = Xc[1] - ptt[1], dz = Xc[2] - ptt[2];
+            double Xw[3] = {pca * dx - psa * dz, dy, psa * dx + pca * dz};
+            if (i % 5 == 4) Xw[0] += 1.0 + rnd();
+            KeyPoint kp;
+            std::memset(&kp, 0, sizeof(kp));
+            kp.x = (float)(camK[0] * Xc[0] / Xc[2] + camK[2]);
+            kp.y = (float)(camK[1] * Xc[1] / Xc[2] + camK[3]);
+            kp.size = 31.f;
+            kp.class_id = -1;
+            kp.octave = i % 8;
+            pf.keys.push_back(kp);
+            pnp_pos.insert(pnp_pos.end(), {(float)Xw[0], (float)Xw[1], (float)Xw[2]});
+            pnp_valid.push_back(1);
+        }
+        PnPsolver pnp(pf, pnp_pos, pnp_valid, ex.context());
+        pnp.SetRansacParameters(0.99, 10, 300, 4, 0.5, 5.991);
+        std::srand(1);
+        bool pnp_no_more = false;
+        std::vector<bool> pnp_inl;
+        int pnp_n_inl = 0, pnp_calls = 0;
+        std::vector<float> pnp_T;
+        while (pnp_T.empty() && !pnp_no_more) {
+            pnp_T = pnp.iterate(5, pnp_no_more, pnp_inl, pnp_n_inl);
+            pnp_calls++;
+        }
+        std::srand(1);
+        std::vector<uint8_t> pnp_ci(81), pnp_mask(81);
+        std::vector<int32_t> pnp_draws;
+        orbx_pnp_query pq;
+        std::memset(&pq, 0, sizeof(pq));
+        pq.keys = pf.keys.data();
+        pq.n = 80;
+        pq.pos = pnp_pos.data();
+        pq.valid = pnp_valid.data();
+        pq.cam = pf.cam;
+        pq.sigma2 = pf.sigma2.data();
+        pq.nlevels = 8;
+        pq.probability = 0.99;
+        pq.min_inliers = 10;
+        pq.max_iterations = 300;
+        pq.min_set = 4;
+        pq.epsilon = 0.5f;
+        pq.th2 = 5.991f;
+        pq.n_iter = 5;
+        pq.best_mask = pnp_mask.data();
+        pq.inliers = pnp_ci.data();
+        pq.cap = 80;
+        int pnp_ccalls = 0;
+        do {
+            // as the adapter draws: four values for each iteration the call can run, zeros up to the required length
+            const int pnp_can_run = std::max(5, pnp.mRansacMaxIts - pq.iter_done);
+            pq.n_draws = std::max(5, 300 - pq.iter_done);
+            pnp_draws.assign((size_t)pq.n_draws * 4, 0);
+            for (int i = 0; i < pnp_can_run * 4; i++) pnp_draws[i] = (int32_t)std::rand();
+            pq.draws = pnp_draws.data();
+            check(orbx_pnp_ransac(ex.context(), &pq), "orbx_pnp_ransac");
+            pnp_ccalls++;
+        } while (!pq.found && !pq.no_more);
+        bool pnp_same = pnp_ccalls == pnp_calls && (pq.found != 0) == !pnp_T.empty() && pq.n_inliers == pnp_n_inl &&
+                        pq.iter_done == pnp.mnIterations && pq.best_inliers == pnp.mnBestInliers && pq.N == pnp.N;
+        if (pq.found && pnp_same)
+            pnp_same = (int)pnp_inl.size() == 80 && std::memcmp(pq.Tcw, pnp_T.data(), sizeof(pq.Tcw)) == 0 &&
+                       std::memcmp(pq.best_Tcw, pnp.mBestTcw, sizeof(pq.best_Tcw)) == 0;
+        for (int i = 0; i < 80 && pnp_same && pq.found; i++)
+            pnp_same = pnp_inl[i] == (pnp_ci[i] != 0) && pnp.mvbBestInliers[i] == pnp_mask[i];
+        // the returned pose against the true one
+        double pnp_err = 0.0;
+        if (pq.found) {
+            const double Rt[9] = {pca, 0.0, psa, 0.0, 1.0, 0.0, -psa, 0.0, pca};
+            for (int r = 0; r < 3; r++) {
+                for (int c = 0; c < 3; c++) pnp_err = std::max(pnp_err, std::fabs((double)pq.Tcw[4 * r + c] - Rt[3 * r + c]));
+                pnp_err = std::max(pnp_err, std::fabs((double)pq.Tcw[4 * r + 3] - ptt[r]));
+            }
+        }
+        // find() where no Refine returns: every partner unrelated, so it runs mRansacMaxIts iterations (35 here,
+        // not the 300 passed to SetRansacParameters) and returns nothing
+        std::vector<float> pnp_pos2;
+        for (int i = 0; i < 80; i++) pnp_pos2.insert(pnp_pos2.end(), {(float)(-3.0 + 6.0 * rnd()), (float)(-3.0 + 6.0 * rnd()), (float)(2.0 + 8.0 * rnd())});
+        PnPsolver pnp2(pf, pnp_pos2, pnp_valid, ex.context());
+        pnp2.SetRansacParameters(0.99, 10, 300, 4, 0.5, 5.991);
+        std::srand(3);
+        std::vector<bool> pnp2_inl;
+        int pnp2_n_inl = 0;
+        const std::vector<float> pnp2_T = pnp2.find(pnp2_inl, pnp2_n_inl);
         std::vector<int> mbf;
         const int n_bf = matcher.MatchBruteForce(F1.desc, F2.desc, mbf);
         // tiny BA: 3 keyframes (first fixed) observing 60 points
@@ -340,8 +440,15 @@ int main()
                     rq.n_hyp > 0 && rq.best >= 0 ? rq.n_good[rq.best] : 0, n_tri, scene_ok ? 1 : 0, scene_init.mModel,
                     scene_tri, scene_front, t_cos, r_trace);
         std::printf("\"sim3_same\": %d, \"sim3_n\": %d, \"sim3_found\": %d, \"sim3_inliers\": %d, "
-                    "\"sim3_iterations\": %d, \"sim3_scale\": %.6f}\n",
+                    "\"sim3_iterations\": %d, \"sim3_scale\": %.6f, ",
                     sim3_same ? 1 : 0, sq.N, sq.found, sq.n_inliers, sq.iter_done, (double)solver.GetEstimatedScale());
+        std::printf("\"pnp_same\": %d, \"pnp_n\": %d, \"pnp_found\": %d, \"pnp_refined\": %d, \"pnp_inliers\": %d, "
+                    "\"pnp_iterations\": %d, \"pnp_calls\": %d, \"pnp_pose_error\": %.3g, \"pnp_max_its\": %d, "
+                    "\"pnp_find_found\": %d, \"pnp_find_iterations\": %d, \"pnp_find_max_its\": %d, "
+                    "\"pnp_find_best\": %d}\n",
+                    pnp_same ? 1 : 0, pq.N, pq.found, pq.refined, pq.n_inliers, pq.iter_done, pnp_ccalls, pnp_err,
+                    pq.ransac_max_its == pnp.mRansacMaxIts ? pnp.mRansacMaxIts : -1, pnp2_T.empty() ? 0 : 1,
+                    pnp2.mnIterations, pnp2.mRansacMaxIts, pnp2.mnBestInliers);
         return 0;
     } catch (const orbx_error& e) {
         std::fprintf(stderr, "%s\n", e.what());

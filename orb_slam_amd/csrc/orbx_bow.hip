@@ -568,11 +568,16 @@ extern "C" int orbx_search_for_triangulation_batch(orbx_ctx* ctx, const orbx_bow
 // F) of each candidate keyframe against the extracted frame in `slot`, whose
 // BoW orbx_dev_compute_bow left in HBM.  One upload of the n keyframes, one
 // launch of n workgroups, one readback.
-extern "C" int orbx_dev_search_by_bow(orbx_ctx* ctx, int slot, int n, const orbx_bow_view* KFs, float nnratio,
-                                      int check_ori, int32_t* const* matches_f, int cap, int* n_matches)
+namespace orbx {
+
+// orbx_dev_search_by_bow without its read-back (orbx_bow_queue.h): in *q the
+// frame is side 1 (k1 its keypoints, n1 the slot capacity) and the keyframes
+// side 2 (mp2 / n2 their uploaded map-point states and keypoint counts); out
+// holds the match per frame keypoint.
+int queue_bow_frame(orbx_ctx* ctx, int slot, int n, const orbx_bow_view* KFs, float nnratio, int check_ori,
+                    int32_t* const* matches_f, int cap, size_t extra_bytes, BowQueued* q)
 {
-    if (!ctx || slot < 0 || slot >= ctx->slots || n < 0 || (n > 0 && (!KFs || !matches_f || !n_matches)))
-        return ORBX_ERR_ARG;
+    if (!ctx || slot < 0 || slot >= ctx->slots || n < 0 || (n > 0 && (!KFs || !matches_f))) return ORBX_ERR_ARG;
     if (!ctx->bow_dev || slot >= (int)ctx->bow_ready.size() || !ctx->bow_ready[slot]) return ORBX_ERR_ARG;
     const int nf = ctx->bow_nf;
     if (n > 0 && cap < nf) return ORBX_ERR_CAPACITY;
@@ -598,6 +603,7 @@ extern "C" int orbx_dev_search_by_bow(orbx_ctx* ctx, int slot, int n, const orbx
         o[k].oo = take_out(s, nf);
     }
     const Region<BowSlotJob> o_jobs = s.take<BowSlotJob>(n);
+    const Region<uint8_t> o_extra = s.take<uint8_t>(extra_bytes);
     int r = s.open();
     if (r != ORBX_OK) return r;
     const SlotBowDev& b = ctx->bow;
@@ -629,8 +635,35 @@ extern "C" int orbx_dev_search_by_bow(orbx_ctx* ctx, int slot, int n, const orbx
     hipLaunchKernelGGL(k_bow_match_slot, dim3(n), dim3(kBlock), 0, ctx->stream, s.dev(o_jobs));
     timer_end(ctx, "bow_match_slot");
     ORBX_HIP_CHECK(hipGetLastError());
-    for (int k = 0; k < n; k++)
-        if ((r = s.get(matches_f[k], o[k].oo.out)) || (r = s.get(&n_matches[k], o[k].oo.n))) return r;
+    q->k1 = slot_frame_dev(ctx, slot, nullptr).kps;
+    q->mp1 = nullptr;
+    q->n1 = nf;
+    q->out_len = nf;
+    q->extra = s.dev(o_extra);
+    q->k2.assign(n, nullptr);
+    q->n2.resize(n);
+    q->mp2.resize(n);
+    q->out.resize(n);
+    q->out_n.resize(n);
+    for (int k = 0; k < n; k++) {
+        q->n2[k] = KFs[k].n;
+        q->mp2[k] = s.dev(o[k].s1.m);
+        q->out[k] = s.dev(o[k].oo.out);
+        q->out_n[k] = s.dev(o[k].oo.n);
+    }
+    return ORBX_OK;
+}
+
+}  // namespace orbx
+
+extern "C" int orbx_dev_search_by_bow(orbx_ctx* ctx, int slot, int n, const orbx_bow_view* KFs, float nnratio,
+                                      int check_ori, int32_t* const* matches_f, int cap, int* n_matches)
+{
+    if (!ctx || (n > 0 && !n_matches)) return ORBX_ERR_ARG;
+    BowQueued q;
+    int r = queue_bow_frame(ctx, slot, n, KFs, nnratio, check_ori, matches_f, cap, 0, &q);
+    if (r != ORBX_OK || n == 0) return r;
+    if ((r = read_bow_queued(ctx, q, q.out_len, matches_f, n_matches)) != ORBX_OK) return r;
     ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     for (int k = 0; k < n; k++)
         if (n_matches[k] < 0) return ORBX_ERR_UNSUPPORTED;

@@ -38,6 +38,14 @@ int queue_bow_batch(orbx_ctx* ctx, const orbx_bow_view* V1, int n, const orbx_bo
 int queue_bow_slots(orbx_ctx* ctx, int mode, int slot1, const uint8_t* mp1, int n, const int* slots2,
                     const uint8_t* const* mp2s, float nnratio, int check_ori, const float* F12s, const float* sigma2s,
                     int nlevels, int cap, size_t extra_bytes, const BowAfter* after, BowQueued* q);
+// orbx_dev_search_by_bow (SearchByBoW(KF, F) of n keyframe views against the
+// frame in `slot`) without its read-back: in *q the frame is side 1 (k1 its
+// keypoints, n1 = out_len the slot capacity, mp1 unused) and keyframe k side 2
+// (mp2[k] its uploaded map-point states, n2[k] its keypoints; k2 unused);
+// out[k] holds the keyframe's keypoint per frame keypoint.  matches_f: the
+// caller's n result arrays, checked with the other arguments.
+int queue_bow_frame(orbx_ctx* ctx, int slot, int n, const orbx_bow_view* KFs, float nnratio, int check_ori,
+                    int32_t* const* matches_f, int cap, size_t extra_bytes, BowQueued* q);
 // The read-back of a queued batch: `len` entries of every match vector and
 // the counts, as asynchronous copies on the context stream.
 int read_bow_queued(orbx_ctx* ctx, const BowQueued& q, int len, int32_t* const* outs, int* n_outs);
