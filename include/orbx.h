@@ -58,8 +58,11 @@ extern "C" {
  *      orbx_sim3_ransac_batch, orbx_sim3_kf, orbx_dev_sim3_candidates);
  *      additions only.
  *  10: the PnP solver of relocalisation (orbx_pnp_query, orbx_pnp_ransac,
- *      orbx_pnp_ransac_batch, orbx_dev_pnp_candidates); additions only. */
-#define ORBX_ABI_VERSION 10
+ *      orbx_pnp_ransac_batch, orbx_dev_pnp_candidates); additions only.
+ *  11: the Sim3 optimisation of loop closing (orbx_sim3_opt_query,
+ *      orbx_optimize_sim3, orbx_optimize_sim3_batch, orbx_dev_optimize_sim3);
+ *      additions only. */
+#define ORBX_ABI_VERSION 11
 int orbx_abi_version(void);
 
 #define ORBX_OK               0
@@ -280,8 +283,9 @@ int orbx_dev_read_matches(orbx_ctx* ctx, int slot, int32_t* matches12, int cap,
  * "sim3.solve", "sim3.check": each kernel on its own), "pnp" (the kernels of
  * orbx_pnp_ransac / _batch / orbx_dev_pnp_candidates, one timed region per
  * call; "pnp.prepare", "pnp.solve", "pnp.check", "pnp.refine": the parts on
- * their own, the last with the final selection).  Returns the number of
- * timed launches; *avg_ms receives the mean duration. */
+ * their own, the last with the final selection), "sim3opt" (the one kernel
+ * of orbx_optimize_sim3 / _batch / orbx_dev_optimize_sim3).  Returns the
+ * number of timed launches; *avg_ms receives the mean duration. */
 int orbx_dev_kernel_time(orbx_ctx* ctx, const char* name, double* avg_ms,
                          double* total_ms);
 int orbx_dev_kernel_time_enable(orbx_ctx* ctx, int enable);
@@ -1067,6 +1071,104 @@ int orbx_dev_sim3_candidates(orbx_ctx* ctx, int slot1, const orbx_sim3_kf* kf1, 
                              double probability, int min_inliers, int max_iterations, int n_iter,
                              const int32_t* draws, int32_t* const* matches12, int cap, int* n_matches,
                              int* discarded, orbx_sim3_query* out);
+
+/* Optimizer::OptimizeSim3 (src/Optimizer.cc:791-987), step 4 of
+ * LoopClosing::ComputeSim3 (src/LoopClosing.cc:328, th2 = 10) between
+ * orbx_search_by_sim3 and the final projection search: g2o's Levenberg over
+ * one free VertexSim3Expmap (7 DoF, _fix_scale false) against fixed points
+ * through an EdgeSim3ProjectXYZ (e12) and an EdgeInverseSim3ProjectXYZ (e21)
+ * per correspondence, Huber with delta = sqrtf(th2), BlockSolverX +
+ * LinearSolverDense (Eigen LDLT, 7 x 7), numeric central-difference Jacobians
+ * with delta 1e-9 (the reference's linearizeOplus is commented out), every sum
+ * in g2o's edge order e12_0, e21_0, e12_1, ...  Two rounds: optimize(5); every
+ * pair tested with the stored errors of the last computeActiveErrors (the last
+ * LM trial, accepted or not) as chi2(e12) > th2 || chi2(e21) > th2 (a NaN keeps
+ * the pair), failing pairs cleared in matches12; fewer than 10 left: return 0
+ * at once with the Sim3 untouched (returned_early = 1); else optimize(n_bad > 0
+ * ? 10 : 5) over the rest, the same test again (clearing only), n_in counted.
+ * A correspondence exists for i when matches12[i] >= 0, valid1[i] and
+ * valid2[matches12[i]] (map points that exist and are not isBad()); it reads
+ * keys1[i], pos1[i], keys2[i2], pos2[i2].  The camera-frame points are
+ * Rcw * X + tcw in the float arithmetic of orbx_sim3_ransac, widened.
+ * All arithmetic is FP64 without contraction; DESIGN.md section 4 says which
+ * parts are reproducible bit for bit.
+ * Arguments are checked before any device work.  ORBX_ERR_ARG: a null
+ * context, query or required pointer, n1 or n2 < 0, a match index >= n2, an
+ * octave outside [0, nlevels), nlevels outside 1..16, th2 not positive and
+ * finite, a non-finite initial Sim3; ORBX_ERR_UNSUPPORTED: more than 4096
+ * keypoints; ORBX_ERR_CAPACITY: a per-correspondence tap with cap < n_corr.
+ * Zero correspondences return ORBX_OK with n_in = 0 and returned_early = 1. */
+#define ORBX_SIM3_OPT_MAX_LM 15       /* optimize(5) + optimize(10) */
+#define ORBX_SIM3_OPT_MAX_TRIALS 10   /* Levenberg trials per iteration */
+typedef struct {
+    /* in */
+    const orbx_keypoint* keys1; int n1;   /* pKF1's mvKeysUn (x, y and octave are read)        */
+    const orbx_keypoint* keys2; int n2;   /* pKF2's                                            */
+    int32_t* matches12;                   /* n1, in and out: >= 0 the KF2 keypoint i2 =
+                                             GetIndexInKeyFrame(pKF2) of vpMatches1[i]; -1 NULL;
+                                             any other negative: a non-NULL entry whose point KF2
+                                             does not observe (skipped and left as it is).  Out:
+                                             -1 where a check cleared the entry                */
+    const float* pos1; const uint8_t* valid1;   /* n1 x 3 GetWorldPos(), n1: 1 = KF1's own map
+                                                   point at i exists and is not bad             */
+    const float* pos2; const uint8_t* valid2;   /* n2 x 3, n2: the matched point is not bad     */
+    const float* T1w; const float* T2w;   /* 16 each: the keyframes' Tcw, row-major            */
+    const float* cam1; const float* cam2; /* fx, fy, cx, cy                                    */
+    const float* inv_sigma2_1;            /* nlevels: pKF1's mvInvLevelSigma2 (e12's information,
+                                             src/Optimizer.cc:894)                             */
+    const float* sigma2_2;                /* nlevels: pKF2's mvLevelSigma2 -- the level's sigma2,
+                                             NOT its inverse: the reference calls GetSigma2 for
+                                             e21 (src/Optimizer.cc:912), and so does this       */
+    int nlevels;
+    float R12[9], t12[3], s12;            /* in: the Sim3 as orbx_sim3_query returns it; out: the
+                                             optimised one (untouched when returned_early)     */
+    float th2;                            /* 10 (src/LoopClosing.cc:328)                       */
+    /* out */
+    int n_in;                             /* the return value of OptimizeSim3                  */
+    int n_corr, n_bad;                    /* nCorrespondences; nBad of the first check         */
+    int returned_early;                   /* the nCorrespondences - nBad < 10 exit             */
+    double q12[4], t12d[3], s12d;         /* g2oS12 (x, y, z, w); untouched when returned_early */
+    int iterations[2], trials[2], not_posdef[2];   /* per optimize(): LM iterations, trials and
+                                                      LDLT failures, as orbx_pose_stats        */
+    /* optional taps (may be NULL) per correspondence, cap entries each, n_corr written */
+    int cap;
+    int32_t* corr_index;                  /* vnIndexEdge                                       */
+    float* x3dc1; float* x3dc2;           /* x 3: P3D1c, P3D2c                                 */
+    double* edge_err;                     /* x 4: e12, e21 errors at round 0's first iteration */
+    double* edge_J;                       /* x 28: their 2 x 7 Jacobians, row-major, e12 first */
+    double* edge_chi2;                    /* 2 x cap x 2: chi2 of (e12, e21) as each check tested
+                                             it (untouched where a pair was not tested)        */
+    /* optional taps per LM iteration, ORBX_SIM3_OPT_MAX_LM entries each, both rounds in order */
+    int n_lm;                             /* out: iterations[0] + iterations[1]                */
+    double* it_est;                       /* x 8: the estimate at the iteration's start (q, t, s) */
+    double* it_chi2;                      /* the robust chi2 there                             */
+    double* it_H;                         /* x 28: H's lower triangle, row-major packed        */
+    double* it_b;                         /* x 7                                               */
+    double* it_lambda;                    /* lambda after the iteration                        */
+    int32_t* it_trials;
+    double* it_dx;                        /* x ORBX_SIM3_OPT_MAX_TRIALS x 7: each trial's step
+                                             (zeros where the LDLT failed and past the last)   */
+    double* check_est;                    /* 2 x 8: the estimate of the last trial of each round,
+                                             where the tested errors were computed             */
+} orbx_sim3_opt_query;
+
+int orbx_optimize_sim3(orbx_ctx* ctx, orbx_sim3_opt_query* q);   /* one upload, one read-back */
+/* Every candidate whose RANSAC returned, in one upload, one launch and one
+ * read-back; results as B single calls.  The reference optimises candidate
+ * after candidate until one keeps 20 (src/LoopClosing.cc:328-336); the caller
+ * takes the first such in the reference's order. */
+int orbx_optimize_sim3_batch(orbx_ctx* ctx, int B, orbx_sim3_opt_query* qs);
+/* The same between device-resident frames: keypoints and octaves are read
+ * from slot1 and slots2[k] as orbx_dev_sim3_candidates reads them; kf1 / kf2s
+ * carry what does not live in a slot (mp: 1 = a good map point; sigma2 is
+ * read from kf2s[k] only), inv_sigma2_1 (nlevels) is KF1's mvInvLevelSigma2.
+ * out[k]: matches12 (one entry per keypoint of slot1), R12 / t12 / s12, th2,
+ * cap and the tap pointers are read, the out fields written; its other in
+ * fields are ignored.  Results are byte-equal to orbx_optimize_sim3_batch on
+ * the slots' keypoints.  An octave outside [0, nlevels) in a slot is clamped;
+ * nlevels is the extractor's (ORBX_ERR_ARG otherwise). */
+int orbx_dev_optimize_sim3(orbx_ctx* ctx, int slot1, const orbx_sim3_kf* kf1, const float* inv_sigma2_1, int n,
+                           const int* slots2, const orbx_sim3_kf* kf2s, orbx_sim3_opt_query* out);
 
 /* PnPsolver (src/PnPsolver.cc): EPnP inside a RANSAC over the map-point
  * matches of a frame, the step of Tracking::Relocalisation

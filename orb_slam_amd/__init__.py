@@ -277,6 +277,112 @@ def sim3_result(q, keep, taps=False, n1=None):
     return r
 
 
+class Sim3OptQuery(ctypes.Structure):
+    """orbx_sim3_opt_query (include/orbx.h)."""
+    _fields_ = [("keys1", ctypes.c_void_p), ("n1", ctypes.c_int), ("keys2", ctypes.c_void_p), ("n2", ctypes.c_int),
+                ("matches12", ctypes.c_void_p),
+                ("pos1", ctypes.c_void_p), ("valid1", ctypes.c_void_p),
+                ("pos2", ctypes.c_void_p), ("valid2", ctypes.c_void_p),
+                ("T1w", ctypes.c_void_p), ("T2w", ctypes.c_void_p), ("cam1", ctypes.c_void_p), ("cam2", ctypes.c_void_p),
+                ("inv_sigma2_1", ctypes.c_void_p), ("sigma2_2", ctypes.c_void_p), ("nlevels", ctypes.c_int),
+                ("R12", ctypes.c_float * 9), ("t12", ctypes.c_float * 3), ("s12", ctypes.c_float),
+                ("th2", ctypes.c_float),
+                ("n_in", ctypes.c_int), ("n_corr", ctypes.c_int), ("n_bad", ctypes.c_int),
+                ("returned_early", ctypes.c_int),
+                ("q12", ctypes.c_double * 4), ("t12d", ctypes.c_double * 3), ("s12d", ctypes.c_double),
+                ("iterations", ctypes.c_int * 2), ("trials", ctypes.c_int * 2), ("not_posdef", ctypes.c_int * 2),
+                ("cap", ctypes.c_int), ("corr_index", ctypes.c_void_p),
+                ("x3dc1", ctypes.c_void_p), ("x3dc2", ctypes.c_void_p),
+                ("edge_err", ctypes.c_void_p), ("edge_J", ctypes.c_void_p), ("edge_chi2", ctypes.c_void_p),
+                ("n_lm", ctypes.c_int),
+                ("it_est", ctypes.c_void_p), ("it_chi2", ctypes.c_void_p), ("it_H", ctypes.c_void_p),
+                ("it_b", ctypes.c_void_p), ("it_lambda", ctypes.c_void_p), ("it_trials", ctypes.c_void_p),
+                ("it_dx", ctypes.c_void_p), ("check_est", ctypes.c_void_p)]
+
+
+SIM3_OPT_MAX_LM, SIM3_OPT_MAX_TRIALS = 15, 10
+_SIM3OPT_CORR_TAPS = (("corr_index", np.int32, 0), ("x3dc1", np.float32, 3), ("x3dc2", np.float32, 3),
+                      ("edge_err", np.float64, 4), ("edge_J", np.float64, 28))
+_SIM3OPT_ITER_TAPS = (("it_est", np.float64, 8), ("it_chi2", np.float64, 0), ("it_H", np.float64, 28),
+                      ("it_b", np.float64, 7), ("it_lambda", np.float64, 0), ("it_trials", np.int32, 0),
+                      ("it_dx", np.float64, (SIM3_OPT_MAX_TRIALS, 7)))
+
+
+def sim3_opt_query(kf1, kf2, matches12, R12, t12, s12, th2=10.0, taps=False, cap=None):
+    """A Sim3OptQuery over numpy arrays and the arrays it points to (keep both
+    alive while the query is used): (query, keep).  kf1 / kf2: dicts of keys
+    (KEYPOINT), pos (n x 3), valid (n), Tcw (4 x 4), cam (fx, fy, cx, cy);
+    kf1 also inv_sigma2 (its mvInvLevelSigma2), kf2 sigma2 (its mvLevelSigma2
+    -- what the reference reads for e21).  matches12 is copied: the copy is the
+    in / out array.  kf1 None: the query of a device-resident candidate
+    (matches12 holds cap entries)."""
+    keep = {}
+    q = Sim3OptQuery()
+    if kf1 is not None:
+        for side, kf in (("1", kf1), ("2", kf2)):
+            keep["keys" + side] = np.ascontiguousarray(kf["keys"], KEYPOINT)
+            keep["pos" + side] = np.ascontiguousarray(kf["pos"], np.float32).reshape(-1, 3)
+            keep["valid" + side] = np.ascontiguousarray(kf["valid"], np.uint8)
+            keep["T" + side + "w"] = np.ascontiguousarray(kf["Tcw"], np.float32).reshape(-1)
+            keep["cam" + side] = np.ascontiguousarray(kf["cam"], np.float32).reshape(-1)
+            for name in ("keys", "pos", "valid"):
+                setattr(q, name + side, keep[name + side].ctypes.data)
+            for name in ("T" + side + "w", "cam" + side):
+                setattr(q, name, keep[name].ctypes.data)
+        keep["inv_sigma2_1"] = np.ascontiguousarray(kf1["inv_sigma2"], np.float32).reshape(-1)
+        keep["sigma2_2"] = np.ascontiguousarray(kf2["sigma2"], np.float32).reshape(-1)
+        q.inv_sigma2_1, q.sigma2_2 = keep["inv_sigma2_1"].ctypes.data, keep["sigma2_2"].ctypes.data
+        q.n1, q.n2 = len(keep["keys1"]), len(keep["keys2"])
+        q.nlevels = min(len(keep["inv_sigma2_1"]), len(keep["sigma2_2"]))
+    keep["matches12"] = np.array(matches12, np.int32).reshape(-1)
+    q.matches12 = keep["matches12"].ctypes.data
+    q.R12[:] = np.asarray(R12, np.float32).reshape(9).tolist()
+    q.t12[:] = np.asarray(t12, np.float32).reshape(3).tolist()
+    q.s12, q.th2 = float(s12), float(th2)
+    if cap is None:
+        cap = len(keep["matches12"])
+    q.cap = max(int(cap), 0)
+    if taps:
+        m = max(q.cap, 1)
+        for name, dt, k in _SIM3OPT_CORR_TAPS:
+            keep[name] = np.zeros((m, k) if k else m, dt)
+            setattr(q, name, keep[name].ctypes.data)
+        keep["edge_chi2"] = np.full((2, m, 2), np.nan)
+        q.edge_chi2 = keep["edge_chi2"].ctypes.data
+        for name, dt, k in _SIM3OPT_ITER_TAPS:
+            shape = (SIM3_OPT_MAX_LM,) + (k if isinstance(k, tuple) else ((k,) if k else ()))
+            keep[name] = np.zeros(shape, dt)
+            setattr(q, name, keep[name].ctypes.data)
+        keep["check_est"] = np.zeros((2, 8))
+        q.check_est = keep["check_est"].ctypes.data
+    return q, keep
+
+
+def sim3_opt_result(q, keep, taps=False):
+    """The out fields (and taps) of a filled Sim3OptQuery as a dict: matches12
+    (out), n_in (OptimizeSim3's return value), n_corr, n_bad, returned_early,
+    q12 / t12d / s12d and the float R12 / t12 / s12 (None on the early exit,
+    where the reference leaves g2oS12 alone), iterations / trials / not_posdef
+    per round."""
+    done = not q.returned_early
+    r = dict(matches12=keep["matches12"], n_in=q.n_in, n_corr=q.n_corr, n_bad=q.n_bad,
+             returned_early=q.returned_early,
+             q12=np.array(q.q12) if done else None, t12d=np.array(q.t12d) if done else None,
+             s12d=float(q.s12d) if done else None,
+             R12=np.array(q.R12, np.float32).reshape(3, 3) if done else None,
+             t12=np.array(q.t12, np.float32) if done else None, s12=np.float32(q.s12) if done else None,
+             iterations=list(q.iterations), trials=list(q.trials), not_posdef=list(q.not_posdef))
+    if taps:
+        r["n_lm"] = q.n_lm
+        for name, _, _ in _SIM3OPT_CORR_TAPS:
+            r[name] = keep[name][:q.n_corr]
+        r["edge_chi2"] = keep["edge_chi2"][:, :q.n_corr]
+        for name, _, _ in _SIM3OPT_ITER_TAPS:
+            r[name] = keep[name][:q.n_lm]
+        r["check_est"] = keep["check_est"]
+    return r
+
+
 class PnpQuery(ctypes.Structure):
     """orbx_pnp_query (include/orbx.h)."""
     _fields_ = [("keys", ctypes.c_void_p), ("n", ctypes.c_int), ("pos", ctypes.c_void_p), ("valid", ctypes.c_void_p),
@@ -541,6 +647,9 @@ def _declare(L):
         "orbx_pnp_ransac_batch": ([vp, i, vp], i),
         "orbx_dev_pnp_candidates": ([vp, i, i, vp, vp, vp, vp, i, f, i, i, vp, i, vp, vp, vp], i),
         "orbx_dev_sim3_candidates": ([vp, i, vp, i, vp, vp, f, i, i, ctypes.c_double, i, i, i, vp, vp, i, vp, vp, vp], i),
+        "orbx_optimize_sim3": ([vp, vp], i),
+        "orbx_optimize_sim3_batch": ([vp, i, vp], i),
+        "orbx_dev_optimize_sim3": ([vp, i, vp, vp, i, vp, vp, vp], i),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(L, name)
@@ -1141,6 +1250,52 @@ class Context:
                "orbx_dev_sim3_candidates")
         return dict(matches12=m12, n_matches=nm[:n], discarded=disc[:n],
                     results=[sim3_result(arr[k], outs[k][1], taps, n1=max(cap, 1)) for k in range(n)])
+
+    # --- LoopClosing::ComputeSim3: Optimizer::OptimizeSim3 --------------------
+    def optimize_sim3(self, kf1, kf2, matches12, R12, t12, s12, th2=10.0, taps=False):
+        """Optimizer::OptimizeSim3 on the device (orbx_optimize_sim3):
+        arguments as sim3_opt_query, a dict as sim3_opt_result (matches12 is
+        the cleared copy; the caller's array is left alone)."""
+        q, keep = sim3_opt_query(kf1, kf2, matches12, R12, t12, s12, th2=th2, taps=taps)
+        _check(lib().orbx_optimize_sim3(self._h, ctypes.byref(q)), "orbx_optimize_sim3")
+        return sim3_opt_result(q, keep, taps)
+
+    def optimize_sim3_batch(self, queries, th2=10.0, taps=False):
+        """orbx_optimize_sim3_batch over (kf1, kf2, matches12, R12, t12, s12)
+        tuples: one upload, one launch, one read-back; a list of dicts."""
+        built = [sim3_opt_query(*a[:6], th2=th2, taps=taps) for a in queries]
+        arr = (Sim3OptQuery * len(built))(*[b[0] for b in built])
+        _check(lib().orbx_optimize_sim3_batch(self._h, len(built), arr), "orbx_optimize_sim3_batch")
+        return [sim3_opt_result(arr[k], built[k][1], taps) for k in range(len(built))]
+
+    def dev_optimize_sim3(self, slot1, kf1, slots2, kf2s, matches12, sims, th2=10.0, taps=False):
+        """orbx_dev_optimize_sim3: OptimizeSim3 of the keyframe in slot1
+        against those in slots2, keypoints and octaves read from the slots.
+        kf1 / kf2s: dicts of mp (states 0, 1, 2 per keypoint), pos, Tcw, cam;
+        kf1 also inv_sigma2, each of kf2s sigma2.  matches12: one array per
+        candidate (an entry per keypoint of slot1); sims: (R12, t12, s12) per
+        candidate.  A list of dicts as optimize_sim3."""
+        n = len(slots2)
+
+        def kf(g, table):
+            keep = dict(mp=np.ascontiguousarray(g["mp"], np.uint8), pos=np.ascontiguousarray(g["pos"], np.float32),
+                        Tcw=np.ascontiguousarray(g["Tcw"], np.float32).reshape(-1),
+                        cam=np.ascontiguousarray(g["cam"], np.float32).reshape(-1),
+                        sigma2=np.ascontiguousarray(g[table], np.float32).reshape(-1))
+            k = Sim3Kf()
+            for name, a in keep.items():
+                setattr(k, name, a.ctypes.data)
+            k.nlevels = int(g.get("nlevels", len(keep["sigma2"])))
+            return k, keep
+        K1, keep1 = kf(kf1, "inv_sigma2")
+        built2 = [kf(g, "sigma2") for g in kf2s]
+        K2 = (Sim3Kf * max(n, 1))(*[b[0] for b in built2])
+        outs = [sim3_opt_query(None, None, matches12[k], *sims[k], th2=th2, taps=taps) for k in range(n)]
+        arr = (Sim3OptQuery * max(n, 1))(*[o[0] for o in outs])
+        s2 = np.ascontiguousarray(list(slots2) + [0], np.int32)
+        _check(lib().orbx_dev_optimize_sim3(self._h, slot1, ctypes.byref(K1), _ptr(keep1["sigma2"]), n, _ptr(s2), K2,
+                                            arr), "orbx_dev_optimize_sim3")
+        return [sim3_opt_result(arr[k], outs[k][1], taps) for k in range(n)]
 
     @property
     def handle(self):

@@ -3,7 +3,8 @@
 // SearchForInitialization between them, the initialisation models of those
 // matches (Initializer::FindModels beside the plain C call fed the same rand()
 // sequence), the whole Initializer::Initialize beside orbx_init_reconstruct, brute-force matching, one local BA on a tiny synthetic problem, and
-// Sim3Solver::iterate in chunks of five beside orbx_sim3_ransac fed the same rand() sequence.  Prints one JSON line.  Exit codes: 0 ok,
+// Sim3Solver::iterate in chunks of five beside orbx_sim3_ransac fed the same rand() sequence, Optimizer::OptimizeSim3
+// beside orbx_optimize_sim3.  Prints one JSON line.  Exit codes: 0 ok,
 // 3 device path unavailable (orbx_error), 1 other failure.
 #include <algorithm>
 #include <cmath>
@@ -275,6 +276,52 @@ int main()
                         std::memcmp(sq.t12, solver.GetEstimatedTranslation(), sizeof(sq.t12)) == 0 &&
                         sq.s12 == solver.GetEstimatedScale();
         for (int i = 0; i < 80 && sim3_same; i++) sim3_same = sim3_inl[i] == (sim3_ci[i] != 0);
+        // Optimizer::OptimizeSim3 on the same pair, started from the solver's estimate as ComputeSim3 does
+        // (src/LoopClosing.cc:324-328): the keypoints at the projections of each keyframe's own points, so the 64
+        // true pairs fit and the 16 unrelated ones are gross; the adapter beside the plain C call
+        Sim3KeyFrame ok[2] = {sk[0], sk[1]};
+        for (int side = 0; side < 2; side++)
+            for (int i = 0; i < 80; i++) {
+                const float* X = &ok[side].pos[3 * i];
+                ok[side].keys[i].x = camK[0] * X[0] / X[2] + camK[2];
+                ok[side].keys[i].y = camK[1] * X[1] / X[2] + camK[3];
+            }
+        std::vector<int> opt_m(sim3_m);
+        opt_m[7] = -2;    // a point KF2 does not observe: skipped and left as it is
+        Sim3 gS12(sq.R12, sq.t12, sq.s12);
+        const int opt_n_in = Optimizer::OptimizeSim3(ex.context(), ok[0], ok[1], opt_m, gS12, 10.f);
+        const Sim3 gProduct = gS12 * Sim3();   // gScm * gSmw with an identity: the same transformation
+        std::vector<int32_t> opt_m32(sim3_m.begin(), sim3_m.end());
+        opt_m32[7] = -2;
+        std::vector<float> opt_inv;
+        for (float v : ok[0].sigma2) opt_inv.push_back(1.0f / v);
+        orbx_sim3_opt_query oq;
+        std::memset(&oq, 0, sizeof(oq));
+        oq.keys1 = ok[0].keys.data();
+        oq.keys2 = ok[1].keys.data();
+        oq.n1 = oq.n2 = 80;
+        oq.matches12 = opt_m32.data();
+        oq.pos1 = ok[0].pos.data();
+        oq.pos2 = ok[1].pos.data();
+        oq.valid1 = ok[0].valid.data();
+        oq.valid2 = ok[1].valid.data();
+        oq.T1w = ok[0].Tcw;
+        oq.T2w = ok[1].Tcw;
+        oq.cam1 = ok[0].cam;
+        oq.cam2 = ok[1].cam;
+        oq.inv_sigma2_1 = opt_inv.data();
+        oq.sigma2_2 = ok[1].sigma2.data();
+        oq.nlevels = 8;
+        std::memcpy(oq.R12, sq.R12, sizeof(oq.R12));
+        std::memcpy(oq.t12, sq.t12, sizeof(oq.t12));
+        oq.s12 = sq.s12;
+        oq.th2 = 10.f;
+        check(orbx_optimize_sim3(ex.context(), &oq), "orbx_optimize_sim3");
+        bool sim3opt_same = oq.n_in == opt_n_in && !oq.returned_early && opt_m[7] == -2 &&
+                            std::memcmp(oq.q12, gS12.q, sizeof(oq.q12)) == 0 &&
+                            std::memcmp(oq.t12d, gS12.t, sizeof(oq.t12d)) == 0 && oq.s12d == gS12.s &&
+                            std::memcmp(gProduct.q, gS12.q, sizeof(gS12.q)) == 0 && gProduct.s == gS12.s;
+        for (int i = 0; i < 80 && sim3opt_same; i++) sim3opt_same = opt_m[i] == opt_m32[i];
         // PnPsolver on a synthetic frame: 80 keypoints with a map point each, seen from a known pose, every fifth
         // partner unrelated; iterate(5) as Relocalisation drives it until it returns, beside the plain C call fed
         // the same rand() sequence
@@ -442,6 +489,9 @@ int main()
         std::printf("\"sim3_same\": %d, \"sim3_n\": %d, \"sim3_found\": %d, \"sim3_inliers\": %d, "
                     "\"sim3_iterations\": %d, \"sim3_scale\": %.6f, ",
                     sim3_same ? 1 : 0, sq.N, sq.found, sq.n_inliers, sq.iter_done, (double)solver.GetEstimatedScale());
+        std::printf("\"sim3opt_same\": %d, \"sim3opt_n_in\": %d, \"sim3opt_n_corr\": %d, \"sim3opt_n_bad\": %d, "
+                    "\"sim3opt_scale\": %.9f, ",
+                    sim3opt_same ? 1 : 0, opt_n_in, oq.n_corr, oq.n_bad, gS12.s);
         std::printf("\"pnp_same\": %d, \"pnp_n\": %d, \"pnp_found\": %d, \"pnp_refined\": %d, \"pnp_inliers\": %d, "
                     "\"pnp_iterations\": %d, \"pnp_calls\": %d, \"pnp_pose_error\": %.3g, \"pnp_max_its\": %d, "
                     "\"pnp_find_found\": %d, \"pnp_find_iterations\": %d, \"pnp_find_max_its\": %d, "

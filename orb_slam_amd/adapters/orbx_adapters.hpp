@@ -6,7 +6,7 @@
 //
 //   ORB_SLAM_AMD::ORBextractor   <- ORB_SLAM::ORBextractor   include/ORBextractor.h:32-77
 //   ORB_SLAM_AMD::ORBmatcher     <- ORB_SLAM::ORBmatcher     include/ORBmatcher.h:37-107
-//   ORB_SLAM_AMD::Optimizer      <- ORB_SLAM::Optimizer::LocalBundleAdjustment
+//   ORB_SLAM_AMD::Optimizer      <- ORB_SLAM::Optimizer::LocalBundleAdjustment, PoseOptimization, OptimizeSim3
 //                                                           include/Optimizer.h:42
 //   ORB_SLAM_AMD::Initializer    <- ORB_SLAM::Initializer    include/Initializer.h:33-96
 //                                   (FindHomography + FindFundamental)
@@ -354,8 +354,16 @@ struct PoseFrame {
     orbx_pose_stats stats{};
 };
 
+struct Sim3KeyFrame;   // below, with Sim3Solver
+struct Sim3;
+
 class Optimizer {
 public:
+    // int OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches1, g2o::Sim3& g2oS12, float th2)
+    // (src/Optimizer.cc:791-987); defined below Sim3.
+    static int OptimizeSim3(orbx_ctx* ctx, const Sim3KeyFrame& kf1, const Sim3KeyFrame& kf2, std::vector<int>& vMatches1,
+                            Sim3& S12, float th2);
+
     // Returns nInitialCorrespondences - nBad, updates F.Tcw and F.outlier.
     static int PoseOptimization(orbx_ctx* ctx, PoseFrame& F)
     {
@@ -647,6 +655,8 @@ struct Sim3KeyFrame {
     float Tcw[16];                   // row-major
     float cam[4];                    // fx, fy, cx, cy
     std::vector<float> sigma2;       // mvLevelSigma2
+    std::vector<float> invSigma2;    // mvInvLevelSigma2 (OptimizeSim3 reads KF1's); empty: 1.0f / sigma2, as
+                                     // ORBextractor fills it
 };
 
 class Sim3Solver {
@@ -752,6 +762,148 @@ private:
     int mRansacMinInliers = 6, mRansacMaxIts = 300;
     float mBestRotation[9] = {0}, mBestTranslation[3] = {0}, mBestScale = 0.f;
 };
+
+// ---------------------------------------------------------------------------
+// g2o::Sim3 (Thirdparty/g2o/g2o/types/sim3/sim3.h) as a value: the rotation as
+// a quaternion (x, y, z, w) that is never renormalised, t and s, and
+// Optimizer::OptimizeSim3 (src/Optimizer.cc:791-987), step 4 of
+// LoopClosing::ComputeSim3.
+// ---------------------------------------------------------------------------
+struct Sim3 {
+    double q[4] = {0, 0, 0, 1};   // x, y, z, w
+    double t[3] = {0, 0, 0};
+    double s = 1.0;
+    // the floats a Sim3 was built from, kept while it is unchanged: q -> R -> float need not return the bits of a
+    // float matrix that is orthonormal to float precision only, and OptimizeSim3 starts from exactly those bits
+    float fR[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, ft[3] = {0, 0, 0}, fs = 1.f;
+    bool from_float = false;
+
+    Sim3() {}
+    // g2o::Sim3(Converter::toMatrix3d(R), Converter::toVector3d(t), s): the float values widened, Eigen's
+    // Quaterniond(R), no normalisation
+    Sim3(const float R[9], const float t_[3], float s_)
+    {
+        double m[9];
+        for (int i = 0; i < 9; i++) m[i] = (double)R[i];
+        double tr = m[0] + m[4] + m[8];
+        if (tr > 0) {
+            tr = std::sqrt(tr + 1.0);
+            q[3] = 0.5 * tr;
+            tr = 0.5 / tr;
+            q[0] = (m[7] - m[5]) * tr;
+            q[1] = (m[2] - m[6]) * tr;
+            q[2] = (m[3] - m[1]) * tr;
+        } else {
+            int i = 0;
+            if (m[4] > m[0]) i = 1;
+            if (m[8] > m[i * 4]) i = 2;
+            const int j = (i + 1) % 3, k = (i + 2) % 3;
+            tr = std::sqrt(m[i * 4] - m[j * 4] - m[k * 4] + 1.0);
+            q[i] = 0.5 * tr;
+            tr = 0.5 / tr;
+            q[3] = (m[k * 3 + j] - m[j * 3 + k]) * tr;
+            q[j] = (m[j * 3 + i] + m[i * 3 + j]) * tr;
+            q[k] = (m[k * 3 + i] + m[i * 3 + k]) * tr;
+        }
+        for (int i = 0; i < 3; i++) t[i] = (double)t_[i];
+        s = (double)s_;
+        std::memcpy(fR, R, sizeof(fR));
+        std::memcpy(ft, t_, sizeof(ft));
+        fs = s_;
+        from_float = true;
+    }
+
+    // Eigen's Quaternion * Vector3
+    void rotate(const double v[3], double o[3]) const
+    {
+        double uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]};
+        for (int i = 0; i < 3; i++) uv[i] += uv[i];
+        const double c[3] = {q[1] * uv[2] - q[2] * uv[1], q[2] * uv[0] - q[0] * uv[2], q[0] * uv[1] - q[1] * uv[0]};
+        for (int i = 0; i < 3; i++) o[i] = v[i] + q[3] * uv[i] + c[i];
+    }
+
+    // Sim3::operator* (sim3.h:266-272), as in gScm * gSmw (src/LoopClosing.cc:341)
+    Sim3 operator*(const Sim3& o) const
+    {
+        Sim3 r;
+        r.q[3] = q[3] * o.q[3] - q[0] * o.q[0] - q[1] * o.q[1] - q[2] * o.q[2];
+        r.q[0] = q[3] * o.q[0] + q[0] * o.q[3] + q[1] * o.q[2] - q[2] * o.q[1];
+        r.q[1] = q[3] * o.q[1] + q[1] * o.q[3] + q[2] * o.q[0] - q[0] * o.q[2];
+        r.q[2] = q[3] * o.q[2] + q[2] * o.q[3] + q[0] * o.q[1] - q[1] * o.q[0];
+        double rt[3];
+        rotate(o.t, rt);
+        for (int i = 0; i < 3; i++) r.t[i] = s * rt[i] + t[i];
+        r.s = s * o.s;
+        return r;
+    }
+
+    // rotation().toRotationMatrix(), translation() and scale() as the floats Converter::toCvMat makes of them
+    void to_float(float R[9], float t_[3], float& s_) const
+    {
+        if (from_float) {
+            std::memcpy(R, fR, sizeof(fR));
+            std::memcpy(t_, ft, sizeof(ft));
+            s_ = fs;
+            return;
+        }
+        const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
+        const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
+        const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
+        const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
+        const double m[9] = {1 - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1 - (txx + tzz),
+                             tyz - twx,       txz - twy, tyz + twx, 1 - (txx + tyy)};
+        for (int i = 0; i < 9; i++) R[i] = (float)m[i];
+        for (int i = 0; i < 3; i++) t_[i] = (float)t[i];
+        s_ = (float)s;
+    }
+};
+
+// vMatches1: per keypoint of kf1 the KF2 keypoint index of vpMatches1[i] (GetIndexInKeyFrame(pKF2)), -1 for NULL,
+// any other negative for a point KF2 does not observe; entries the checks remove become -1.  S12 enters as the
+// float matrix, vector and scale ComputeSim3 builds it from (:324-327: the Sim3Solver's estimate) and is replaced
+// by the optimised g2oS12 unless the call returns 0 at the nCorrespondences - nBad < 10 exit.  Returns nIn.
+inline int Optimizer::OptimizeSim3(orbx_ctx* ctx, const Sim3KeyFrame& kf1, const Sim3KeyFrame& kf2,
+                                   std::vector<int>& vMatches1, Sim3& S12, float th2)
+{
+    const int n1 = (int)kf1.keys.size(), n2 = (int)kf2.keys.size();
+    if ((int)vMatches1.size() != n1 || kf1.pos.size() != (size_t)n1 * 3 || kf1.valid.size() != (size_t)n1 ||
+        kf2.pos.size() != (size_t)n2 * 3 || kf2.valid.size() != (size_t)n2 || kf1.sigma2.size() != kf2.sigma2.size() ||
+        (!kf1.invSigma2.empty() && kf1.invSigma2.size() != kf1.sigma2.size()))
+        throw orbx_error(ORBX_ERR_ARG, "Optimizer::OptimizeSim3");
+    std::vector<float> inv(kf1.invSigma2);
+    if (inv.empty())
+        for (float v : kf1.sigma2) inv.push_back(1.0f / v);   // mvInvLevelSigma2[i] = 1.0f / mvLevelSigma2[i]
+    std::vector<int32_t> m(vMatches1.begin(), vMatches1.end());
+    orbx_sim3_opt_query q;
+    std::memset(&q, 0, sizeof(q));
+    q.keys1 = kf1.keys.data();
+    q.n1 = n1;
+    q.keys2 = kf2.keys.data();
+    q.n2 = n2;
+    q.matches12 = m.data();
+    q.pos1 = kf1.pos.data();
+    q.valid1 = kf1.valid.data();
+    q.pos2 = kf2.pos.data();
+    q.valid2 = kf2.valid.data();
+    q.T1w = kf1.Tcw;
+    q.T2w = kf2.Tcw;
+    q.cam1 = kf1.cam;
+    q.cam2 = kf2.cam;
+    q.inv_sigma2_1 = inv.data();
+    q.sigma2_2 = kf2.sigma2.data();   // GetSigma2, as the reference (:912)
+    q.nlevels = (int)kf1.sigma2.size();
+    S12.to_float(q.R12, q.t12, q.s12);
+    q.th2 = th2;
+    check(orbx_optimize_sim3(ctx, &q), "Optimizer::OptimizeSim3");
+    vMatches1.assign(m.begin(), m.end());
+    if (!q.returned_early) {
+        for (int i = 0; i < 4; i++) S12.q[i] = q.q12[i];
+        for (int i = 0; i < 3; i++) S12.t[i] = q.t12d[i];
+        S12.s = q.s12d;
+        S12.from_float = false;
+    }
+    return q.n_in;
+}
 
 // ---------------------------------------------------------------------------
 // PnPsolver (include/PnPsolver.h, src/PnPsolver.cc): the RANSAC of

@@ -1,0 +1,1070 @@
+// Optimizer::OptimizeSim3 on MI355X (FP64): the Sim3 refinement of
+// LoopClosing::ComputeSim3 (src/Optimizer.cc:791-987) for batches of
+// loop-closure candidates.
+//
+// g2o subset (as the reference configures it): one free VertexSim3Expmap
+// against fixed points through an EdgeSim3ProjectXYZ (e12) and an
+// EdgeInverseSim3ProjectXYZ (e21) per correspondence, Huber, BlockSolverX +
+// LinearSolverDense (Eigen LDLT, diagonal pivoting, 7 x 7) and
+// OptimizationAlgorithmLevenberg with ORB-SLAM's stop rule.  Both edge
+// classes leave linearizeOplus to BaseBinaryEdge: central differences with
+// delta = 1e-9 on the Sim3 vertex (base_binary_edge.hpp:131-205).
+//
+// Mapping: one workgroup per candidate -- a wavefront in a batch, four
+// wavefronts for a lone call -- and both optimize() rounds with their checks
+// in ONE launch.  A thread handles both edges of a correspondence; the
+// correspondences (camera-frame points, observations, the two information
+// values, a flag) live in the candidate's block of global memory, written by
+// the kernel's own set-up pass and re-read by every pass, so no edge count is
+// bounded by LDS.  Per LM iteration the 15 estimates of the linearisation
+// (the current one and Sim3(+-delta e_d) * S for the 7 dimensions) and their
+// inverses are computed once, a lane each, into LDS; every thread then
+// evaluates the 15 projections of each of its two edges, forms the numeric
+// Jacobians and writes the pair's 72 terms (per edge the robust chi2, the 28
+// lower entries of B^T W B and the 7 of B^T omega_r) to an LDS row; lane q of
+// the first wavefront adds column q over the rows in g2o's edge order
+// e12_0, e21_0, e12_1, ... -- every sum is the sequential sum of the
+// restatement (tests/sim3opt_numpy.py).  A trial is one error pass summed the
+// same way.  The sums reach every thread through LDS, so the LDLT, the
+// exp-map update and the accept / reject logic run redundantly on uniform
+// data.  A removed pair writes +0.0 terms: the sums start at +0.0 and
+// round-to-nearest never makes -0.0 of them, so that leaves every bit as
+// skipping the pair would.
+//
+// Stored-error semantics: the checks read each edge's _error as left by the
+// LAST computeActiveErrors -- the final trial's state even when that trial was
+// rejected.  The kernel keeps that estimate ("errest", orbx_pose.hip's
+// errpose) and evaluates the tested chi2 there.
+//
+// The Jacobian path needs Sim3(update) at +-1e-9 e_d only: the |sigma| < eps,
+// theta < eps branch, + - * /, sqrt and exp at 0 and +-1e-9.  The two
+// exponentials are constants (the correctly rounded values), so the whole
+// linearisation is reproducible bit for bit; the device's exp / sin / cos
+// enter in the LM update alone.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <type_traits>
+#include <vector>
+
+#include "orbx_device.h"
+#include "orbx_internal.h"
+#include "orbx_match_common.h"
+#include "orbx_se3.h"
+
+namespace orbx {
+
+constexpr int kSoLm = ORBX_SIM3_OPT_MAX_LM;
+constexpr int kSoTrials = ORBX_SIM3_OPT_MAX_TRIALS;
+constexpr int kSoWide = 4;          // wavefronts of a lone call's workgroup
+constexpr int kSoTerms = 36;        // per edge: chi2, 28 of H, 7 of b
+constexpr int kSoStride = 73;       // doubles per LDS row (72 terms + 1: odd, so rows spread over the banks)
+constexpr double kSoDelta = 1e-9;   // base_binary_edge.hpp:133
+constexpr double kSoExpP = 0x1.000000044b830p+0;   // exp(+1e-9), correctly rounded
+constexpr double kSoExpM = 0x1.fffffff768fa1p-1;   // exp(-1e-9)
+static_assert(64 * kSoWide * kSoStride * sizeof(double) <= 150 * 1024, "the term rows of a lone call fit gfx950's LDS");
+
+// One candidate: device pointers to its inputs.
+struct Sim3OptProb {
+    const orbx_keypoint* k1;
+    const orbx_keypoint* k2;
+    const int32_t* ci;       // n: KF1 keypoint of each correspondence (vnIndexEdge)
+    const int32_t* cj;       // n: KF2 keypoint
+    const float* pos1;
+    const float* pos2;
+    const float* isig1;      // KF1's mvInvLevelSigma2
+    const float* sig2;       // KF2's mvLevelSigma2
+    int32_t n, nlevels, taps, pad;
+    float T1w[12], T2w[12];  // rows 0..2 of Tcw
+    float cam1[4], cam2[4];
+    float R12[9], t12[3], s12, th2;
+    double delta;            // (double) sqrtf(th2)
+};
+
+struct Sim3OptIter {
+    double est[8], chi2, H[28], b[7], lambda, dx[kSoTrials][7];
+    int32_t trials, pad;
+};
+
+struct Sim3OptHdr {
+    double est[8], check_est[2][8];
+    float R12[9], t12[3], s12, padf[3];
+    int32_t n_in, n_bad, early, n_lm;
+    int32_t iters[2], trials[2], npd[2], pad[2];
+};
+
+// Byte offsets inside one candidate's block.
+struct Sim3OptLayout {
+    long long stride;
+    int o_x1, o_x2, o_obs, o_w, o_flag, o_it, o_err, o_J, o_chi;
+    int cap;
+};
+
+inline Sim3OptLayout sim3opt_layout(int cap, bool taps)
+{
+    Sim3OptLayout L;
+    long long o = 0;
+    auto take = [&](long long bytes) {
+        const long long r = o;
+        o += (bytes + 15) & ~15ll;
+        return (int)r;
+    };
+    take(sizeof(Sim3OptHdr));
+    L.o_x1 = take((long long)cap * 12);
+    L.o_x2 = take((long long)cap * 12);
+    L.o_obs = take((long long)cap * 16);
+    L.o_w = take((long long)cap * 8);
+    L.o_flag = take(cap);
+    L.o_it = take(taps ? (long long)kSoLm * sizeof(Sim3OptIter) : 0);
+    L.o_err = take(taps ? (long long)cap * 32 : 0);
+    L.o_J = take(taps ? (long long)cap * 224 : 0);
+    L.o_chi = take(taps ? (long long)cap * 32 : 0);
+    L.stride = o;
+    L.cap = cap;
+    return L;
+}
+
+// g2o::Sim3 as (x, y, z, w, tx, ty, tz, s).
+// Sim3(const Vector7d& update) (sim3.h:70-142); es = exp(update[6]).
+__device__ inline void sim3_exp(const double u[7], double es, double out[8])
+{
+    const double om[3] = {u[0], u[1], u[2]}, up[3] = {u[3], u[4], u[5]};
+    const double sigma = u[6];
+    const double theta = sqrt(om[0] * om[0] + om[1] * om[1] + om[2] * om[2]);
+    const double O[9] = {0, -om[2], om[1], om[2], 0, -om[0], -om[1], om[0], 0};
+    double O2[9], R[9], W[9];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) O2[i * 3 + j] = O[i * 3] * O[j] + O[i * 3 + 1] * O[3 + j] + O[i * 3 + 2] * O[6 + j];
+    const double s = es;
+    const double eps = 0.00001;
+    double A, B, C;
+    bool rodrigues;
+    if (fabs(sigma) < eps) {
+        C = 1;
+        if (theta < eps) {
+            A = 1. / 2.;
+            B = 1. / 6.;
+            rodrigues = false;
+        } else {
+            const double theta2 = theta * theta;
+            A = (1 - cos(theta)) / (theta2);
+            B = (theta - sin(theta)) / (theta2 * theta);
+            rodrigues = true;
+        }
+    } else {
+        C = (s - 1) / sigma;
+        if (theta < eps) {
+            const double sigma2 = sigma * sigma;
+            A = ((sigma - 1) * s + 1) / sigma2;
+            B = ((0.5 * sigma2 - sigma + 1) * s) / (sigma2 * sigma);
+            rodrigues = false;
+        } else {
+            const double a = s * sin(theta);
+            const double b = s * cos(theta);
+            const double theta2 = theta * theta;
+            const double sigma2 = sigma * sigma;
+            const double c = theta2 + sigma2;
+            A = (a * sigma + (1 - b) * theta) / (theta * c);
+            B = (C - ((b - 1) * sigma + a * theta) / (c)) * 1. / (theta2);
+            rodrigues = true;
+        }
+    }
+    if (rodrigues) {
+        const double ra = sin(theta) / theta, rb = (1 - cos(theta)) / (theta * theta);
+#pragma unroll
+        for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0 ? 1.0 : 0.0) + ra * O[i] + rb * O2[i];
+    } else {
+#pragma unroll
+        for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0 ? 1.0 : 0.0) + O[i] + O2[i];
+    }
+    const Q q = qfrom(R);
+#pragma unroll
+    for (int i = 0; i < 9; i++) W[i] = A * O[i] + B * O2[i] + C * (i % 4 == 0 ? 1.0 : 0.0);
+    out[0] = q.x; out[1] = q.y; out[2] = q.z; out[3] = q.w;
+#pragma unroll
+    for (int i = 0; i < 3; i++) out[4 + i] = W[i * 3] * up[0] + W[i * 3 + 1] * up[1] + W[i * 3 + 2] * up[2];
+    out[7] = s;
+}
+
+// Sim3::operator* (sim3.h:266-272): the quaternion is never renormalised
+__device__ inline void sim3_mul(const double a[8], const double b[8], double o[8])
+{
+    const Q qa{a[0], a[1], a[2], a[3]};
+    const Q r = qmul(qa, Q{b[0], b[1], b[2], b[3]});
+    const double bt[3] = {b[4], b[5], b[6]};
+    double rt[3];
+    qrot(qa, bt, rt);
+    o[0] = r.x; o[1] = r.y; o[2] = r.z; o[3] = r.w;
+#pragma unroll
+    for (int i = 0; i < 3; i++) o[4 + i] = a[7] * rt[i] + a[4 + i];
+    o[7] = a[7] * b[7];
+}
+
+// Sim3::inverse (sim3.h:233-236)
+__device__ inline void sim3_inverse(const double a[8], double o[8])
+{
+    const Q rc{-a[0], -a[1], -a[2], a[3]};
+    const double f = -1. / a[7];
+    const double st[3] = {f * a[4], f * a[5], f * a[6]};
+    double rt[3];
+    qrot(rc, st, rt);
+    o[0] = rc.x; o[1] = rc.y; o[2] = rc.z; o[3] = rc.w;
+    o[4] = rt[0]; o[5] = rt[1]; o[6] = rt[2];
+    o[7] = 1. / a[7];
+}
+
+struct SoCam {
+    double fx, fy, cx, cy;
+};
+
+// obs - cam_map(project(S.map(X))) (types_seven_dof_expmap.h:138-167)
+__device__ inline void sim3_edge_error(const double* S, const double X[3], double o0, double o1, const SoCam& c,
+                                       double& e0, double& e1)
+{
+    const Q q{S[0], S[1], S[2], S[3]};
+    double r[3];
+    qrot(q, X, r);
+    const double s = S[7];
+    const double x = s * r[0] + S[4], y = s * r[1] + S[5], z = s * r[2] + S[6];
+    e0 = o0 - (x / z * c.fx + c.cx);
+    e1 = o1 - (y / z * c.fy + c.cy);
+}
+
+// RobustKernelHuber::robustify (robust_kernel_impl.cpp:78-91)
+__device__ inline void so_huber(double e2, double delta, double& rho0, double& rho1)
+{
+    const double dsqr = delta * delta;
+    if (e2 <= dsqr) {
+        rho0 = e2;
+        rho1 = 1.;
+    } else {
+        const double sq = sqrt(e2);
+        rho0 = 2 * sq * delta - dsqr;
+        rho1 = delta / sq;
+    }
+}
+
+// Packed lower triangle: entry (i, j), j <= i, at i (i + 1) / 2 + j.
+#define SO_LT(i, j) ((i) * ((i) + 1) / 2 + (j))
+
+// Eigen::LDLT<MatrixXd> of the lower triangle of m (packed, N x N) and the
+// solve of m x = b: the algorithm of orbx_pose.hip's ldlt6_solve for any N,
+// every index a compile-time constant (the runtime pivot selects among
+// unrolled swap variants), so the matrix stays in registers.
+template <int N>
+__device__ inline bool ldlt_solve(double (&m)[N * (N + 1) / 2], const double (&b)[N], double (&x)[N])
+{
+    int tr[N];
+    double temp[N];
+    int sign = 0;   // 0 zero, 1 positive semidefinite, 2 negative semidefinite, 3 indefinite
+    auto swap_d = [](double& a, double& c) {
+        const double t = a;
+        a = c;
+        c = t;
+    };
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        int big = k;
+        double bv = fabs(m[SO_LT(k, k)]);
+#pragma unroll
+        for (int i = k + 1; i < N; i++)
+            if (fabs(m[SO_LT(i, i)]) > bv) {
+                bv = fabs(m[SO_LT(i, i)]);
+                big = i;
+            }
+        tr[k] = big;
+#pragma unroll
+        for (int q = k + 1; q < N; q++) {
+            if (big == q) {
+#pragma unroll
+                for (int j = 0; j < k; j++) swap_d(m[SO_LT(k, j)], m[SO_LT(q, j)]);
+#pragma unroll
+                for (int i = q + 1; i < N; i++) swap_d(m[SO_LT(i, k)], m[SO_LT(i, q)]);
+                swap_d(m[SO_LT(k, k)], m[SO_LT(q, q)]);
+#pragma unroll
+                for (int i = k + 1; i < q; i++) swap_d(m[SO_LT(i, k)], m[SO_LT(q, i)]);
+            }
+        }
+        if (k > 0) {
+#pragma unroll
+            for (int j = 0; j < k; j++) temp[j] = m[SO_LT(j, j)] * m[SO_LT(k, j)];
+            double acc = m[SO_LT(k, 0)] * temp[0];
+#pragma unroll
+            for (int j = 1; j < k; j++) acc += m[SO_LT(k, j)] * temp[j];
+            m[SO_LT(k, k)] -= acc;
+#pragma unroll
+            for (int i = k + 1; i < N; i++)
+#pragma unroll
+                for (int j = 0; j < k; j++) m[SO_LT(i, k)] -= m[SO_LT(i, j)] * temp[j];
+        }
+        const double akk = m[SO_LT(k, k)];
+        if (k < N - 1 && fabs(akk) > 0.0) {
+#pragma unroll
+            for (int i = k + 1; i < N; i++) m[SO_LT(i, k)] /= akk;
+        }
+        if (sign == 1) {
+            if (akk < 0) sign = 3;
+        } else if (sign == 2) {
+            if (akk > 0) sign = 3;
+        } else if (sign == 0) {
+            if (akk > 0) sign = 1;
+            else if (akk < 0) sign = 2;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < N; i++) x[i] = b[i];
+#pragma unroll
+    for (int k = 0; k < N; k++)
+#pragma unroll
+        for (int q = k + 1; q < N; q++)
+            if (tr[k] == q) swap_d(x[k], x[q]);
+#pragma unroll
+    for (int i = 0; i < N; i++)
+#pragma unroll
+        for (int j = 0; j < i; j++) x[i] -= m[SO_LT(i, j)] * x[j];
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+        if (fabs(m[SO_LT(i, i)]) > 2.2250738585072014e-308) x[i] /= m[SO_LT(i, i)];
+        else x[i] = 0.0;
+    }
+#pragma unroll
+    for (int i = N - 2; i >= 0; i--) {
+        double s = m[SO_LT(i + 1, i)] * x[i + 1];
+#pragma unroll
+        for (int j = i + 2; j < N; j++) s += m[SO_LT(j, i)] * x[j];
+        x[i] -= s;
+    }
+#pragma unroll
+    for (int k = N - 1; k >= 0; k--)
+#pragma unroll
+        for (int q = k + 1; q < N; q++)
+            if (tr[k] == q) swap_d(x[k], x[q]);
+    return sign == 1 || sign == 0;
+}
+
+// One edge's 36 terms at the 15 estimates S[0..14] (LDS): computeError, the
+// central differences of BaseBinaryEdge::linearizeOplus, robustify and
+// constructQuadraticForm's products for the Sim3 vertex
+// (base_binary_edge.hpp:91-113), written to row[0, 36).
+__device__ inline void so_edge_terms(const double (*S)[8], const double X[3], double o0, double o1, const SoCam& cam,
+                                     double info, double delta, double* row, bool tap, double* tap_err, double* tap_J)
+{
+    constexpr double scalar = 1.0 / (2 * kSoDelta);
+    double er0, er1, J0[7], J1[7];
+    sim3_edge_error(S[0], X, o0, o1, cam, er0, er1);
+#pragma unroll
+    for (int d = 0; d < 7; d++) {
+        double p0, p1, m0, m1;
+        sim3_edge_error(S[1 + 2 * d], X, o0, o1, cam, p0, p1);
+        sim3_edge_error(S[2 + 2 * d], X, o0, o1, cam, m0, m1);
+        J0[d] = scalar * (p0 - m0);
+        J1[d] = scalar * (p1 - m1);
+    }
+    if (tap) {
+        tap_err[0] = er0;
+        tap_err[1] = er1;
+#pragma unroll
+        for (int d = 0; d < 7; d++) {
+            tap_J[d] = J0[d];
+            tap_J[7 + d] = J1[d];
+        }
+    }
+    double rho0, rho1;
+    so_huber(er0 * (info * er0) + er1 * (info * er1), delta, rho0, rho1);
+    row[0] = rho0;
+    const double w = rho1 * info;
+    const double om0 = -(info * er0) * rho1, om1 = -(info * er1) * rho1;
+    int k = 1;
+#pragma unroll
+    for (int i = 0; i < 7; i++)
+#pragma unroll
+        for (int j = 0; j <= i; j++, k++) row[k] = (J0[i] * w) * J0[j] + (J1[i] * w) * J1[j];
+#pragma unroll
+    for (int i = 0; i < 7; i++) row[29 + i] = J0[i] * om0 + J1[i] * om1;
+}
+
+template <int kW>
+__global__ __launch_bounds__(64 * kW) void k_sim3_opt(const Sim3OptProb* __restrict__ probs, uint8_t* __restrict__ res,
+                                                      Sim3OptLayout L)
+{
+    constexpr int kT = 64 * kW;
+    __shared__ double s_rows[kT * kSoStride];
+    __shared__ double s_est[15][8], s_inv[15][8];
+    __shared__ double s_sum[kSoTerms];
+    __shared__ int s_cnt[2];
+    const Sim3OptProb& P = probs[blockIdx.x];
+    uint8_t* blk = res + (long long)blockIdx.x * L.stride;
+    Sim3OptHdr* hdr = reinterpret_cast<Sim3OptHdr*>(blk);
+    const int tid = threadIdx.x;
+    const int n = max(0, min(P.n, L.cap));
+    const bool taps = P.taps != 0;
+    float* gx1 = reinterpret_cast<float*>(blk + L.o_x1);
+    float* gx2 = reinterpret_cast<float*>(blk + L.o_x2);
+    float* gobs = reinterpret_cast<float*>(blk + L.o_obs);
+    float* gw = reinterpret_cast<float*>(blk + L.o_w);
+    uint8_t* gflag = blk + L.o_flag;
+    Sim3OptIter* tap_it = reinterpret_cast<Sim3OptIter*>(blk + L.o_it);
+    double* tap_err = reinterpret_cast<double*>(blk + L.o_err);
+    double* tap_J = reinterpret_cast<double*>(blk + L.o_J);
+    double* tap_chi = reinterpret_cast<double*>(blk + L.o_chi);
+    const SoCam cam1{(double)P.cam1[0], (double)P.cam1[1], (double)P.cam1[2], (double)P.cam1[3]};
+    const SoCam cam2{(double)P.cam2[0], (double)P.cam2[1], (double)P.cam2[2], (double)P.cam2[3]};
+    const double delta = P.delta;
+    const double th2 = (double)P.th2;
+
+    // the correspondences (:844-923): P3D1c = R1w * P3D1w + t1w in the float
+    // gemm of the Sim3 solver (FP64 accumulation over k in order, the addend,
+    // rounded once), the observations and the two information values
+#pragma unroll 1
+    for (int c = tid; c < n; c += kT) {
+        const int i1 = P.ci[c], i2 = P.cj[c];
+        const orbx_keypoint ka = P.k1[i1], kb = P.k2[i2];
+        const float* a = P.pos1 + 3 * (long long)i1;
+        const float* b = P.pos2 + 3 * (long long)i2;
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            double acc = (double)P.T1w[4 * r] * (double)a[0];
+            acc = acc + (double)P.T1w[4 * r + 1] * (double)a[1];
+            acc = acc + (double)P.T1w[4 * r + 2] * (double)a[2];
+            gx1[3 * c + r] = (float)(acc + (double)P.T1w[4 * r + 3]);
+            acc = (double)P.T2w[4 * r] * (double)b[0];
+            acc = acc + (double)P.T2w[4 * r + 1] * (double)b[1];
+            acc = acc + (double)P.T2w[4 * r + 2] * (double)b[2];
+            gx2[3 * c + r] = (float)(acc + (double)P.T2w[4 * r + 3]);
+        }
+        gobs[4 * c] = ka.x;
+        gobs[4 * c + 1] = ka.y;
+        gobs[4 * c + 2] = kb.x;
+        gobs[4 * c + 3] = kb.y;
+        gw[2 * c] = P.isig1[min(max(ka.octave, 0), P.nlevels - 1)];
+        gw[2 * c + 1] = P.sig2[min(max(kb.octave, 0), P.nlevels - 1)];   // GetSigma2, not its inverse (:912)
+        gflag[c] = 0;
+    }
+    __syncthreads();
+
+    // vertex 0: Sim3(toMatrix3d(R), toVector3d(t), s) -- widened floats, Eigen's
+    // quaternion of the matrix, no normalisation
+    double est[8], errest[8];
+    {
+        double R[9];
+#pragma unroll
+        for (int i = 0; i < 9; i++) R[i] = (double)P.R12[i];
+        const Q q = qfrom(R);
+        est[0] = q.x; est[1] = q.y; est[2] = q.z; est[3] = q.w;
+#pragma unroll
+        for (int i = 0; i < 3; i++) est[4 + i] = (double)P.t12[i];
+        est[7] = (double)P.s12;
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++) errest[i] = est[i];
+
+    // a pair's inputs
+    auto load_pair = [&](int c, double X1[3], double X2[3], double o[4], double w[2]) {
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            X1[r] = (double)gx1[3 * c + r];
+            X2[r] = (double)gx2[3 * c + r];
+        }
+#pragma unroll
+        for (int r = 0; r < 4; r++) o[r] = (double)gobs[4 * c + r];
+        w[0] = (double)gw[2 * c];
+        w[1] = (double)gw[2 * c + 1];
+    };
+    // Q sequential sums over the rows of the groups of kT pairs: fill(c, row)
+    // writes pair c's 2 x Q terms to row[0, Q) and row[36, 36 + Q); lane q < Q
+    // of wave 0 adds both per row in pair order.  The results land in
+    // s_sum[0, Q) for every thread.
+    auto seq_sums = [&](auto Qc, auto&& fill) {
+        constexpr int Qn = decltype(Qc)::value;
+        double acc = 0.0;
+#pragma unroll 1
+        for (int g = 0; g < n; g += kT) {
+            const int cnt = min(kT, n - g);
+            const int rows8 = (cnt + 7) & ~7;   // the chain runs in blocks of 8 rows
+            if (tid < rows8) {
+                double* row = s_rows + tid * kSoStride;
+                const int c = g + tid;
+                if (c < n && gflag[c] == 0) {
+                    fill(c, row);
+                } else {
+                    asm volatile("" ::: "memory");   // keeps the zero stores a branch of their own
+#pragma unroll
+                    for (int q = 0; q < Qn; q++) {
+                        row[q] = 0.0;
+                        row[kSoTerms + q] = 0.0;
+                    }
+                }
+            }
+            __syncthreads();
+            if (tid < Qn) {
+#pragma unroll 1
+                for (int k0 = 0; k0 < rows8; k0 += 8) {
+                    double v[16];
+#pragma unroll
+                    for (int j = 0; j < 8; j++) {
+                        v[2 * j] = s_rows[(k0 + j) * kSoStride + tid];
+                        v[2 * j + 1] = s_rows[(k0 + j) * kSoStride + kSoTerms + tid];
+                    }
+#pragma unroll
+                    for (int j = 0; j < 16; j++) acc += v[j];
+                }
+            }
+            __syncthreads();
+        }
+        if (tid < Qn) s_sum[tid] = acc;
+        __syncthreads();
+    };
+
+    int n_bad = 0, n_in = 0, early = 0, n_lm = 0;
+    if (tid == 0) {
+#pragma unroll
+        for (int r = 0; r < 2; r++) hdr->iters[r] = hdr->trials[r] = hdr->npd[r] = 0;
+    }
+#pragma unroll 1
+    for (int round = 0; round < 2 && n > 0; round++) {
+        const int its = round == 0 ? 5 : (n_bad > 0 ? 10 : 5);   // nMoreIterations (:951-955)
+        double lambda = 0, ni = 2;
+        int nBadLM = 0, iters = 0, trials = 0, npd = 0;
+#pragma unroll 1
+        for (int iter = 0; iter < its; iter++) {
+            // the 15 estimates of the linearisation and their inverses, a lane each
+            if (tid < 15) {
+                double pe[8], pi[8];
+                if (tid == 0) {
+#pragma unroll
+                    for (int i = 0; i < 8; i++) pe[i] = est[i];
+                } else {
+                    const int d = (tid - 1) >> 1;
+                    const bool minus = ((tid - 1) & 1) != 0;
+                    const double v = minus ? -kSoDelta : kSoDelta;
+                    double u[7], ex[8];
+#pragma unroll
+                    for (int k = 0; k < 7; k++) u[k] = k == d ? v : 0.0;
+                    sim3_exp(u, d == 6 ? (minus ? kSoExpM : kSoExpP) : 1.0, ex);
+                    sim3_mul(ex, est, pe);
+                }
+                sim3_inverse(pe, pi);
+#pragma unroll
+                for (int i = 0; i < 8; i++) {
+                    s_est[tid][i] = pe[i];
+                    s_inv[tid][i] = pi[i];
+                }
+            }
+            __syncthreads();
+            // computeActiveErrors + activeRobustChi2 + buildSystem
+            const bool tap_edges = taps && round == 0 && iter == 0;
+            seq_sums(std::integral_constant<int, kSoTerms>{}, [&](int c, double* row) {
+                double X1[3], X2[3], o[4], w[2];
+                load_pair(c, X1, X2, o, w);
+                so_edge_terms(s_est, X2, o[0], o[1], cam1, w[0], delta, row, tap_edges, tap_err + 4 * c, tap_J + 28 * c);
+                so_edge_terms(s_inv, X1, o[2], o[3], cam2, w[1], delta, row + kSoTerms, tap_edges, tap_err + 4 * c + 2,
+                              tap_J + 28 * c + 14);
+            });
+            double h[28], bv[7];
+            double currentChi = s_sum[0];
+#pragma unroll
+            for (int k = 0; k < 28; k++) h[k] = s_sum[1 + k];
+#pragma unroll
+            for (int k = 0; k < 7; k++) bv[k] = s_sum[29 + k];
+            __syncthreads();   // s_sum is written again by the trial pass
+            const double iniChi = currentChi;
+            if (iter == 0) {   // computeLambdaInit (levenberg.cpp:166-180)
+                double mx = 0;
+#pragma unroll
+                for (int j = 0; j < 7; j++) mx = fmax(fabs(h[SO_LT(j, j)]), mx);
+                lambda = 1e-5 * mx;
+                ni = 2;
+                nBadLM = 0;
+            }
+            Sim3OptIter* rec = tap_it + min(n_lm, kSoLm - 1);
+            if (taps && tid == 0) {
+#pragma unroll
+                for (int i = 0; i < 8; i++) rec->est[i] = est[i];
+                rec->chi2 = currentChi;
+#pragma unroll
+                for (int k = 0; k < 28; k++) rec->H[k] = h[k];
+#pragma unroll
+                for (int k = 0; k < 7; k++) rec->b[k] = bv[k];
+            }
+            double rho = 0;
+            int qmax = 0;
+            do {
+                double m[28], xs[7], te[8];
+#pragma unroll
+                for (int k = 0; k < 28; k++) m[k] = h[k];
+#pragma unroll
+                for (int j = 0; j < 7; j++) m[SO_LT(j, j)] += lambda;
+                const bool ok2 = ldlt_solve<7>(m, bv, xs);
+                if (ok2) {   // VertexSim3Expmap::oplusImpl: Sim3(update) * estimate
+                    double ex[8];
+                    sim3_exp(xs, exp(xs[6]), ex);
+                    sim3_mul(ex, est, te);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 7; i++) xs[i] = 0.0;
+#pragma unroll
+                    for (int i = 0; i < 8; i++) te[i] = est[i];
+                    npd++;
+                }
+                if (taps && tid == 0 && qmax < kSoTrials) {
+#pragma unroll
+                    for (int i = 0; i < 7; i++) rec->dx[qmax][i] = xs[i];
+                }
+                // computeActiveErrors at the trial estimate
+                if (tid == 0) {
+                    double ti[8];
+                    sim3_inverse(te, ti);
+#pragma unroll
+                    for (int i = 0; i < 8; i++) {
+                        s_est[0][i] = te[i];
+                        s_inv[0][i] = ti[i];
+                    }
+                }
+                __syncthreads();
+                seq_sums(std::integral_constant<int, 1>{}, [&](int c, double* row) {
+                    double X1[3], X2[3], o[4], w[2], e0, e1, rho1;
+                    load_pair(c, X1, X2, o, w);
+                    sim3_edge_error(s_est[0], X2, o[0], o[1], cam1, e0, e1);
+                    so_huber(e0 * (w[0] * e0) + e1 * (w[0] * e1), delta, row[0], rho1);
+                    sim3_edge_error(s_inv[0], X1, o[2], o[3], cam2, e0, e1);
+                    so_huber(e0 * (w[1] * e0) + e1 * (w[1] * e1), delta, row[kSoTerms], rho1);
+                });
+                double tempChi = s_sum[0];
+                __syncthreads();
+#pragma unroll
+                for (int i = 0; i < 8; i++) errest[i] = te[i];
+                if (!ok2) tempChi = 1.79769313486231570815e+308;
+                double scale = 0;
+#pragma unroll
+                for (int j = 0; j < 7; j++) scale += xs[j] * (lambda * xs[j] + bv[j]);
+                scale += 1e-3;
+                rho = (currentChi - tempChi) / scale;
+                if (rho > 0 && isfinite(tempChi)) {
+                    double alpha = 1. - pow((2 * rho - 1), 3);
+                    alpha = fmin(alpha, 2. / 3.);
+                    lambda *= fmax(1. / 3., alpha);
+                    ni = 2;
+                    currentChi = tempChi;
+#pragma unroll
+                    for (int i = 0; i < 8; i++) est[i] = te[i];
+                } else {
+                    lambda *= ni;
+                    ni *= 2;
+                }
+                qmax++;
+            } while (rho < 0 && qmax < 10);
+            if (taps && tid == 0) {
+                rec->lambda = lambda;
+                rec->trials = qmax;
+            }
+            iters++;
+            n_lm++;
+            trials += qmax;
+            if (qmax == 10 || rho == 0) break;
+            if ((iniChi - currentChi) * 1e3 < iniChi) nBadLM++;
+            else nBadLM = 0;
+            if (nBadLM >= 3) break;
+        }
+        if (tid == 0) {
+            hdr->iters[round] = iters;
+            hdr->trials[round] = trials;
+            hdr->npd[round] = npd;
+        }
+        // the check (:930-949, :965-980): chi2() of the stored errors, those of
+        // the last trial's estimate; a NaN keeps the pair
+        if (tid == 0) {
+            double ti[8];
+            sim3_inverse(errest, ti);
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                s_est[0][i] = errest[i];
+                s_inv[0][i] = ti[i];
+                hdr->check_est[round][i] = errest[i];
+            }
+            s_cnt[0] = 0;
+            s_cnt[1] = 0;
+        }
+        __syncthreads();
+        int bad = 0, good = 0;
+#pragma unroll 1
+        for (int c = tid; c < n; c += kT) {
+            if (gflag[c] != 0) continue;
+            double X1[3], X2[3], o[4], w[2], e0, e1;
+            load_pair(c, X1, X2, o, w);
+            sim3_edge_error(s_est[0], X2, o[0], o[1], cam1, e0, e1);
+            const double c12 = e0 * (w[0] * e0) + e1 * (w[0] * e1);
+            sim3_edge_error(s_inv[0], X1, o[2], o[3], cam2, e0, e1);
+            const double c21 = e0 * (w[1] * e0) + e1 * (w[1] * e1);
+            if (taps) {
+                tap_chi[((long long)round * L.cap + c) * 2] = c12;
+                tap_chi[((long long)round * L.cap + c) * 2 + 1] = c21;
+            }
+            if (c12 > th2 || c21 > th2) {
+                gflag[c] = (uint8_t)(round + 1);
+                bad++;
+            } else {
+                good++;
+            }
+        }
+        if (bad) atomicAdd(&s_cnt[0], bad);
+        if (good) atomicAdd(&s_cnt[1], good);
+        __syncthreads();
+        const int nb = s_cnt[0], ng = s_cnt[1];
+        __syncthreads();
+        if (round == 0) {
+            n_bad = nb;
+            if (n - n_bad < 10) {   // return 0 at once: g2oS12 is not updated (:957-958)
+                early = 1;
+                break;
+            }
+        } else {
+            n_in = ng;
+        }
+    }
+    if (n == 0) early = 1;
+    if (tid == 0) {
+        double R[9];
+        qmat(Q{est[0], est[1], est[2], est[3]}, R);   // Eigen's toRotationMatrix
+#pragma unroll
+        for (int i = 0; i < 8; i++) hdr->est[i] = est[i];
+#pragma unroll
+        for (int i = 0; i < 9; i++) hdr->R12[i] = (float)R[i];
+#pragma unroll
+        for (int i = 0; i < 3; i++) hdr->t12[i] = (float)est[4 + i];
+        hdr->s12 = (float)est[7];
+        hdr->n_in = early ? 0 : n_in;
+        hdr->n_bad = n_bad;
+        hdr->early = early;
+        hdr->n_lm = n_lm;
+    }
+}
+
+}  // namespace orbx
+
+// ---------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------
+using namespace orbx;
+
+namespace {
+
+inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+bool finite_all(const float* v, int n)
+{
+    for (int i = 0; i < n; i++)
+        if (!std::isfinite(v[i])) return false;
+    return true;
+}
+
+// What every form checks of a query's own fields.
+int check_common(const orbx_sim3_opt_query& q)
+{
+    if (!q.matches12 && q.n1 > 0) return ORBX_ERR_ARG;
+    if (!(q.th2 > 0.f) || !std::isfinite(q.th2)) return ORBX_ERR_ARG;
+    if (!finite_all(q.R12, 9) || !finite_all(q.t12, 3) || !std::isfinite(q.s12)) return ORBX_ERR_ARG;
+    return ORBX_OK;
+}
+
+// The correspondences of :844-923 in i order: matches12[i] >= 0, both map
+// points good.  ORBX_ERR_ARG for a match index >= n2.
+int correspondences(const int32_t* m, int n1, int n2, const uint8_t* v1, int good1, const uint8_t* v2, int good2,
+                    std::vector<int32_t>* ci, std::vector<int32_t>* cj)
+{
+    for (int i = 0; i < n1; i++) {
+        const int i2 = m[i];
+        if (i2 >= n2) return ORBX_ERR_ARG;   // the reference would read past KF2's keypoints
+        if (i2 < 0) continue;
+        const bool ok1 = good1 ? v1[i] == good1 : v1[i] != 0;
+        const bool ok2 = good2 ? v2[i2] == good2 : v2[i2] != 0;
+        if (ok1 && ok2) {
+            ci->push_back(i);
+            cj->push_back(i2);
+        }
+    }
+    return ORBX_OK;
+}
+
+bool any_corr_tap(const orbx_sim3_opt_query& q)
+{
+    return q.corr_index || q.x3dc1 || q.x3dc2 || q.edge_err || q.edge_J || q.edge_chi2;
+}
+
+bool any_tap(const orbx_sim3_opt_query& q)
+{
+    return any_corr_tap(q) || q.it_est || q.it_chi2 || q.it_H || q.it_b || q.it_lambda || q.it_trials || q.it_dx ||
+           q.check_est;
+}
+
+// One candidate's block (host copy) into the query's outputs and taps.
+void scatter(const uint8_t* blk, const Sim3OptLayout& L, const std::vector<int32_t>& ci, bool taps,
+             orbx_sim3_opt_query* q)
+{
+    const Sim3OptHdr* h = reinterpret_cast<const Sim3OptHdr*>(blk);
+    const int n = (int)ci.size();
+    q->n_corr = n;
+    q->n_bad = h->n_bad;
+    q->n_in = h->n_in;
+    q->returned_early = h->early;
+    q->n_lm = h->n_lm;
+    for (int r = 0; r < 2; r++) {
+        q->iterations[r] = h->iters[r];
+        q->trials[r] = h->trials[r];
+        q->not_posdef[r] = h->npd[r];
+    }
+    const uint8_t* flag = blk + L.o_flag;
+    for (int c = 0; c < n; c++)
+        if (flag[c]) q->matches12[ci[c]] = -1;
+    if (!h->early) {
+        std::memcpy(q->q12, h->est, 4 * sizeof(double));
+        std::memcpy(q->t12d, h->est + 4, 3 * sizeof(double));
+        q->s12d = h->est[7];
+        std::memcpy(q->R12, h->R12, sizeof(q->R12));
+        std::memcpy(q->t12, h->t12, sizeof(q->t12));
+        q->s12 = h->s12;
+    }
+    if (q->corr_index && n) std::memcpy(q->corr_index, ci.data(), (size_t)n * 4);
+    if (q->x3dc1 && n) std::memcpy(q->x3dc1, blk + L.o_x1, (size_t)n * 12);
+    if (q->x3dc2 && n) std::memcpy(q->x3dc2, blk + L.o_x2, (size_t)n * 12);
+    if (!taps) return;
+    if (q->edge_err && n) std::memcpy(q->edge_err, blk + L.o_err, (size_t)n * 32);
+    if (q->edge_J && n) std::memcpy(q->edge_J, blk + L.o_J, (size_t)n * 224);
+    if (q->edge_chi2) {
+        const double* chi = reinterpret_cast<const double*>(blk + L.o_chi);
+        const int rounds = h->early ? 1 : 2;
+        for (int r = 0; r < rounds && n > 0; r++)
+            for (int c = 0; c < n; c++)
+                if (flag[c] == 0 || flag[c] > r)   // tested in round r
+                    std::memcpy(q->edge_chi2 + ((size_t)r * q->cap + c) * 2, chi + ((size_t)r * L.cap + c) * 2, 16);
+    }
+    const Sim3OptIter* it = reinterpret_cast<const Sim3OptIter*>(blk + L.o_it);
+    for (int k = 0; k < std::min<int>(h->n_lm, kSoLm); k++) {
+        if (q->it_est) std::memcpy(q->it_est + 8 * k, it[k].est, 64);
+        if (q->it_chi2) q->it_chi2[k] = it[k].chi2;
+        if (q->it_H) std::memcpy(q->it_H + 28 * k, it[k].H, 224);
+        if (q->it_b) std::memcpy(q->it_b + 7 * k, it[k].b, 56);
+        if (q->it_lambda) q->it_lambda[k] = it[k].lambda;
+        if (q->it_trials) q->it_trials[k] = it[k].trials;
+        if (q->it_dx) {   // the trials that ran; zeros behind them
+            double* dx = q->it_dx + (size_t)kSoTrials * 7 * k;
+            const int t = std::max(0, std::min<int>(it[k].trials, kSoTrials));
+            std::memset(dx, 0, sizeof(it[k].dx));
+            std::memcpy(dx, it[k].dx, (size_t)t * 7 * sizeof(double));
+        }
+    }
+    if (q->check_est && n > 0) std::memcpy(q->check_est, h->check_est, (h->early ? 1 : 2) * 64);
+}
+
+// The out fields of a candidate without correspondences: no kernel work.
+void scatter_empty(orbx_sim3_opt_query* q)
+{
+    q->n_corr = q->n_bad = q->n_in = q->n_lm = 0;
+    q->returned_early = 1;
+    for (int r = 0; r < 2; r++) q->iterations[r] = q->trials[r] = q->not_posdef[r] = 0;
+}
+
+void fill_prob(Sim3OptProb& d, const orbx_sim3_opt_query& q, int n, int nlevels, const float* T1w, const float* T2w,
+               const float* cam1, const float* cam2, bool taps)
+{
+    d.n = n;
+    d.nlevels = nlevels;
+    d.taps = taps ? 1 : 0;
+    d.pad = 0;
+    std::memcpy(d.T1w, T1w, 48);
+    std::memcpy(d.T2w, T2w, 48);
+    std::memcpy(d.cam1, cam1, 16);
+    std::memcpy(d.cam2, cam2, 16);
+    std::memcpy(d.R12, q.R12, 36);
+    std::memcpy(d.t12, q.t12, 12);
+    d.s12 = q.s12;
+    d.th2 = q.th2;
+    d.delta = (double)std::sqrt(q.th2);   // const float deltaHuber = sqrt(th2) (:840)
+}
+
+int launch_sim3opt(orbx_ctx* ctx, int P, const Sim3OptProb* descs, uint8_t* res, const Sim3OptLayout& L)
+{
+    timer_begin(ctx, "sim3opt");
+    if (P == 1)
+        hipLaunchKernelGGL(k_sim3_opt<kSoWide>, dim3(1), dim3(64 * kSoWide), 0, ctx->stream, descs, res, L);
+    else
+        hipLaunchKernelGGL(k_sim3_opt<1>, dim3(P), dim3(64), 0, ctx->stream, descs, res, L);
+    timer_end(ctx, "sim3opt");
+    ORBX_HIP_CHECK(hipGetLastError());
+    return ORBX_OK;
+}
+
+}  // namespace
+
+extern "C" int orbx_optimize_sim3_batch(orbx_ctx* ctx, int B, orbx_sim3_opt_query* qs)
+{
+    if (!ctx || !qs || B < 1) return ORBX_ERR_ARG;
+    // argument rules, before any device work
+    std::vector<std::vector<int32_t>> ci(B), cj(B);
+    int cap = 1, work = 0;
+    bool taps = false;
+    size_t bytes = up16((size_t)B * sizeof(Sim3OptProb));
+    for (int b = 0; b < B; b++) {
+        const orbx_sim3_opt_query& q = qs[b];
+        if (q.n1 < 0 || q.n2 < 0 || (q.n1 > 0 && (!q.keys1 || !q.pos1 || !q.valid1)) ||
+            (q.n2 > 0 && (!q.keys2 || !q.pos2 || !q.valid2)) || !q.T1w || !q.T2w || !q.cam1 || !q.cam2 ||
+            !q.inv_sigma2_1 || !q.sigma2_2)
+            return ORBX_ERR_ARG;
+        int r = check_common(q);
+        if (r != ORBX_OK) return r;
+        if (q.nlevels < 1 || q.nlevels > kMaxLevels) return ORBX_ERR_ARG;
+        if (q.n1 > kMaxFeatures || q.n2 > kMaxFeatures) return ORBX_ERR_UNSUPPORTED;
+        for (int i = 0; i < q.n1; i++)
+            if (q.keys1[i].octave < 0 || q.keys1[i].octave >= q.nlevels) return ORBX_ERR_ARG;
+        for (int i = 0; i < q.n2; i++)
+            if (q.keys2[i].octave < 0 || q.keys2[i].octave >= q.nlevels) return ORBX_ERR_ARG;
+        if ((r = correspondences(q.matches12, q.n1, q.n2, q.valid1, 0, q.valid2, 0, &ci[b], &cj[b])) != ORBX_OK) return r;
+        const int n = (int)ci[b].size();
+        if (any_corr_tap(q) && q.cap < n) return ORBX_ERR_CAPACITY;
+        taps = taps || any_tap(q);
+        cap = std::max(cap, n);
+        work += n > 0;
+        bytes += up16((size_t)q.n1 * sizeof(orbx_keypoint)) + up16((size_t)q.n2 * sizeof(orbx_keypoint)) +
+                 2 * up16((size_t)n * 4) + up16((size_t)q.n1 * 12) + up16((size_t)q.n2 * 12) +
+                 2 * up16((size_t)q.nlevels * 4);
+    }
+    if (work == 0) {
+        for (int b = 0; b < B; b++) scatter_empty(&qs[b]);
+        return ORBX_OK;
+    }
+    ctx_enter(ctx);
+    const Sim3OptLayout L = sim3opt_layout(cap, taps);
+    const size_t o_res = up16(bytes);
+    const size_t res_bytes = (size_t)B * L.stride;
+    int r = ensure_scratch(ctx, o_res + res_bytes);
+    if (r != ORBX_OK) return r;
+    uint8_t* dev = static_cast<uint8_t*>(ctx->scratch);
+    // one upload: descriptors | per candidate: keypoints, correspondence lists, positions, level tables
+    std::vector<uint8_t> blob(o_res, 0);
+    Sim3OptProb* descs = reinterpret_cast<Sim3OptProb*>(blob.data());
+    size_t o = up16((size_t)B * sizeof(Sim3OptProb));
+    auto put = [&](const void* src, size_t nbytes) {
+        const size_t at = o;
+        if (nbytes) std::memcpy(blob.data() + at, src, nbytes);
+        o += up16(nbytes);
+        return dev + at;
+    };
+    for (int b = 0; b < B; b++) {
+        const orbx_sim3_opt_query& q = qs[b];
+        Sim3OptProb& d = descs[b];
+        const int n = (int)ci[b].size();
+        d.k1 = reinterpret_cast<const orbx_keypoint*>(put(q.keys1, (size_t)q.n1 * sizeof(orbx_keypoint)));
+        d.k2 = reinterpret_cast<const orbx_keypoint*>(put(q.keys2, (size_t)q.n2 * sizeof(orbx_keypoint)));
+        d.ci = reinterpret_cast<const int32_t*>(put(ci[b].data(), (size_t)n * 4));
+        d.cj = reinterpret_cast<const int32_t*>(put(cj[b].data(), (size_t)n * 4));
+        d.pos1 = reinterpret_cast<const float*>(put(q.pos1, (size_t)q.n1 * 12));
+        d.pos2 = reinterpret_cast<const float*>(put(q.pos2, (size_t)q.n2 * 12));
+        d.isig1 = reinterpret_cast<const float*>(put(q.inv_sigma2_1, (size_t)q.nlevels * 4));
+        d.sig2 = reinterpret_cast<const float*>(put(q.sigma2_2, (size_t)q.nlevels * 4));
+        fill_prob(d, q, n, q.nlevels, q.T1w, q.T2w, q.cam1, q.cam2, taps);
+    }
+    if (o > o_res) return ORBX_ERR_NOMEM;   // the sizes above and the layout here disagree
+    ORBX_HIP_CHECK(hipMemcpyAsync(dev, blob.data(), o_res, hipMemcpyHostToDevice, ctx->stream));
+    if ((r = launch_sim3opt(ctx, B, reinterpret_cast<const Sim3OptProb*>(dev), dev + o_res, L)) != ORBX_OK) return r;
+    std::vector<uint8_t> out(res_bytes);
+    ORBX_HIP_CHECK(hipMemcpyAsync(out.data(), dev + o_res, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    for (int b = 0; b < B; b++) {
+        if (ci[b].empty()) scatter_empty(&qs[b]);
+        else scatter(out.data() + (size_t)b * L.stride, L, ci[b], taps, &qs[b]);
+    }
+    return ORBX_OK;
+}
+
+extern "C" int orbx_optimize_sim3(orbx_ctx* ctx, orbx_sim3_opt_query* q) { return orbx_optimize_sim3_batch(ctx, 1, q); }
+
+extern "C" int orbx_dev_optimize_sim3(orbx_ctx* ctx, int slot1, const orbx_sim3_kf* kf1, const float* inv_sigma2_1, int n,
+                                      const int* slots2, const orbx_sim3_kf* kf2s, orbx_sim3_opt_query* out)
+{
+    if (!ctx || n < 0) return ORBX_ERR_ARG;
+    if (n == 0) return ORBX_OK;
+    auto kf_ok = [&](const orbx_sim3_kf* k) {
+        return k && k->mp && k->pos && k->Tcw && k->cam && k->nlevels == ctx->geom.nlevels && k->nlevels >= 1 &&
+               k->nlevels <= kMaxLevels;
+    };
+    auto slot_ok = [&](int s) { return s >= 0 && s < ctx->slots; };
+    if (!kf_ok(kf1) || !inv_sigma2_1 || !slots2 || !kf2s || !out || !slot_ok(slot1)) return ORBX_ERR_ARG;
+    for (int k = 0; k < n; k++) {
+        if (!kf_ok(&kf2s[k]) || !kf2s[k].sigma2 || !slot_ok(slots2[k]) || !out[k].matches12) return ORBX_ERR_ARG;
+        const int r = check_common(out[k]);
+        if (r != ORBX_OK) return r;
+    }
+    const int nf = ctx->geom.nfeatures;
+    if (nf > kMaxFeatures) return ORBX_ERR_UNSUPPORTED;
+    ctx_enter(ctx);
+    // the slots' feature counts bound the arrays the caller passes
+    std::vector<int32_t> cnt(ctx->slots);
+    ORBX_HIP_CHECK(hipMemcpyAsync(cnt.data(), ctx->out_n, sizeof(int32_t) * ctx->slots, hipMemcpyDeviceToHost, ctx->stream));
+    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    auto count = [&](int slot) { return std::max(0, std::min<int>(cnt[slot], nf)); };
+    const int n1 = count(slot1);
+    const int nl = kf1->nlevels;
+    std::vector<std::vector<int32_t>> ci(n), cj(n);
+    int cap = 1, work = 0;
+    bool taps = false;
+    size_t bytes = up16((size_t)n * sizeof(Sim3OptProb)) + up16((size_t)n1 * 12) + up16((size_t)nl * 4);
+    for (int k = 0; k < n; k++) {
+        const int n2 = count(slots2[k]);
+        const int r = correspondences(out[k].matches12, n1, n2, kf1->mp, 1, kf2s[k].mp, 1, &ci[k], &cj[k]);
+        if (r != ORBX_OK) return r;
+        const int nc = (int)ci[k].size();
+        if (any_corr_tap(out[k]) && out[k].cap < nc) return ORBX_ERR_CAPACITY;
+        taps = taps || any_tap(out[k]);
+        cap = std::max(cap, nc);
+        work += nc > 0;
+        bytes += 2 * up16((size_t)nc * 4) + up16((size_t)n2 * 12) + up16((size_t)nl * 4);
+    }
+    if (work == 0) {
+        for (int k = 0; k < n; k++) scatter_empty(&out[k]);
+        return ORBX_OK;
+    }
+    const Sim3OptLayout L = sim3opt_layout(cap, taps);
+    const size_t o_res = up16(bytes);
+    const size_t res_bytes = (size_t)n * L.stride;
+    int r = ensure_scratch(ctx, o_res + res_bytes);
+    if (r != ORBX_OK) return r;
+    uint8_t* dev = static_cast<uint8_t*>(ctx->scratch);
+    // what travels: descriptors | KF1: positions, inverse sigma2 | per candidate: lists, positions, sigma2
+    std::vector<uint8_t> blob(o_res, 0);
+    Sim3OptProb* descs = reinterpret_cast<Sim3OptProb*>(blob.data());
+    size_t o = up16((size_t)n * sizeof(Sim3OptProb));
+    auto put = [&](const void* src, size_t nbytes) {
+        const size_t at = o;
+        if (nbytes) std::memcpy(blob.data() + at, src, nbytes);
+        o += up16(nbytes);
+        return dev + at;
+    };
+    const float* d_pos1 = reinterpret_cast<const float*>(put(kf1->pos, (size_t)n1 * 12));
+    const float* d_isig1 = reinterpret_cast<const float*>(put(inv_sigma2_1, (size_t)nl * 4));
+    for (int k = 0; k < n; k++) {
+        Sim3OptProb& d = descs[k];
+        const int n2 = count(slots2[k]);
+        const int nc = (int)ci[k].size();
+        d.k1 = slot_frame_dev(ctx, slot1, nullptr).kps;
+        d.k2 = slot_frame_dev(ctx, slots2[k], nullptr).kps;
+        d.ci = reinterpret_cast<const int32_t*>(put(ci[k].data(), (size_t)nc * 4));
+        d.cj = reinterpret_cast<const int32_t*>(put(cj[k].data(), (size_t)nc * 4));
+        d.pos1 = d_pos1;
+        d.pos2 = reinterpret_cast<const float*>(put(kf2s[k].pos, (size_t)n2 * 12));
+        d.isig1 = d_isig1;
+        d.sig2 = reinterpret_cast<const float*>(put(kf2s[k].sigma2, (size_t)nl * 4));
+        fill_prob(d, out[k], nc, nl, kf1->Tcw, kf2s[k].Tcw, kf1->cam, kf2s[k].cam, taps);
+    }
+    if (o > o_res) return ORBX_ERR_NOMEM;
+    ORBX_HIP_CHECK(hipMemcpyAsync(dev, blob.data(), o_res, hipMemcpyHostToDevice, ctx->stream));
+    if ((r = launch_sim3opt(ctx, n, reinterpret_cast<const Sim3OptProb*>(dev), dev + o_res, L)) != ORBX_OK) return r;
+    std::vector<uint8_t> res(res_bytes);
+    ORBX_HIP_CHECK(hipMemcpyAsync(res.data(), dev + o_res, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < n; k++) {
+        if (ci[k].empty()) scatter_empty(&out[k]);
+        else scatter(res.data() + (size_t)k * L.stride, L, ci[k], taps, &out[k]);
+    }
+    return ORBX_OK;
+}
