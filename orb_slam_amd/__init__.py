@@ -620,6 +620,8 @@ def _declare(L):
         "orbx_debug_level0_direct": ([vp], i),
         "orbx_debug_fast_instance": ([vp, vp], i),
         "orbx_debug_fast_lists": ([vp, i, vp, i, vp, i, vp], i),
+        "orbx_debug_fast_list_cap": ([vp, i], i),
+        "orbx_debug_fast_paths": ([vp, i, vp, i, vp], i),
         "orbx_pose_set_exact": ([vp, i], i),
         "orbx_pose_get_exact": ([vp], i),
         "orbx_dev_set_image_bounds": ([vp, vp], i),
@@ -878,6 +880,23 @@ class Context:
         out = np.zeros(3, np.int32)
         _check(lib().orbx_debug_fast_instance(self._h, _ptr(out)), "orbx_debug_fast_instance")
         return tuple(int(v) for v in out)
+
+    def set_fast_list_cap(self, n):
+        """Capacity of the FAST kernel's scored-pixel list for the context's
+        later extractions (orbx_debug_fast_list_cap): n < 0 the default, 0
+        every cell on the dword path."""
+        _check(lib().orbx_debug_fast_list_cap(self._h, int(n)), "orbx_debug_fast_list_cap")
+
+    def fast_paths(self, slot, cells_cap=1 << 14):
+        """(paths, capacity) of a slot's last extraction
+        (orbx_debug_fast_paths): per cell the paths its bands took (bit 0: the
+        scored-pixel list, bit 1: the dword path) and the list capacity the
+        launch ran with."""
+        out = np.zeros(cells_cap, np.uint8)
+        cap = ctypes.c_int(0)
+        n = lib().orbx_debug_fast_paths(self._h, slot, _ptr(out), out.size, ctypes.byref(cap))
+        _check(min(n, 0), "orbx_debug_fast_paths")
+        return out[:n].copy(), cap.value
 
     def fast_lists(self, slot, cells_cap=1 << 14, lists_cap=1 << 22):
         """FAST's output for a slot before retainBest (orbx_debug_fast_lists):

@@ -80,7 +80,7 @@ static void free_buffers(orbx_ctx* ctx)
                     ctx->level_keys, ctx->cell_keys64, ctx->level_keys64, ctx->level_count, ctx->out_kps, ctx->out_desc, ctx->out_n,
                     ctx->match12, ctx->match_n, ctx->error_flags, ctx->dgeom.levels, ctx->dgeom.cells,
                     ctx->dgeom.res_cols, ctx->dgeom.res_rows, ctx->dgeom.umax, ctx->blur_tiles, ctx->cascade,
-                    ctx->scratch, ctx->pose_dev, ctx->bow_dev};
+                    ctx->scratch, ctx->pose_dev, ctx->bow_dev, ctx->fast_path};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (ctx->host_pinned) (void)hipHostFree(ctx->host_pinned);
@@ -118,6 +118,7 @@ static int set_geometry(orbx_ctx* ctx, int w, int h)
     }
     if ((int)g.cells.size() > ctx->cap_cells) {
         if ((r = realloc_dev(ctx->cell_count, (size_t)S * g.cells.size())) != ORBX_OK) return r;
+        if ((r = realloc_dev(ctx->fast_path, (size_t)S * g.cells.size())) != ORBX_OK) return r;
         if ((r = realloc_dev(ctx->dgeom.cells, g.cells.size())) != ORBX_OK) return r;
         ctx->cap_cells = (int)g.cells.size();
     }

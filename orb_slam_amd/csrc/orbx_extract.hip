@@ -39,7 +39,7 @@ __constant__ __attribute__((aligned(4))) int8_t c_pattern[256][4] = {
 };
 
 #ifdef ORBX_FAST_PROFILE
-__device__ unsigned long long g_fast_prof[24];
+__device__ unsigned long long g_fast_prof[32];
 __device__ inline unsigned long long fp_stamp()
 {
     unsigned long long t;
@@ -56,7 +56,7 @@ __device__ inline unsigned long long fp_stamp()
 #define FP_ADD(k, v) atomicAdd(&g_fast_prof[k], (unsigned long long)(v))
 extern "C" int orbx_debug_fast_prof(unsigned long long* out)
 {
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fast_prof), sizeof(unsigned long long) * 24) == hipSuccess ? 0 : -2;
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fast_prof), sizeof(unsigned long long) * 32) == hipSuccess ? 0 : -2;
 }
 #else
 #define FP_T0()
@@ -75,6 +75,7 @@ struct ExtractArgs {
     uint8_t* pyr_blur;
     uint32_t* cell_lists;
     int32_t* cell_count;
+    uint8_t* fast_path;             // slots x ncells (all slots, indexed from first_slot): k_fast_cells' path per cell
     uint32_t* level_keys;
     int32_t* level_count;
     orbx_keypoint* out_kps;
@@ -955,6 +956,13 @@ __device__ inline uint32_t fast_arc2(const uint8_t* t, int pa, int pb, int pitch
 //     scan), kept pixels set their `kept` bit;
 //  3. raster-order compaction of the `kept` bitmap (tile byte order is
 //     raster order), one block scan over ~2 bitmap words per thread.
+// Where the launch has LDS to spare (plist_cap > 0), `kept` lies behind nz
+// (cleared with the maps) and is followed by a list of plist_cap scored
+// pixels: the score pass appends every pixel it stores, and a cell (band)
+// whose pixels all fit is suppressed and emitted from that list, one lane per
+// scored pixel (2 and 3 above, without nz, the dword list and the bit-serial
+// loops).  A cell with more scored pixels derives nz from the S' map and
+// takes the dword path.
 // ---------------------------------------------------------------------------
 __device__ inline int byte_of(uint32_t w, int k) { return (int)((w >> (8 * k)) & 0xFF); }
 
@@ -983,6 +991,16 @@ __host__ __device__ constexpr int fast_lds_bytes(int tile_bytes) { return 2 * ti
 // static LDS of a 256-thread FAST workgroup: 4 survivor queues of 384
 // entries (u16, or u32 for the runtime-pitch instance) + block scratch
 __host__ __device__ constexpr int fast_static_lds(bool u32_entries) { return 4 * 384 * (u32_entries ? 4 : 2) + 64; }
+// Extra dynamic LDS of the scored-pixel list path, behind fast_lds_bytes: the
+// kept bitmap (one bit per tile byte) and the list of n entries.
+__host__ __device__ constexpr int fast_list_lds(int tile_bytes, int n, bool u32_entries)
+{
+    return n > 0 ? tile_bytes / 8 + (((n + 1) * (u32_entries ? 4 : 2) + 15) & ~15) : 0;   // + the spare entry
+}
+// Default capacity of the list: the largest that the u16 prefix table and a
+// cell of ~1000 scored pixels (the bench's 640x480 frames peak near that)
+// need; a fuller cell takes the dword path.
+constexpr int kFastListCap = 1536;
 #ifndef ORBX_FAST_LDS_TARGET
 #define ORBX_FAST_LDS_TARGET (40 * 1024)   // 4 workgroups per CU
 #endif
@@ -1003,7 +1021,7 @@ constexpr int kDiagRepeat[4] = {ORBX_DIAG_REPEAT};
 // get more waves per workgroup instead.
 template <int kP, int kThreads = 256, bool kBanded = false>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(kThreads > 256 ? 6 : 4))) void k_fast_cells(
-    ExtractArgs a, int tile_bytes, int band_rows)
+    ExtractArgs a, int tile_bytes, int band_rows, int plist_cap)
 {
     constexpr int kBlock = kThreads, kWaves = kThreads / 64;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -1025,7 +1043,12 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(kThrea
     QEntry* cand = reinterpret_cast<QEntry*>(qbuf) + wv * kQueue;
     // S' (0 where not scored) and nz start at zero (contiguous: tile_bytes *
     // (1 + 1/32), a multiple of 16); kept is cleared after the score pass
-    const int clear16 = (tile_bytes + tile_bytes / 32) >> 4;
+    // (with a scored-pixel list, the kept bitmap behind nz is cleared too)
+    const int clear16 = (tile_bytes + tile_bytes / 32 + (plist_cap > 0 ? tile_bytes / 8 : 0)) >> 4;
+    // prefix of the kept bitmap's words (u16, list path), aliasing the queues
+    uint16_t* kprefix = reinterpret_cast<uint16_t*>(qbuf);
+    int& s_nlist = bs.vars[0];   // scored pixels of the band (may exceed plist_cap)
+    const uint32_t nlist_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) int*)&s_nlist;
     auto clear_maps_at = [&](uint8_t* sm) {
         for (int i = tid; i < clear16; i += kBlock) reinterpret_cast<uint4*>(sm)[i] = make_uint4(0, 0, 0, 0);
     };
@@ -1056,8 +1079,12 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(kThrea
     const uint8_t* src = ls.base + (size_t)(kEdge + C.ini_y) * lstride + x_al;
     uint32_t* tile32 = reinterpret_cast<uint32_t*>(tile);
     uint32_t* sm32 = reinterpret_cast<uint32_t*>(sm);
-    uint32_t* kept = tile32;                                      // bit per tile byte (after scoring)
     uint32_t* nz = reinterpret_cast<uint32_t*>(sm + tile_bytes);  // bit per tile dword
+    // bit per tile byte: in the tile (after scoring), or behind nz with the list
+    const bool listed = plist_cap > 0;                            // uniform over the launch
+    uint32_t* kept = listed ? nz + (tile_bytes >> 7) : tile32;
+    QEntry* plist = reinterpret_cast<QEntry*>(sm + tile_bytes + tile_bytes / 32 + tile_bytes / 8);
+    int path_mask = 0;   // 1: a band took the list path, 2: the dword path
     FP_T0();
     // the cell's rows [w0, w0 + wh) into tile rows 0 .. wh - 1
     auto load_tile = [&](int w0, int wh) {
@@ -1114,13 +1141,51 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(kThrea
             // S + 1 from the bit pattern (a set sign bit: a negative int16)
             const uint32_t rb = fast_arc2(tile, pa, pb, P);
             const int Sa = (int)(int16_t)rb - 1, Sb = ((int32_t)rb >> 16) - 1;
-            if (Sa >= tmin) {
-                sm[pa] = (uint8_t)Sa;
-                set_nz(pa);
-            }
-            if (has_b && Sb >= tmin) {
-                sm[pb] = (uint8_t)Sb;
-                set_nz(pb);
+            const bool st_a = Sa >= tmin, st_b = has_b && Sb >= tmin;
+            if (listed) {
+                // the stored pixels join the band's list: one LDS atomic per
+                // batch (by the first lane that stores; the compiler's own
+                // wave aggregation of atomicAdd cost 20 more instructions),
+                // slots by lane rank (a's, then b's); entries past the
+                // capacity go to the spare entry behind it, the count goes on
+                const uint64_t ma = __builtin_amdgcn_ballot_w64(st_a), mb = __builtin_amdgcn_ballot_w64(st_b);
+                const uint32_t na = (uint32_t)__popcll(ma), nab = na + (uint32_t)__popcll(mb);
+                uint32_t base = 0;
+                if (nab) {   // uniform
+                    const uint32_t first = (uint32_t)__builtin_ctzll(ma | mb);
+                    uint64_t saved;
+                    uint32_t ret;
+                    asm volatile("s_mov_b64 %0, exec\n\t"
+                                 "s_mov_b64 exec, %2\n\tds_add_rtn_u32 %1, %3, %4\n\t"
+                                 "s_mov_b64 exec, %0\n\ts_waitcnt lgkmcnt(0)"
+                                 : "=&s"(saved), "=&v"(ret)
+                                 : "s"(1ull << first), "v"(nlist_lds), "v"(nab)
+                                 : "memory");
+                    base = (uint32_t)__builtin_amdgcn_readlane((int)ret, (int)first);
+#ifdef ORBX_FAST_PROFILE
+                    if (lane == first) FP_ADD(19, nab);
+#endif
+                }
+                const uint32_t ia = __builtin_amdgcn_mbcnt_hi((uint32_t)(ma >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ma, base));
+                const uint32_t ib =
+                    __builtin_amdgcn_mbcnt_hi((uint32_t)(mb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mb, base + na));
+                if (st_a) {
+                    sm[pa] = (uint8_t)Sa;
+                    plist[min(ia, (uint32_t)plist_cap)] = (QEntry)pa;
+                }
+                if (st_b) {
+                    sm[pb] = (uint8_t)Sb;
+                    plist[min(ib, (uint32_t)plist_cap)] = (QEntry)pb;
+                }
+            } else {
+                if (st_a) {
+                    sm[pa] = (uint8_t)Sa;
+                    set_nz(pa);
+                }
+                if (st_b) {
+                    sm[pb] = (uint8_t)Sb;
+                    set_nz(pb);
+                }
             }
         };
         // pass <=> max(v - A, B - v) >= tmin + 1 with A = min of the four
@@ -1404,12 +1469,95 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(kThrea
         }
         return c1;
     };
+    // The same from the band's list of scored pixels (n <= plist_cap of them,
+    // in any order), one per lane: S' against the map's eight neighbour bytes
+    // (0 where not scored; a scored pixel is an interior one, so all eight
+    // lie in its tile rows' neighbours).
+    bool on_list = false;   // the current band's path
+    auto nms_list = [&](const int rb0, const int rb1, const int n) {
+        int c1 = 0;
+        const int ft = max(a.fast_th, 1);
+        for (int i = tid; i < n; i += kBlock) {
+            const int pos = (int)plist[i];
+            const uint8_t* m = sm + pos;
+            const uint32_t s = m[0];
+            const uint32_t up = max(max((uint32_t)m[-P - 1], (uint32_t)m[-P]), (uint32_t)m[-P + 1]);
+            const uint32_t dn = max(max((uint32_t)m[P - 1], (uint32_t)m[P]), (uint32_t)m[P + 1]);
+            bool keep = s > max(max(up, dn), max((uint32_t)m[-1], (uint32_t)m[1]));
+            if constexpr (kBanded) {   // halo rows are scored, not kept
+                const int rw = pos / P;
+                keep = keep && rw >= rb0 && rw < rb1;
+            }
+            if (keep) {
+                atomicOr(&kept[pos >> 5], 1u << (pos & 31));
+                c1 += (int)s >= ft;
+            }
+        }
+#ifdef ORBX_FAST_PROFILE
+        if (tid == 0) FP_ADD(20, (n + kBlock - 1) / kBlock);
+        if (tid == 0) atomicMax(&g_fast_prof[21], (unsigned long long)n);
+#endif
+        return c1;
+    };
+    // The dword path's nz bitmap from the S' map (a band whose scored pixels
+    // overflowed the list): each wave's 64 dwords are two nz words.
+    auto nz_from_map = [&]() {
+        for (int i = tid; i < (tile_bytes >> 2); i += kBlock) {   // tile_bytes / 4 is a multiple of 128
+            const uint64_t b = __builtin_amdgcn_ballot_w64(sm32[i] != 0);
+            if (lane == 0) *reinterpret_cast<uint64_t*>(&nz[i >> 5]) = b;
+        }
+    };
     uint32_t* out = a.cell_lists + (size_t)f * a.list_entries + C.list_off;
+    // The list path's emission into the cell's list at out_base (t, tmin and
+    // the return value as compact's, below): a kept pixel's raster rank is
+    // the prefix of its bitmap word (one block scan, written to LDS) plus the
+    // kept bits below it in the word; each listed pixel's lane writes its own
+    // entry.
+    auto emit_list = [&](const int t, const int tmin, const int w0, const int wh, const int out_base) {
+        const int n = s_nlist;
+        if (t != tmin) {   // fastTh < 7 fell back to 7: only S' >= t is emitted, and ranked
+            for (int i = tid; i < n; i += kBlock) {
+                const int pos = (int)plist[i];
+                if (sm[pos] < t) atomicAnd(&kept[pos >> 5], ~(1u << (pos & 31)));
+            }
+            __syncthreads();
+        }
+        const int nkw = (wh * P + 31) >> 5;
+        const int per = (nkw + kBlock - 1) / kBlock;
+        const int ka = min(tid * per, nkw), kb = min(ka + per, nkw);
+        int cnt = 0;
+        for (int k = ka; k < kb; k++) cnt += __popc(kept[k]);
+        int total;
+        int off = block_exclusive_scan(cnt, &total, bs, 1);
+        for (int k = ka; k < kb; k++) {
+            kprefix[k] = (uint16_t)off;
+            off += __popc(kept[k]);
+        }
+        __syncthreads();
+        for (int i = tid; i < n; i += kBlock) {
+            const int pos = (int)plist[i];
+            const uint32_t w = kept[pos >> 5], bit = 1u << (pos & 31);
+            if (w & bit) {
+                const int o = out_base + (int)kprefix[pos >> 5] + __popc(w & (bit - 1));
+                if (o < C.list_cap) {
+                    const int r = w0 + pos / P, cc = pos % P - sh;   // cell row, ROI column
+                    out[o] = ((uint32_t)sm[pos] << 24) | ((uint32_t)(C.ini_y + r) << 12) | (uint32_t)(C.ini_x + cc);
+                }
+            }
+        }
+#ifdef ORBX_FAST_PROFILE
+        if (tid == 0) FP_ADD(22, total);
+        if (tid == 0) atomicMax(&g_fast_prof[23], (unsigned long long)total);
+#endif
+        return total;
+    };
     // Raster-order compaction of the kept bitmap into the cell's list at
     // out_base: thread tid owns the contiguous bitmap words [ka, kb); kept
     // bytes are S' >= tmin of the pass, and t == tmin unless fastTh < 7 fell
     // back to 7 (then each byte is compared).  Returns the entries written.
+    // (A band on the list path: emit_list.)
     auto compact = [&](const int t, const int tmin, const int w0, const int wh, const int out_base) {
+        if (on_list) return emit_list(t, tmin, w0, wh, out_base);
         const int nkw = (wh * P + 31) >> 5;
         const int per = (nkw + kBlock - 1) / kBlock;
         const int ka = min(tid * per, nkw), kb = min(ka + per, nkw);
@@ -1471,6 +1619,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(kThrea
             load_tile(w0, wh);
             FP_MARK(5);
             clear_maps();
+            if (tid == 0) s_nlist = 0;
             FP_MARK(6);
             __syncthreads();
         }
@@ -1478,10 +1627,24 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(kThrea
         score_pass(tmin, s0 - w0, s1 - s0 + 1);
         __syncthreads();
         FP_MARK(1);
-        clear_kept();   // the tile is dead until the next band reloads it
-        __syncthreads();
-        const int n1 = block_sum(nms_pass(b0 - w0, b1 - w0, wh), bs, 0);
-        __syncthreads();
+        int c1;
+        on_list = listed && s_nlist <= plist_cap;   // uniform over the block
+        if (on_list) {
+            c1 = nms_list(b0 - w0, b1 - w0, s_nlist);
+        } else {
+            if (listed) nz_from_map();   // kept is clear already
+            else clear_kept();           // the tile is dead until the next band reloads it
+            __syncthreads();
+            c1 = nms_pass(b0 - w0, b1 - w0, wh);
+        }
+        path_mask |= on_list ? 1 : 2;
+        if (tid == 0) FP_ADD(on_list ? 24 : 25, 1);
+        // (its barrier also ends the kept bitmap's updates)
+        const int n1 = block_sum(c1, bs, 0);
+        // (the list path's next steps touch nothing that a thread still
+        // before this point reads: s_nlist, the list and S' were read before
+        // block_sum's barrier)
+        if (!on_list) __syncthreads();
         return n1;
     };
     // Thresholds (:599-614): FAST(fastTh), and FAST(7) when that finds <= 3
@@ -1526,6 +1689,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(kThrea
     }
     if (tid == 0) {
         *count_out = written;
+        a.fast_path[(size_t)(a.first_slot + f) * a.ncells + cell] = (uint8_t)path_mask;
         if (written > C.list_cap) atomicOr(a.error_flags, 1);
     }
     FP_MARK(4);
@@ -2588,6 +2752,39 @@ extern "C" int orbx_debug_fast_instance(orbx_ctx* ctx, int* out)
     return ORBX_OK;
 }
 
+/* Diagnostics (not in include/orbx.h): the capacity (entries) of k_fast_cells'
+ * scored-pixel list for the context's later extractions; n < 0 restores the
+ * default, 0 sends every cell down the dword path.  A launch without LDS for
+ * it runs with capacity 0 whatever is set.  Set it before the context's first
+ * orbx_extract (whose captured graph keeps the launch's arguments). */
+extern "C" int orbx_debug_fast_list_cap(orbx_ctx* ctx, int n)
+{
+    if (!ctx) return ORBX_ERR_ARG;
+    ctx->fast_list_cap = n < 0 ? -1 : n;
+    return ORBX_OK;
+}
+
+/* Diagnostics (not in include/orbx.h): per cell of slot `slot`'s last
+ * extraction, the paths its bands took through NMS and emission (bit 0: the
+ * scored-pixel list, bit 1: the dword path; 0: nothing scored, an invalid
+ * cell or one without interior rows); *list_cap gets the capacity the last
+ * launch ran with.  Returns the number of cells. */
+extern "C" int orbx_debug_fast_paths(orbx_ctx* ctx, int slot, uint8_t* out, int cap, int* list_cap)
+{
+    if (!ctx || !out || !list_cap || slot < 0 || slot >= ctx->slots || ctx->last_fast[0] < 0) return ORBX_ERR_ARG;
+    ctx_enter(ctx);
+    const orbx::Geometry& g = ctx->geom;
+    const int n = (int)g.cells.size();
+    if (cap < n) return ORBX_ERR_CAPACITY;
+    if (hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(out, ctx->fast_path + (size_t)slot * n, (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
+        return ORBX_ERR_HIP;
+    for (int c = 0; c < n; c++)
+        if (!g.cells[c].valid) out[c] = 0;
+    *list_cap = ctx->last_fast[3];
+    return n;
+}
+
 /* Diagnostics (not in include/orbx.h): FAST's output for slot `slot` of the
  * last extraction, before retainBest: per cell 10 ints in `cells` (level,
  * ini_x, ini_y, hx, hy, valid, list offset, list capacity, corner count, 0)
@@ -2647,6 +2844,7 @@ int launch_extract(orbx_ctx* ctx, int first, int count, const MatchSpec* m)
     a.pyr_blur = nullptr;   // off the extraction path (launch_blur_slot fills the one-frame buffer)
     a.cell_lists = ctx->cell_lists + (size_t)first * g.list_entries;
     a.cell_count = ctx->cell_count + (size_t)first * g.cells.size();
+    a.fast_path = ctx->fast_path;
     a.level_keys = ctx->level_keys + (size_t)first * g.level_entries;
     a.level_count = ctx->level_count + (size_t)first * g.nlevels;
     a.out_kps = ctx->out_kps;
@@ -2787,7 +2985,17 @@ int launch_extract(orbx_ctx* ctx, int first, int count, const MatchSpec* m)
                 ctx->last_fast[0] = pitch;
                 ctx->last_fast[1] = threads;
                 ctx->last_fast[2] = band_rows;
-                hipLaunchKernelGGL(kern, grid, dim3(threads), lds, st, x, bytes, band_rows);
+                // The scored-pixel list and its kept bitmap go behind the
+                // planned bytes where the workgroup stays within the target
+                // (and the bitmap's u16 prefix table fits the queues' 3 KB);
+                // else capacity 0: every cell on the dword path.
+                const bool u32e = pitch == 0;
+                int cap = ctx->fast_list_cap < 0 ? kFastListCap : std::min(ctx->fast_list_cap, 4096);
+                if (cap > 0 && (lds + fast_static_lds(u32e) + fast_list_lds(bytes, cap, u32e) > kFastLdsTarget || bytes / 32 > 1536))
+                    cap = 0;
+                ctx->last_fast[3] = cap;
+                hipLaunchKernelGGL(kern, grid, dim3(threads), lds + fast_list_lds(bytes, cap, u32e), st, x, bytes, band_rows,
+                                   cap);
             };
             // the templated instances queue u16 tile positions: windows of up
             // to 64 KB (larger ones take the runtime-pitch instance)

@@ -287,7 +287,9 @@ struct orbx_ctx {
     bool last_l0_direct = false;          // the last launch_extract read level 0 from the frame store
     // the k_fast_cells instance of the last launch_extract: tile pitch (0: the
     // runtime-pitch instance), workgroup threads, band rows (0: whole cells)
-    int last_fast[3] = {-1, 0, 0};
+    int last_fast[4] = {-1, 0, 0, 0};     // [3]: the scored-pixel list's capacity (0: dword path only)
+    int fast_list_cap = -1;               // orbx_debug_fast_list_cap (-1: the default)
+    uint8_t* fast_path = nullptr;         // slots x cells: the path each cell's bands took (1 list, 2 dword)
     // Frame::ComputeImageBounds of the slots' keypoints (orbx_dev_set_image_bounds;
     // has_bounds 0: 0..w x 0..h, the undistorted case) for the device matchers
     int has_bounds = 0;
