@@ -617,6 +617,7 @@ def _declare(L):
         "orbx_lba_last_workgroups": ([vp], i),
         "orbx_debug_lba_split": ([vp, i, i, i, i], i),
         "orbx_debug_describe_patch": ([vp, i, i, i, i, vp], i),
+        "orbx_debug_describe_moments": ([vp, i, i, i, i, vp], i),
         "orbx_debug_level0_direct": ([vp], i),
         "orbx_debug_fast_instance": ([vp, vp], i),
         "orbx_debug_fast_lists": ([vp, i, vp, i, vp, i, vp], i),
@@ -864,6 +865,14 @@ class Context:
         out = np.zeros((37, 37), np.uint8)
         _check(lib().orbx_debug_describe_patch(self._h, slot, level, x, y, _ptr(out)), "orbx_debug_describe_patch")
         return out
+
+    def describe_moments(self, slot, level, x, y):
+        """IC_Angle's moments as the describe kernel computes them at level
+        position (x, y) of the slot's pyramid: (m01, m10) of the wave's lower
+        half and of its upper half (orbx_debug_describe_moments)."""
+        out = np.zeros(4, np.int32)
+        _check(lib().orbx_debug_describe_moments(self._h, slot, level, x, y, _ptr(out)), "orbx_debug_describe_moments")
+        return (int(out[0]), int(out[1])), (int(out[2]), int(out[3]))
 
     def level0_direct(self):
         """Whether the last extraction read pyramid level 0 from the frame

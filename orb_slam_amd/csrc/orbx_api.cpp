@@ -79,7 +79,7 @@ static void free_buffers(orbx_ctx* ctx)
     void* ptrs[] = {ctx->frames, ctx->pyr_raw, ctx->pyr_blur, ctx->cell_lists, ctx->retain_scratch, ctx->cell_count,
                     ctx->level_keys, ctx->cell_keys64, ctx->level_keys64, ctx->level_count, ctx->out_kps, ctx->out_desc, ctx->out_n,
                     ctx->match12, ctx->match_n, ctx->error_flags, ctx->dgeom.levels, ctx->dgeom.cells,
-                    ctx->dgeom.res_cols, ctx->dgeom.res_rows, ctx->dgeom.umax, ctx->blur_tiles, ctx->cascade,
+                    ctx->dgeom.res_cols, ctx->dgeom.res_rows, ctx->dgeom.ic_rows, ctx->blur_tiles, ctx->cascade,
                     ctx->scratch, ctx->pose_dev, ctx->bow_dev, ctx->fast_path};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
@@ -327,7 +327,7 @@ int orbx_create(orbx_ctx** out, int device, int nfeatures, float scale_factor, i
     for (int i = 0; r == ORBX_OK && i < orbx_ctx::kMaxUploads; i++)
         if (hipEventCreateWithFlags(&ctx->ev_upload[i], hipEventDisableTiming) != hipSuccess) r = ORBX_ERR_HIP;
     if (r == ORBX_OK) r = realloc_dev(ctx->dgeom.levels, kMaxLevels);
-    if (r == ORBX_OK) r = realloc_dev(ctx->dgeom.umax, kHalfPatch + 1);
+    if (r == ORBX_OK) r = realloc_dev(ctx->dgeom.ic_rows, kIcTabRows * kIcTabDw);
     if (r == ORBX_OK) r = realloc_dev(ctx->level_count, (size_t)S * nlevels);
     if (r == ORBX_OK) r = realloc_dev(ctx->out_kps, (size_t)S * nfeatures);
     if (r == ORBX_OK) r = realloc_dev(ctx->out_desc, (size_t)S * nfeatures * 32);
@@ -337,9 +337,11 @@ int orbx_create(orbx_ctx** out, int device, int nfeatures, float scale_factor, i
     if (r == ORBX_OK) r = realloc_dev(ctx->error_flags, 4);
     if (r == ORBX_OK && hipMemset(ctx->error_flags, 0, 4 * sizeof(int32_t)) != hipSuccess) r = ORBX_ERR_HIP;
     if (r == ORBX_OK && hipMemset(ctx->out_n, 0, S * sizeof(int32_t)) != hipSuccess) r = ORBX_ERR_HIP;
-    if (r == ORBX_OK &&
-        hipMemcpy(ctx->dgeom.umax, ctx->geom.umax.data(), ctx->geom.umax.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
-        r = ORBX_ERR_HIP;
+    if (r == ORBX_OK) {   // IC_Angle's circle (geom.umax) in the form k_describe reads
+        const std::vector<uint32_t> rows = ic_row_table(ctx->geom);
+        if (hipMemcpy(ctx->dgeom.ic_rows, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
+            r = ORBX_ERR_HIP;
+    }
     // size the per-frame buffers for the largest frame up front
     if (r == ORBX_OK) r = set_geometry(ctx, max_w, max_h);
     if (r != ORBX_OK) {

@@ -69,7 +69,7 @@ struct ExtractArgs {
     const CellGeom* cells;
     const ResizeCol* res_cols;
     const ResizeRow* res_rows;
-    const int* umax;
+    const uint32_t* ic_rows;   // ic_row_table: IC_Angle's circle, by rows
     const uint8_t* frames;
     uint8_t* pyr_raw;
     uint8_t* pyr_blur;
@@ -2324,6 +2324,56 @@ __device__ inline int half_wave_sum(int v)
     return (threadIdx.x & 32) ? hi : lo;
 }
 
+// IC_Angle (src/ORBextractor.cc:124-151) on the staged raw window, by rows:
+// lane hl of the half owns row v = hl - 15 of the circular patch (lane 31:
+// the table's row of zeros).  The moments are integer sums, exact in any
+// order: m01 = sum_v v * S1(v) and m10 = sum_v (Su(v) - 16 S1(v)) with
+// S1 = sum_u inside * I and Su = sum_u (u + 16) * inside * I over the row's
+// bytes u = -15 .. 16.  Those 32 bytes start at window byte (X - x0) - 15 =
+// 6 .. 9 of the row: nine aligned dwords, shifted into place by a byte count
+// that is uniform in the half, then one v_dot4_u32_u8 per dword and sum
+// against the row's weights (ic_row_table: 0 outside the circle, which also
+// drops the byte at u = 16).  Every partial stays below 2^23.
+// describe_ic_weights: the lane's table row, loaded ahead of the staging.
+__device__ __forceinline__ void describe_ic_weights(const uint32_t* ic_rows, int hl, uint32_t (&t)[kIcTabDw])
+{
+    const int row = min(abs(hl - kHalfPatch), kHalfPatch + 1);
+    const uint4* p = reinterpret_cast<const uint4*>(ic_rows + row * kIcTabDw);
+#pragma unroll
+    for (int q = 0; q < kIcTabDw / 4; q++) {
+        const uint4 w = p[q];
+        t[4 * q] = w.x;
+        t[4 * q + 1] = w.y;
+        t[4 * q + 2] = w.z;
+        t[4 * q + 3] = w.w;
+    }
+}
+
+// win: the staged window of the keypoint at padded level column X; returns
+// the half's moments in every lane of the half.
+__device__ __forceinline__ void describe_moments(const uint8_t* win, int X, int hl, const uint32_t (&t)[kIcTabDw],
+                                                 int& m01, int& m10)
+{
+    static_assert(kIcTabDw == 16 && ((kWinR - kHalfPatch + 3) & ~3) + 36 <= kBrPitch &&
+                      kWinR - kHalfPatch + kIcRows < kWinRows,
+                  "nine dwords from the row's byte 4 or 8 stay inside the row, lane 31's row inside the window");
+    const int b0 = kWinR - kHalfPatch + ((X - kWinR) & 3);   // the row's byte of u = -15
+    const uint32_t* row = reinterpret_cast<const uint32_t*>(win) + (kWinR - kHalfPatch + hl) * kWinDw + (b0 >> 2);
+    uint32_t w[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) w[i] = row[i];
+    const uint32_t sh = (uint32_t)b0 & 3u;
+    uint32_t s1 = 0, su = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const uint32_t d = __builtin_amdgcn_alignbyte(w[i + 1], w[i], sh);
+        s1 = __builtin_amdgcn_udot4(d, t[i], s1, false);
+        su = __builtin_amdgcn_udot4(d, t[8 + i], su, false);
+    }
+    m01 = half_wave_sum((hl - kHalfPatch) * (int)s1);
+    m10 = half_wave_sum((int)su - 16 * (int)s1);
+}
+
 // Two keypoints per wave, one per 32-lane half, eight per workgroup: the
 // per-keypoint scalar steps (fastAtan2, the correctly rounded sin/cos) run
 // once per workgroup, one keypoint per lane of one wave, and the pattern's
@@ -2375,7 +2425,7 @@ struct DescTrig {
 };
 
 // 5 waves per SIMD: the register allocator otherwise spends past 128 VGPRs
-// on hoisted window reads (the kernel is VALU-bound; 88 VGPRs, no spills)
+// on hoisted window reads (the kernel is VALU-bound; 90 VGPRs, no spills)
 template <bool kFma>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k_describe(ExtractArgs a, int nframes)
 {
@@ -2394,8 +2444,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k
     const int slot = wv * 2 + half;
     const int k0 = chunk * (2 * kWaves) + wv * 2, k = k0 + half;
     // tables needed later, loaded up front (independent of the keypoint):
-    // umax[0..15] one entry per lane, this lane's 8 pattern pairs
-    const int umax_l = a.umax[min(lane, kHalfPatch)];
+    // this lane's row of IC_Angle's weights, its 8 pattern pairs
+    uint32_t icw[kIcTabDw];
+    describe_ic_weights(a.ic_rows, hl, icw);
     uint32_t pat[8];
 #pragma unroll
     for (int r = 0; r < 8; r++) pat[r] = *reinterpret_cast<const uint32_t*>(c_pattern[r * 32 + hl]);
@@ -2471,31 +2522,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k
         x = (int)(e & 0xFFF);
         X = kEdge + (valid ? x : kHalfPatch + 8);
         Y = kEdge + (valid ? y : kHalfPatch + 8);
-        // the raw window; ic / br: its centre, the patch centre of IC_Angle now
-        // and of the blurred patch after describe_blur_window
+        // the raw window; br: its centre, the centre of the blurred patch
+        // after describe_blur_window
         const LevelSrc ls = level_src(a, f, level, lev_off, lev_stride);
-        const uint8_t* ic = win + describe_stage_window(ls.base, (uint32_t)ls.stride, a.l0_direct && level == 0, lev_w,
-                                                        lev_h, X, Y, win, hl);
-        br = ic;
+        br = win + describe_stage_window(ls.base, (uint32_t)ls.stride, a.l0_direct && level == 0, lev_w, lev_h, X, Y,
+                                         win, hl);
         wave_lds_sync();
-        // IC_Angle on the unblurred level (src/ORBextractor.cc:124-151): lane u
-        // of the half takes column u - 15 over all rows of the circular patch
-        // umax read back from the lanes with readlane: no table loads in the loop
-        if (hl < kIcRows) {
-            const int u = hl - kHalfPatch;
-            m10 = u * ic[u];
-#pragma unroll
-            for (int v = 1; v <= kHalfPatch; v++) {
-                const int d = __builtin_amdgcn_readlane(umax_l, v);
-                if (u >= -d && u <= d) {
-                    const int vp = ic[u + v * kBrPitch], vm = ic[u - v * kBrPitch];
-                    m01 += v * (vp - vm);
-                    m10 += u * (vp + vm);
-                }
-            }
-        }
-        m01 = half_wave_sum(m01);
-        m10 = half_wave_sum(m10);
+        // IC_Angle on the unblurred level
+        describe_moments(win, X, hl, icw, m01, m10);
     }
     // fastAtan2 and the correctly rounded sin/cos are one value per keypoint:
     // one wave of the workgroup (a different one from block to block, so the
@@ -2648,6 +2682,27 @@ __global__ __launch_bounds__(64) void k_debug_describe_patch(const uint8_t* lev,
         }
 }
 
+// Test hook: k_describe's window staging and IC_Angle moments for one position
+// of one level, both halves of the wave on the same keypoint; out: m01, m10 of
+// half 0, then of half 1.
+__global__ __launch_bounds__(64) void k_debug_describe_moments(const uint8_t* lev, int stride, int direct, LevelGeom L,
+                                                               const uint32_t* ic_rows, int X, int Y, int* out)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t s_patch[2][kDescWaveBytes];
+    const int lane = threadIdx.x, half = lane >> 5, hl = lane & 31;
+    uint8_t* win = s_patch[half] + kWinPad;
+    uint32_t icw[kIcTabDw];
+    describe_ic_weights(ic_rows, hl, icw);
+    describe_stage_window(lev, (uint32_t)stride, direct != 0, L.w, L.h, X, Y, win, hl);
+    wave_lds_sync();
+    int m01, m10;
+    describe_moments(win, X, hl, icw, m01, m10);
+    if (hl == 0) {
+        out[2 * half] = m01;
+        out[2 * half + 1] = m10;
+    }
+}
+
 // k_pyr_level0 over nb frames on stream st (x: levels, frames, first_slot,
 // pyr_raw, w, h).
 static void launch_level0(const Geometry& g, const ExtractArgs& x, int nb, hipStream_t st)
@@ -2728,6 +2783,35 @@ extern "C" int orbx_debug_describe_patch(orbx_ctx* ctx, int slot, int level, int
     int r = ORBX_OK;
     if (hipStreamSynchronize(ctx->stream) != hipSuccess ||
         hipMemcpy(out, d, kBrRows * kBrRows, hipMemcpyDeviceToHost) != hipSuccess)
+        r = ORBX_ERR_HIP;
+    (void)hipFree(d);
+    return r;
+}
+
+/* Diagnostics (not in include/orbx.h): IC_Angle's moments as k_describe
+ * computes them for a keypoint at level position (x, y) of slot `slot`'s raw
+ * pyramid (the same range as above): out = m01, m10 of the wave's lower half,
+ * then of its upper half, both on the same keypoint. */
+extern "C" int orbx_debug_describe_moments(orbx_ctx* ctx, int slot, int level, int x, int y, int32_t* out)
+{
+    using namespace orbx;
+    if (!ctx || !out || slot < 0 || slot >= ctx->slots || level < 0 || level >= ctx->geom.nlevels) return ORBX_ERR_ARG;
+    const LevelGeom& L = ctx->geom.levels[level];
+    if (x < kEdge || x >= L.w - kEdge || y < kEdge || y >= L.h - kEdge) return ORBX_ERR_ARG;
+    ctx_enter(ctx);
+    int* d = nullptr;
+    if (hipDeviceSynchronize() != hipSuccess) return ORBX_ERR_HIP;   // every part stream's pyramid
+    if (hipMalloc(&d, 4 * sizeof(int)) != hipSuccess) return ORBX_ERR_NOMEM;
+    // the level as k_describe sees it (see orbx_debug_describe_patch)
+    const bool direct = level == 0 && kEdge == 16 && ctx->geom.w % 16 == 0;
+    const long long fw = ctx->geom.w, fh = ctx->geom.h;
+    const uint8_t* lev = direct ? ctx->frames + ((long long)slot * fw * fh - (long long)kEdge * fw - kEdge)
+                                : ctx->pyr_raw + (size_t)slot * ctx->geom.frame_pyr_bytes + L.off;
+    hipLaunchKernelGGL(k_debug_describe_moments, dim3(1), dim3(64), 0, ctx->stream, lev, direct ? (int)fw : L.stride,
+                       direct ? 1 : 0, L, ctx->dgeom.ic_rows, kEdge + x, kEdge + y, d);
+    int r = ORBX_OK;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess ||
+        hipMemcpy(out, d, 4 * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
         r = ORBX_ERR_HIP;
     (void)hipFree(d);
     return r;
@@ -2836,7 +2920,7 @@ int launch_extract(orbx_ctx* ctx, int first, int count, const MatchSpec* m)
     a.cells = ctx->dgeom.cells;
     a.res_cols = ctx->dgeom.res_cols;
     a.res_rows = ctx->dgeom.res_rows;
-    a.umax = ctx->dgeom.umax;
+    a.ic_rows = ctx->dgeom.ic_rows;
     a.frames = ctx->frames;
     // work buffers are per slot (frame f of this pass uses slot first + f):
     // batches on disjoint slots can be in flight at the same time

@@ -139,6 +139,19 @@ static int resize_tables(Geometry& g, int sw, int sh, int dw, int dh)
     return ORBX_OK;
 }
 
+std::vector<uint32_t> ic_row_table(const Geometry& g)
+{
+    std::vector<uint32_t> t((size_t)kIcTabRows * kIcTabDw, 0u);
+    for (int v = 0; v <= kHalfPatch; v++)
+        for (int i = 0; i < 32; i++) {   // byte i of the row: u = i - 15
+            const int u = i - kHalfPatch;
+            if (std::abs(u) > g.umax[v]) continue;
+            t[(size_t)v * kIcTabDw + i / 4] |= 1u << (8 * (i % 4));
+            t[(size_t)v * kIcTabDw + 8 + i / 4] |= (uint32_t)(u + 16) << (8 * (i % 4));
+        }
+    return t;
+}
+
 int compute_geometry(Geometry& g, int w, int h)
 {
     if (w <= 0 || h <= 0 || w > 4095 || h > 4095) return ORBX_ERR_ARG;

@@ -132,6 +132,13 @@ struct Geometry {
 
 // ORBextractor constructor tables (src/ORBextractor.cc:457-511).
 void init_extractor_tables(Geometry& g, int nfeatures, float scale_factor, int nlevels, int fast_th);
+// k_describe's IC_Angle row table, from g.umax: kIcTabRows rows (|v| = 0 ..
+// kHalfPatch, then one row of zeros for the idle lane) of kIcTabDw dwords.
+// Dwords 0..7 weigh the row's bytes u = -15 .. 16, four to a dword, with 1
+// inside the circle (|u| <= umax[|v|]) and 0 outside; dwords 8..15 with
+// u + 16 inside and 0 outside.
+constexpr int kIcTabRows = 17, kIcTabDw = 16;
+std::vector<uint32_t> ic_row_table(const Geometry& g);
 // Per image size: level sizes, cell grid, resize coefficient tables.
 // Returns ORBX_OK or ORBX_ERR_UNSUPPORTED for sizes the reference cannot
 // handle (empty cell grid, 2x INTER_AREA decimation).
@@ -151,7 +158,7 @@ struct DeviceGeometry {
     CellGeom* cells = nullptr;
     ResizeCol* res_cols = nullptr;
     ResizeRow* res_rows = nullptr;
-    int* umax = nullptr;
+    uint32_t* ic_rows = nullptr;   // ic_row_table(geom): umax as k_describe reads it
 };
 
 struct KernelTimer {
