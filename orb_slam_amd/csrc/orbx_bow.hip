@@ -694,10 +694,8 @@ int queue_bow_slots(orbx_ctx* ctx, int mode, int slot1, const uint8_t* mp1, int 
     if (n == 0) return ORBX_OK;
     ctx_enter(ctx);
     // the slots' feature counts bound the map-point arrays the caller passes
-    std::vector<int32_t> cnt(ctx->slots);
-    ORBX_HIP_CHECK(hipMemcpyAsync(cnt.data(), ctx->out_n, sizeof(int32_t) * ctx->slots, hipMemcpyDeviceToHost,
-                                  ctx->stream));
-    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    std::vector<int32_t> cnt;
+    if (const int rc = read_slot_counts(ctx, cnt)) return rc;
     auto count = [&](int slot) { return std::min<int>(cnt[slot], nf); };
     ArrayStage s(ctx);
     const Region<uint8_t> o_m1 = s.take<uint8_t>(nf);

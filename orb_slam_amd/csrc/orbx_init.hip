@@ -33,6 +33,7 @@
 #include "orbx_init_layout.h"
 #include "orbx_jacobi.h"
 #include "orbx_linalg.h"
+#include "orbx_stage.h"
 
 namespace orbx {
 
@@ -640,21 +641,17 @@ extern "C" int orbx_init_models_batch(orbx_ctx* ctx, int B, orbx_init_query* qs)
     }
     ctx_enter(ctx);
     const InitLayout L = make_layout(Mmax, cap);
-    // one upload: descriptors | keypoints | matches | draws
-    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    const size_t o_desc = 0, o_kp = up16((size_t)B * sizeof(InitPair));
-    const size_t o_m = up16(o_kp + (size_t)n_kp * sizeof(orbx_keypoint));
-    const size_t o_dr = up16(o_m + (size_t)n_m * 4);
-    const size_t o_res = up16(o_dr + (size_t)n_dr * 4);
-    const size_t res_bytes = (size_t)B * L.stride;
-    int r = ensure_scratch(ctx, o_res + res_bytes);
+    // one upload: descriptors | keypoints | matches | draws (each array the queries' end to end)
+    PackedStage st(ctx);
+    const Region<InitPair> descs = st.take<InitPair>(B);
+    const Region<orbx_keypoint> kps = st.take<orbx_keypoint>(n_kp);
+    const Region<int32_t> m12 = st.take<int32_t>(n_m), draws = st.take<int32_t>(n_dr);
+    int r = st.open((size_t)B * L.stride);
     if (r != ORBX_OK) return r;
-    std::vector<uint8_t> blob(o_res, 0);
-    InitPair* descs = reinterpret_cast<InitPair*>(blob.data() + o_desc);
     long long kp = 0, mm = 0, dr = 0;
     for (int b = 0; b < B; b++) {
         const orbx_init_query& q = qs[b];
-        InitPair& d = descs[b];
+        InitPair& d = st.host(descs)[b];
         d.k1_off = kp;
         d.k2_off = kp + q.n1;
         d.m_off = mm;
@@ -664,26 +661,20 @@ extern "C" int orbx_init_models_batch(orbx_ctx* ctx, int B, orbx_init_query* qs)
         d.cnt1 = d.cnt2 = -1;
         d.max_iter = q.max_iter;
         d.sigma = q.sigma;
-        if (q.n1) std::memcpy(blob.data() + o_kp + (size_t)kp * sizeof(orbx_keypoint), q.keys1, (size_t)q.n1 * sizeof(orbx_keypoint));
-        if (q.n2)
-            std::memcpy(blob.data() + o_kp + (size_t)(kp + q.n1) * sizeof(orbx_keypoint), q.keys2,
-                        (size_t)q.n2 * sizeof(orbx_keypoint));
-        if (q.n1) std::memcpy(blob.data() + o_m + (size_t)mm * 4, q.matches12, (size_t)q.n1 * 4);
-        std::memcpy(blob.data() + o_dr + (size_t)dr * 4, q.draws, (size_t)q.max_iter * 32);
+        if (q.n1) std::memcpy(st.host(kps) + kp, q.keys1, (size_t)q.n1 * sizeof(orbx_keypoint));
+        if (q.n2) std::memcpy(st.host(kps) + kp + q.n1, q.keys2, (size_t)q.n2 * sizeof(orbx_keypoint));
+        if (q.n1) std::memcpy(st.host(m12) + mm, q.matches12, (size_t)q.n1 * 4);
+        std::memcpy(st.host(draws) + dr, q.draws, (size_t)q.max_iter * 32);
         kp += q.n1 + q.n2;
         mm += q.n1;
         dr += (long long)q.max_iter * 8;
     }
-    uint8_t* dev = static_cast<uint8_t*>(ctx->scratch);
-    ORBX_HIP_CHECK(hipMemcpyAsync(dev, blob.data(), o_res, hipMemcpyHostToDevice, ctx->stream));
-    r = launch_init(ctx, B, reinterpret_cast<const orbx_keypoint*>(dev + o_kp),
-                    reinterpret_cast<const int32_t*>(dev + o_m), nullptr, reinterpret_cast<const int32_t*>(dev + o_dr),
-                    reinterpret_cast<const InitPair*>(dev + o_desc), dev + o_res, L);
-    if (r != ORBX_OK) return r;
-    std::vector<uint8_t> out(res_bytes);
-    ORBX_HIP_CHECK(hipMemcpyAsync(out.data(), dev + o_res, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    for (int b = 0; b < B; b++) scatter(out.data() + (size_t)b * L.stride, L, qs[b].max_iter, &qs[b]);
+    ResultBlocks res(ctx, st.behind(), B, L.stride);
+    if ((r = st.upload()) != ORBX_OK) return r;
+    if ((r = launch_init(ctx, B, st.dev(kps), st.dev(m12), nullptr, st.dev(draws), st.dev(descs), res.dev, L)) != ORBX_OK)
+        return r;
+    if ((r = res.read()) != ORBX_OK) return r;
+    for (int b = 0; b < B; b++) scatter(res.block(b), L, qs[b].max_iter, &qs[b]);
     return ORBX_OK;
 }
 
@@ -728,19 +719,14 @@ extern "C" int orbx_dev_init_models(orbx_ctx* ctx, int first, int count, int seq
         ctx->init_res_bytes = (size_t)P * L.stride;
     }
     if (P > 0) {
-        const size_t desc_bytes = ((size_t)P * sizeof(InitPair) + 15) & ~(size_t)15;
-        const size_t draw_bytes = (size_t)count * max_iter * 32;
-        r = ensure_scratch(ctx, desc_bytes + draw_bytes);
-        if (r != ORBX_OK) return r;
-        uint8_t* dev = static_cast<uint8_t*>(ctx->scratch);
-        // the sources are pageable host memory the caller (draws) or this
-        // function (descs) frees on return: the copies are waited for, the
-        // kernels are not
-        ORBX_HIP_CHECK(hipMemcpyAsync(dev, descs.data(), (size_t)P * sizeof(InitPair), hipMemcpyHostToDevice, ctx->stream));
-        ORBX_HIP_CHECK(hipMemcpyAsync(dev + desc_bytes, draws, draw_bytes, hipMemcpyHostToDevice, ctx->stream));
+        PackedStage st(ctx);
+        const Region<InitPair> pairs = st.take(P, descs.data());
+        const Region<int32_t> dr = st.take((size_t)count * max_iter * 8, draws);
+        if ((r = st.open(0)) != ORBX_OK || (r = st.upload()) != ORBX_OK) return r;
+        // the blob is freed on return: the copy is waited for, the kernels are not
         ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        r = launch_init(ctx, P, ctx->out_kps, ctx->match12, ctx->out_n, reinterpret_cast<const int32_t*>(dev + desc_bytes),
-                        reinterpret_cast<const InitPair*>(dev), static_cast<uint8_t*>(ctx->init_res), L);
+        r = launch_init(ctx, P, ctx->out_kps, ctx->match12, ctx->out_n, st.dev(dr), st.dev(pairs),
+                        static_cast<uint8_t*>(ctx->init_res), L);
         if (r != ORBX_OK) return r;
     }
     ctx->init_first = first;
@@ -760,13 +746,12 @@ extern "C" int orbx_dev_read_init_models(orbx_ctx* ctx, int slot, orbx_init_quer
     ctx_enter(ctx);
     const int M = ctx->init_iter;
     const InitLayout L = make_layout(M, std::max(ctx->geom.nfeatures, 1));
-    std::vector<uint8_t> blk(L.stride);
-    ORBX_HIP_CHECK(hipMemcpyAsync(blk.data(), static_cast<uint8_t*>(ctx->init_res) + (size_t)p * L.stride, L.stride,
-                                  hipMemcpyDeviceToHost, ctx->stream));
-    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    const int N = reinterpret_cast<const InitHdr*>(blk.data())->n;
+    ResultBlocks blk(ctx, static_cast<uint8_t*>(ctx->init_res) + (size_t)p * L.stride, 1, L.stride);
+    const int r = blk.read();
+    if (r != ORBX_OK) return r;
+    const int N = reinterpret_cast<const InitHdr*>(blk.block(0))->n;
     out->n_matches = N;
     if (out->cap < N) return ORBX_ERR_CAPACITY;
-    scatter(blk.data(), L, M, out);
+    scatter(blk.block(0), L, M, out);
     return ORBX_OK;
 }

@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+#include "orbx_pack.h"
+
 namespace orbx {
 
 constexpr int kInitMaxIter = 1024;
@@ -36,26 +38,21 @@ struct InitLayout {
 inline InitLayout make_layout(int M, int cap)
 {
     InitLayout L;
-    long long o = 0;
-    auto take = [&](long long bytes) {
-        const long long r = o;
-        o += (bytes + 15) & ~15ll;
-        return (int)r;
-    };
-    take(sizeof(InitHdr));
-    L.o_pairs = take((long long)cap * 8);
-    L.o_xy = take((long long)cap * 16);
-    L.o_sets = take((long long)M * 32);
-    L.o_Hn = take((long long)M * 36);
-    L.o_Fn = take((long long)M * 36);
-    L.o_H21 = take((long long)M * 36);
-    L.o_H12 = take((long long)M * 36);
-    L.o_F21 = take((long long)M * 36);
-    L.o_sh = take((long long)M * 4);
-    L.o_sf = take((long long)M * 4);
-    L.o_inh = take(cap);
-    L.o_inf = take(cap);
-    L.stride = o;
+    BlockOffsets o;
+    o.take(sizeof(InitHdr));
+    L.o_pairs = o.take((long long)cap * 8);
+    L.o_xy = o.take((long long)cap * 16);
+    L.o_sets = o.take((long long)M * 32);
+    L.o_Hn = o.take((long long)M * 36);
+    L.o_Fn = o.take((long long)M * 36);
+    L.o_H21 = o.take((long long)M * 36);
+    L.o_H12 = o.take((long long)M * 36);
+    L.o_F21 = o.take((long long)M * 36);
+    L.o_sh = o.take((long long)M * 4);
+    L.o_sf = o.take((long long)M * 4);
+    L.o_inh = o.take(cap);
+    L.o_inf = o.take(cap);
+    L.stride = o.end;
     L.M = M;
     L.cap = cap;
     return L;

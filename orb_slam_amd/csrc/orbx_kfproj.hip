@@ -642,10 +642,8 @@ extern "C" int orbx_dev_fuse_candidates(orbx_ctx* ctx, int n_kf, const int* slot
     if (n_kf == 0) return ORBX_OK;
     ctx_enter(ctx);
     // the slots' keypoint counts size the kernel's LDS grid
-    std::vector<int32_t> cnt(ctx->slots);
-    ORBX_HIP_CHECK(hipMemcpyAsync(cnt.data(), ctx->out_n, sizeof(int32_t) * ctx->slots, hipMemcpyDeviceToHost,
-                                  ctx->stream));
-    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    std::vector<int32_t> cnt;
+    if (const int rc = read_slot_counts(ctx, cnt)) return rc;
     const Geometry& g = ctx->geom;
     ArrayStage s(ctx);
     std::vector<MpRegions> mp(n_kf);
@@ -791,10 +789,8 @@ extern "C" int orbx_dev_search_by_sim3(orbx_ctx* ctx, int slot1, const float* bo
     for (const float* b : {bounds1, bounds2})
         if (b && !(b[1] > b[0] && b[3] > b[2])) return ORBX_ERR_ARG;
     ctx_enter(ctx);
-    std::vector<int32_t> cnt(ctx->slots);
-    ORBX_HIP_CHECK(hipMemcpyAsync(cnt.data(), ctx->out_n, sizeof(int32_t) * ctx->slots, hipMemcpyDeviceToHost,
-                                  ctx->stream));
-    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    std::vector<int32_t> cnt;
+    if (const int rc = read_slot_counts(ctx, cnt)) return rc;
     const Geometry& g = ctx->geom;
     const int N1 = slot_count(ctx, cnt[slot1]), N2 = slot_count(ctx, cnt[slot2]);
     if (mp1->n != N1 || mp2->n != N2 || (N1 && (!valid1 || !prior12)) || (N2 && !valid2)) return ORBX_ERR_ARG;
@@ -972,10 +968,8 @@ extern "C" int orbx_dev_search_by_projection_frame_kf(orbx_ctx* ctx, int f_slot,
         return ORBX_ERR_ARG;
     if (f_bounds && !(f_bounds[1] > f_bounds[0] && f_bounds[3] > f_bounds[2])) return ORBX_ERR_ARG;
     ctx_enter(ctx);
-    std::vector<int32_t> cnt(ctx->slots);
-    ORBX_HIP_CHECK(hipMemcpyAsync(cnt.data(), ctx->out_n, sizeof(int32_t) * ctx->slots, hipMemcpyDeviceToHost,
-                                  ctx->stream));
-    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    std::vector<int32_t> cnt;
+    if (const int rc = read_slot_counts(ctx, cnt)) return rc;
     const int nF = slot_count(ctx, cnt[f_slot]), nK = slot_count(ctx, cnt[kf_slot]);
     if (kf_mps->n != nK) return ORBX_ERR_ARG;   // one map-point entry per keyframe keypoint
     if (cap < nF) return ORBX_ERR_CAPACITY;

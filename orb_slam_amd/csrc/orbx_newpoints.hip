@@ -23,6 +23,7 @@
 #include "orbx_internal.h"
 #include "orbx_jacobi.h"
 #include "orbx_linalg.h"
+#include "orbx_stage.h"
 
 namespace orbx {
 
@@ -193,20 +194,11 @@ __global__ __launch_bounds__(256) void k_triangulate(const TriJob* __restrict__ 
 
 namespace {
 
-inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 // Argument rules of one orbx_kf_geom (before any device work).
 bool valid_geom(const orbx_kf_geom* g)
 {
     return g && g->Rcw && g->tcw && g->Ow && g->cam && g->scale_factors && g->level_sigma2 && g->nlevels >= 2 &&
            g->nlevels <= kMaxLevels;
-}
-
-bool octaves_ok(const orbx_keypoint* k, int n, int nlevels)
-{
-    for (int i = 0; i < n; i++)
-        if (k[i].octave < 0 || k[i].octave >= nlevels) return false;
-    return true;
 }
 
 TriGeom to_dev(const orbx_kf_geom& g)
@@ -233,11 +225,13 @@ struct TriLayout {
 TriLayout tri_layout(int len)
 {
     TriLayout L;
+    BlockOffsets o;
     L.len = len;
-    L.o_xyz = up16((size_t)len);
-    L.o_v4 = L.o_xyz + up16((size_t)len * 12);
-    L.o_n = L.o_v4 + (size_t)len * 16;
-    L.stride = L.o_n + 16;
+    o.take(len);   // status
+    L.o_xyz = o.take((long long)len * 12);
+    L.o_v4 = o.take((long long)len * 16);
+    L.o_n = o.take(16);
+    L.stride = o.end;
     return L;
 }
 
@@ -262,11 +256,11 @@ int launch_triangulate(orbx_ctx* ctx, const TriJob* jobs, int n, int len)
 
 // The result blocks (host copy) into the caller's arrays: status whole, xyz
 // where a point was created, the v4 tap where the solve ran.
-void scatter_results(const uint8_t* res, const TriLayout& L, int n, float* const* xyz, uint8_t* const* status,
+void scatter_results(const ResultBlocks& res, const TriLayout& L, int n, float* const* xyz, uint8_t* const* status,
                      int* n_created, float* const* v4)
 {
     for (int k = 0; k < n; k++) {
-        const uint8_t* blk = res + (size_t)k * L.stride;
+        const uint8_t* blk = res.block(k);
         const float* x = reinterpret_cast<const float*>(blk + L.o_xyz);
         const float* v = reinterpret_cast<const float*>(blk + L.o_v4);
         if (L.len) std::memcpy(status[k], blk, L.len);
@@ -295,7 +289,11 @@ extern "C" int orbx_triangulate_matches(orbx_ctx* ctx, const orbx_keypoint* keys
         return ORBX_ERR_ARG;
     if (n1 > kMaxFeatures) return ORBX_ERR_UNSUPPORTED;
     if (!octaves_ok(keys1, n1, g1->nlevels)) return ORBX_ERR_ARG;
-    size_t n_kp = (size_t)n1;
+    // one upload: jobs | keypoints (KF1, then each KF2) | matches; then the result blocks
+    PackedStage st(ctx);
+    const Region<TriJob> jobs = st.take<TriJob>(n);
+    const Region<orbx_keypoint> kps1 = st.take(n1, keys1);
+    std::vector<Region<orbx_keypoint>> kps2(n);
     for (int k = 0; k < n; k++) {
         if (n2s[k] < 0 || !valid_geom(&g2s[k]) || !matches12[k] || !xyz[k] || !status[k] || (n2s[k] > 0 && !keys2[k]))
             return ORBX_ERR_ARG;
@@ -303,46 +301,32 @@ extern "C" int orbx_triangulate_matches(orbx_ctx* ctx, const orbx_keypoint* keys
         if (!octaves_ok(keys2[k], n2s[k], g2s[k].nlevels)) return ORBX_ERR_ARG;
         for (int i = 0; i < n1; i++)
             if (matches12[k][i] >= n2s[k]) return ORBX_ERR_ARG;   // the reference would index past KF2's keypoints
-        n_kp += (size_t)n2s[k];
+        kps2[k] = st.take(n2s[k], keys2[k]);
     }
+    std::vector<Region<int32_t>> m12(n);
+    for (int k = 0; k < n; k++) m12[k] = st.take(n1, matches12[k]);
     ctx_enter(ctx);
-    // one upload: jobs | keypoints (KF1, then each KF2) | matches; then the result blocks
     const TriLayout L = tri_layout(n1);
-    const size_t o_kp = up16((size_t)n * sizeof(TriJob));
-    const size_t o_m = up16(o_kp + n_kp * sizeof(orbx_keypoint));
-    const size_t o_res = up16(o_m + (size_t)n * n1 * 4);
-    const size_t res_bytes = (size_t)n * L.stride;
-    int r = ensure_scratch(ctx, o_res + res_bytes);
+    int r = st.open((size_t)n * L.stride);
     if (r != ORBX_OK) return r;
-    uint8_t* dev = static_cast<uint8_t*>(ctx->scratch);
-    std::vector<uint8_t> blob(o_res, 0);
-    TriJob* jobs = reinterpret_cast<TriJob*>(blob.data());
-    const orbx_keypoint* dkp = reinterpret_cast<const orbx_keypoint*>(dev + o_kp);
-    std::memcpy(blob.data() + o_kp, keys1, (size_t)n1 * sizeof(orbx_keypoint));
+    ResultBlocks res(ctx, st.behind(), n, L.stride);
     const TriGeom G1 = to_dev(*g1);
-    size_t kp = (size_t)n1;
     for (int k = 0; k < n; k++) {
-        TriJob& j = jobs[k];
-        j.k1 = dkp;
-        j.k2 = dkp + kp;
-        j.m12 = reinterpret_cast<const int32_t*>(dev + o_m) + (size_t)k * n1;
+        TriJob& j = st.host(jobs)[k];
+        j.k1 = st.dev(kps1);
+        j.k2 = st.dev(kps2[k]);
+        j.m12 = st.dev(m12[k]);
         j.mark = nullptr;
         j.n1 = n1;
         j.n2 = n2s[k];
         j.g1 = G1;
         j.g2 = to_dev(g2s[k]);
-        point_job(j, dev + o_res + (size_t)k * L.stride, L);
-        if (n2s[k]) std::memcpy(blob.data() + o_kp + kp * sizeof(orbx_keypoint), keys2[k], (size_t)n2s[k] * sizeof(orbx_keypoint));
-        std::memcpy(blob.data() + o_m + (size_t)k * n1 * 4, matches12[k], (size_t)n1 * 4);
-        kp += (size_t)n2s[k];
+        point_job(j, res.dev + (size_t)k * L.stride, L);
     }
-    ORBX_HIP_CHECK(hipMemcpyAsync(dev, blob.data(), o_res, hipMemcpyHostToDevice, ctx->stream));
-    ORBX_HIP_CHECK(hipMemsetAsync(dev + o_res, 0, res_bytes, ctx->stream));
-    if ((r = launch_triangulate(ctx, reinterpret_cast<const TriJob*>(dev), n, n1)) != ORBX_OK) return r;
-    std::vector<uint8_t> out(res_bytes);
-    ORBX_HIP_CHECK(hipMemcpyAsync(out.data(), dev + o_res, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    scatter_results(out.data(), L, n, xyz, status, n_created, v4);
+    if ((r = st.upload()) != ORBX_OK || (r = res.zero()) != ORBX_OK) return r;
+    if ((r = launch_triangulate(ctx, st.dev(jobs), n, n1)) != ORBX_OK) return r;
+    if ((r = res.read()) != ORBX_OK) return r;
+    scatter_results(res, L, n, xyz, status, n_created, v4);
     return ORBX_OK;
 }
 
@@ -359,12 +343,13 @@ struct NewPointsCall {
     const orbx_kf_geom* g2s;
     BowQueued q;
     TriLayout L{};
-    std::vector<TriJob> jobs;
+    PackedStage st{ctx};   // the jobs, ahead of the result blocks, in the search's extra bytes
+    Region<TriJob> jobs = st.take<TriJob>(n);
     bool prepared = false;
 
-    size_t extra_bytes(int len) const { return up16((size_t)n * sizeof(TriJob)) + (size_t)n * tri_layout(len).stride; }
-    TriJob* dev_jobs() const { return reinterpret_cast<TriJob*>(q.extra); }
-    uint8_t* dev_res() const { return q.extra + up16((size_t)n * sizeof(TriJob)); }
+    size_t extra_bytes(int len) const { return st.total + (size_t)n * tri_layout(len).stride; }
+    TriJob* dev_jobs() const { return st.dev(jobs); }
+    uint8_t* dev_res() const { return st.behind(); }
 
     // jobs uploaded, result blocks zeroed (once q is filled)
     int prepare()
@@ -372,10 +357,10 @@ struct NewPointsCall {
         if (prepared) return ORBX_OK;
         prepared = true;
         L = tri_layout(q.out_len);
-        jobs.assign(n, TriJob{});
+        st.bind(q.extra);
         const TriGeom G1 = to_dev(*g1);
         for (int k = 0; k < n; k++) {
-            TriJob& j = jobs[k];
+            TriJob& j = st.host(jobs)[k];
             j.k1 = q.k1;
             j.k2 = q.k2[k];
             j.m12 = q.out[k];
@@ -386,10 +371,8 @@ struct NewPointsCall {
             j.g2 = to_dev(g2s[k]);
             point_job(j, dev_res() + (size_t)k * L.stride, L);
         }
-        ORBX_HIP_CHECK(hipMemcpyAsync(dev_jobs(), jobs.data(), (size_t)n * sizeof(TriJob), hipMemcpyHostToDevice,
-                                      ctx->stream));
-        ORBX_HIP_CHECK(hipMemsetAsync(dev_res(), 0, (size_t)n * L.stride, ctx->stream));
-        return ORBX_OK;
+        const int r = st.upload();
+        return r != ORBX_OK ? r : ResultBlocks(ctx, dev_res(), n, L.stride).zero();
     }
 
     int after(int k)
@@ -409,10 +392,9 @@ struct NewPointsCall {
             if ((r = launch_triangulate(ctx, dev_jobs(), n, L.len)) != ORBX_OK) return r;
         }
         if ((r = read_bow_queued(ctx, q, q.out_len, matches12, n_matches)) != ORBX_OK) return r;
-        std::vector<uint8_t> out((size_t)n * L.stride);
-        ORBX_HIP_CHECK(hipMemcpyAsync(out.data(), dev_res(), out.size(), hipMemcpyDeviceToHost, ctx->stream));
-        ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        scatter_results(out.data(), L, n, xyz, status, n_created, v4);
+        ResultBlocks res(ctx, dev_res(), n, L.stride);
+        if ((r = res.read()) != ORBX_OK) return r;
+        scatter_results(res, L, n, xyz, status, n_created, v4);
         return ORBX_OK;
     }
 };

@@ -31,14 +31,13 @@
 #include <cfloat>
 #include <cmath>
 #include <cstring>
-#include <memory>
-#include <new>
 #include <vector>
 
 #include "orbx_bow_queue.h"
 #include "orbx_device.h"
 #include "orbx_internal.h"
 #include "orbx_jacobi.h"
+#include "orbx_stage.h"
 
 namespace orbx {
 
@@ -88,31 +87,26 @@ struct PnpLayout {
 inline PnpLayout pnp_layout(int M, int cap)
 {
     PnpLayout L;
-    long long o = 0;
-    auto take = [&](long long bytes) {
-        const long long r = o;
-        o += (bytes + 15) & ~15ll;
-        return r;
-    };
+    BlockOffsets o;
     L.M = M;
     L.cap = cap;
     L.K = std::min(M, cap) + 1;
-    take(sizeof(PnpHdr));
-    L.o_inl = take(cap);
-    L.o_mask = take(cap);
-    L.head = (int)o;   // what a call without taps reads back
-    L.o_kp = take((long long)cap * 4);
-    L.o_p2 = take((long long)cap * 8);
-    L.o_p3 = take((long long)cap * 12);
-    L.o_me = take((long long)cap * 4);
-    L.o_sets = take((long long)M * 16);
-    L.o_rec = take((long long)M * kRec * 8);
-    L.o_cnt = take((long long)M * 4);
-    L.o_recl = take((long long)L.K * 4);
-    L.o_rrec = take((long long)L.K * kRec * 8);
-    L.o_rcnt = take((long long)L.K * 4);
-    L.o_ridx = take((long long)kPnpRefineBlocks * cap * 4);
-    L.stride = o;
+    o.take(sizeof(PnpHdr));
+    L.o_inl = o.take(cap);
+    L.o_mask = o.take(cap);
+    L.head = (int)o.end;   // what a call without taps reads back
+    L.o_kp = o.take((long long)cap * 4);
+    L.o_p2 = o.take((long long)cap * 8);
+    L.o_p3 = o.take((long long)cap * 12);
+    L.o_me = o.take((long long)cap * 4);
+    L.o_sets = o.take((long long)M * 16);
+    L.o_rec = o.take((long long)M * kRec * 8);
+    L.o_cnt = o.take((long long)M * 4);
+    L.o_recl = o.take((long long)L.K * 4);
+    L.o_rrec = o.take((long long)L.K * kRec * 8);
+    L.o_rcnt = o.take((long long)L.K * 4);
+    L.o_ridx = o.take((long long)kPnpRefineBlocks * cap * 4);
+    L.stride = o.end;
     return L;
 }
 
@@ -1158,8 +1152,6 @@ __global__ __launch_bounds__(256) void k_pnp_select(const PnpCand* __restrict__ 
 // ---------------------------------------------------------------------------
 namespace {
 
-inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 int launch_pnp(orbx_ctx* ctx, int P, const PnpCand* cands, uint8_t* res, const PnpLayout& L)
 {
     hipStream_t st = ctx->stream;
@@ -1200,13 +1192,7 @@ void ransac_parameters(int N, double probability, int min_inliers, int max_itera
     if (N < nMinInliers) return;
     float eps = epsilon;
     if (eps < (float)nMinInliers / N) eps = (float)nMinInliers / N;
-    int nIterations;
-    if (nMinInliers == N)
-        nIterations = 1;
-    else {
-        const double v = std::ceil(std::log(1 - probability) / std::log(1 - std::pow((double)eps, 3)));
-        nIterations = !(v < 2147483647.0) ? 2147483647 : (v < 1.0 ? 1 : (int)v);
-    }
+    const int nIterations = nMinInliers == N ? 1 : ransac_iterations(eps, probability);
     *out_its = std::max(1, std::min(nIterations, max_iterations));
 }
 
@@ -1225,6 +1211,8 @@ int check_params(const orbx_pnp_query& q)
     return ORBX_OK;
 }
 
+// Finite and not negative: nothing here converts a multiple of it to int, as
+// orbx_sim3.hip's kernels do.
 bool sigma2_ok(const float* s, int nlevels)
 {
     if (!s) return false;
@@ -1281,21 +1269,11 @@ bool wants_taps(const orbx_pnp_query& q)
            q.record_iter;
 }
 
-// The read-back of P result blocks: whole when a tap is asked for, else the
-// head of each (header and the two masks).  *pitch: the distance of the
-// blocks in `out`.
-int read_results(orbx_ctx* ctx, const uint8_t* res, int P, const PnpLayout& L, bool taps,
-                 std::unique_ptr<uint8_t[]>& out, size_t* pitch)
+// What is read back of a result block: all of it when a tap is asked for,
+// else its head (header and the two masks).
+size_t read_bytes(const PnpLayout& L, int n, const orbx_pnp_query* qs)
 {
-    *pitch = taps ? (size_t)L.stride : (size_t)L.head;
-    out.reset(new (std::nothrow) uint8_t[*pitch * (size_t)P]);
-    if (!out) return ORBX_ERR_NOMEM;
-    if (taps)
-        ORBX_HIP_CHECK(hipMemcpyAsync(out.get(), res, *pitch * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
-    else
-        ORBX_HIP_CHECK(hipMemcpy2DAsync(out.get(), *pitch, res, (size_t)L.stride, *pitch, (size_t)P,
-                                        hipMemcpyDeviceToHost, ctx->stream));
-    return ORBX_OK;
+    return std::any_of(qs, qs + n, wants_taps) ? (size_t)L.stride : (size_t)L.head;
 }
 
 }  // namespace
@@ -1306,10 +1284,19 @@ using namespace orbx;
 extern "C" int orbx_pnp_ransac_batch(orbx_ctx* ctx, int B, orbx_pnp_query* qs)
 {
     if (!ctx || !qs || B < 1) return ORBX_ERR_ARG;
-    // argument rules, before any device work
+    // argument rules, before any device work; what travels is taken as it is checked:
+    // descriptors | per candidate: keypoints, positions, sigma2, flags, mask, draws
+    struct Staged {
+        Region<orbx_keypoint> keys;
+        Region<float> pos, sigma2;
+        Region<uint8_t> valid, mask;
+        Region<int32_t> draws;
+    };
     int Mmax = 1, cap = 1;
     std::vector<int> Ns(B);
-    size_t bytes = up16((size_t)B * sizeof(PnpCand));
+    std::vector<Staged> at(B);
+    PackedStage st(ctx);
+    const Region<PnpCand> cands = st.take<PnpCand>(B);
     for (int b = 0; b < B; b++) {
         const orbx_pnp_query& q = qs[b];
         if (q.n < 0 || (q.n > 0 && (!q.keys || !q.pos || !q.valid)) || !q.cam) return ORBX_ERR_ARG;
@@ -1317,45 +1304,31 @@ extern "C" int orbx_pnp_ransac_batch(orbx_ctx* ctx, int B, orbx_pnp_query* qs)
         if (r != ORBX_OK) return r;
         if (q.nlevels < 1 || q.nlevels > kMaxLevels || !sigma2_ok(q.sigma2, q.nlevels)) return ORBX_ERR_ARG;
         if (q.n > kMaxFeatures) return ORBX_ERR_UNSUPPORTED;
+        if (!octaves_ok(q.keys, q.n, q.nlevels)) return ORBX_ERR_ARG;
         int N = 0;
-        for (int i = 0; i < q.n; i++) {
-            if (q.keys[i].octave < 0 || q.keys[i].octave >= q.nlevels) return ORBX_ERR_ARG;
-            N += q.valid[i] != 0;
-        }
+        for (int i = 0; i < q.n; i++) N += q.valid[i] != 0;
         if (q.cap < q.n) return ORBX_ERR_CAPACITY;
         Ns[b] = N;
         Mmax = std::max(Mmax, q.n_draws);
         cap = std::max(cap, q.n);
-        bytes += up16((size_t)q.n * sizeof(orbx_keypoint)) + up16((size_t)q.n * 12) + 2 * up16(q.n) +
-                 up16((size_t)q.nlevels * 4) + up16((size_t)q.n_draws * 16);
+        at[b] = {st.take(q.n, q.keys), st.take((size_t)q.n * 3, q.pos), st.take(q.nlevels, q.sigma2),
+                 st.take(q.n, q.valid), st.take(q.n, q.best_mask), st.take((size_t)q.n_draws * 4, q.draws)};
     }
     ctx_enter(ctx);
     const PnpLayout L = pnp_layout(Mmax, cap);
-    const size_t o_res = up16(bytes);
-    const size_t res_bytes = (size_t)B * L.stride;
-    int r = ensure_scratch(ctx, o_res + res_bytes);
+    int r = st.open((size_t)B * L.stride);
     if (r != ORBX_OK) return r;
-    uint8_t* dev = static_cast<uint8_t*>(ctx->scratch);
-    // one upload: descriptors | per candidate: keypoints, positions, flags, mask, sigma2, draws
-    std::vector<uint8_t> blob(o_res, 0);
-    PnpCand* cands = reinterpret_cast<PnpCand*>(blob.data());
-    size_t o = up16((size_t)B * sizeof(PnpCand));
-    auto put = [&](const void* src, size_t n) {
-        const size_t at = o;
-        if (n) std::memcpy(blob.data() + at, src, n);
-        o += up16(n);
-        return dev + at;
-    };
     for (int b = 0; b < B; b++) {
         const orbx_pnp_query& q = qs[b];
-        PnpCand& d = cands[b];
-        d.keys = reinterpret_cast<const orbx_keypoint*>(put(q.keys, (size_t)q.n * sizeof(orbx_keypoint)));
+        const Staged& a = at[b];
+        PnpCand& d = st.host(cands)[b];
+        d.keys = st.dev(a.keys);
         d.match = nullptr;
-        d.pos = reinterpret_cast<const float*>(put(q.pos, (size_t)q.n * 12));
-        d.valid = put(q.valid, q.n);
-        d.mask_in = put(q.best_mask, q.n);
-        d.sigma2 = reinterpret_cast<const float*>(put(q.sigma2, (size_t)q.nlevels * 4));
-        d.draws = reinterpret_cast<const int32_t*>(put(q.draws, (size_t)q.n_draws * 16));
+        d.pos = st.dev(a.pos);
+        d.valid = st.dev(a.valid);
+        d.mask_in = st.dev(a.mask);
+        d.sigma2 = st.dev(a.sigma2);
+        d.draws = st.dev(a.draws);
         d.tab_min = d.tab_its = d.n_matches = nullptr;
         d.n = q.n;
         d.n2 = 0;
@@ -1371,18 +1344,11 @@ extern "C" int orbx_pnp_ransac_batch(orbx_ctx* ctx, int B, orbx_pnp_query* qs)
         std::memcpy(d.cam, q.cam, 16);
         std::memcpy(d.Tcw_in, q.best_Tcw, 64);
     }
-    if (o > o_res) return ORBX_ERR_NOMEM;   // the sizes above and the layout here disagree
-    ORBX_HIP_CHECK(hipMemcpyAsync(dev, blob.data(), o_res, hipMemcpyHostToDevice, ctx->stream));
-    ORBX_HIP_CHECK(hipMemsetAsync(dev + o_res, 0, res_bytes, ctx->stream));
-    r = launch_pnp(ctx, B, reinterpret_cast<const PnpCand*>(dev), dev + o_res, L);
-    if (r != ORBX_OK) return r;
-    bool taps = false;
-    for (int b = 0; b < B; b++) taps = taps || wants_taps(qs[b]);
-    std::unique_ptr<uint8_t[]> out;
-    size_t pitch = 0;
-    if ((r = read_results(ctx, dev + o_res, B, L, taps, out, &pitch)) != ORBX_OK) return r;
-    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    for (int b = 0; b < B; b++) scatter(out.get() + (size_t)b * pitch, L, qs[b].n, &qs[b]);
+    ResultBlocks res(ctx, st.behind(), B, L.stride);
+    if ((r = st.upload()) != ORBX_OK || (r = res.zero()) != ORBX_OK) return r;
+    if ((r = launch_pnp(ctx, B, st.dev(cands), res.dev, L)) != ORBX_OK) return r;
+    if ((r = res.read(read_bytes(L, B, qs))) != ORBX_OK) return r;
+    for (int b = 0; b < B; b++) scatter(res.block(b), L, qs[b].n, &qs[b]);
     return ORBX_OK;
 }
 
@@ -1413,47 +1379,42 @@ extern "C" int orbx_dev_pnp_candidates(orbx_ctx* ctx, int slot, int n, const orb
     const PnpLayout L = pnp_layout(Mmax, len);
     // what the solver adds to the search's upload: descriptors | sigma2 | per
     // candidate: positions, the incoming mask, draws, the two tables | result blocks
-    const size_t tab_bytes = up16((size_t)(kMaxFeatures + 1) * 4);
-    const size_t o_sig = up16((size_t)n * sizeof(PnpCand));
-    size_t o = o_sig + up16((size_t)nlevels * 4);
-    std::vector<size_t> o_cand(n);
+    struct Staged {
+        Region<float> pos;
+        Region<uint8_t> mask;
+        Region<int32_t> draws, tab_min, tab_its;
+    };
+    std::vector<Staged> at(n);
+    PackedStage st(ctx);
+    const Region<PnpCand> cands = st.take<PnpCand>(n);
+    const Region<float> sig = st.take(nlevels, sigma2);
     for (int k = 0; k < n; k++) {
         if (KFs[k].n < 0 || KFs[k].n > kMaxFeatures) return ORBX_ERR_UNSUPPORTED;
-        o_cand[k] = o;
-        o += up16((size_t)KFs[k].n * 12) + up16(len) + up16((size_t)out[k].n_draws * 16) + 2 * tab_bytes;
+        at[k] = {st.take((size_t)KFs[k].n * 3, pos[k]), st.take<uint8_t>(len), st.take((size_t)out[k].n_draws * 4, out[k].draws),
+                 st.take<int32_t>(kMaxFeatures + 1), st.take<int32_t>(kMaxFeatures + 1)};
+        st.later(at[k].mask.part(0, nf), out[k].best_mask);   // nf of the len bytes
     }
-    const size_t o_res = (o + 255) & ~(size_t)255;
-    const size_t res_bytes = (size_t)n * L.stride;
+    st.align_end(256);
     BowQueued q;
-    int r = queue_bow_frame(ctx, slot, n, KFs, nnratio, check_ori, matches_f, cap, o_res + res_bytes, &q);
+    int r = queue_bow_frame(ctx, slot, n, KFs, nnratio, check_ori, matches_f, cap, st.total + (size_t)n * L.stride, &q);
     if (r != ORBX_OK) return r;
-    std::vector<uint8_t> blob(o_res, 0);
-    PnpCand* cands = reinterpret_cast<PnpCand*>(blob.data());
-    std::memcpy(blob.data() + o_sig, sigma2, (size_t)nlevels * 4);
+    st.bind(q.extra);
     for (int k = 0; k < n; k++) {
         const orbx_pnp_query& p = out[k];
-        size_t at = o_cand[k];
-        PnpCand& d = cands[k];
-        auto put = [&](const void* src, size_t bytes) {
-            const size_t here = at;
-            if (bytes) std::memcpy(blob.data() + here, src, bytes);
-            at += up16(bytes);
-            return q.extra + here;
-        };
+        const Staged& a = at[k];
+        PnpCand& d = st.host(cands)[k];
         d.keys = q.k1;
         d.match = q.out[k];
         d.valid = q.mp2[k];
-        d.pos = reinterpret_cast<const float*>(put(pos[k], (size_t)KFs[k].n * 12));
-        d.mask_in = put(p.best_mask, (size_t)nf);
-        at = o_cand[k] + up16((size_t)KFs[k].n * 12) + up16(len);
-        d.draws = reinterpret_cast<const int32_t*>(put(p.draws, (size_t)p.n_draws * 16));
-        int32_t* tmin = reinterpret_cast<int32_t*>(blob.data() + at);
-        int32_t* tits = reinterpret_cast<int32_t*>(blob.data() + at + tab_bytes);
+        d.pos = st.dev(a.pos);
+        d.mask_in = st.dev(a.mask);
+        d.draws = st.dev(a.draws);
         for (int N = 0; N <= kMaxFeatures; N++)
-            ransac_parameters(N, p.probability, p.min_inliers, p.max_iterations, p.min_set, p.epsilon, &tmin[N], &tits[N]);
-        d.tab_min = reinterpret_cast<const int32_t*>(q.extra + at);
-        d.tab_its = reinterpret_cast<const int32_t*>(q.extra + at + tab_bytes);
-        d.sigma2 = reinterpret_cast<const float*>(q.extra + o_sig);
+            ransac_parameters(N, p.probability, p.min_inliers, p.max_iterations, p.min_set, p.epsilon,
+                              &st.host(a.tab_min)[N], &st.host(a.tab_its)[N]);
+        d.tab_min = st.dev(a.tab_min);
+        d.tab_its = st.dev(a.tab_its);
+        d.sigma2 = st.dev(sig);
         d.n_matches = q.out_n[k];
         d.n = nf;
         d.n2 = KFs[k].n;
@@ -1468,19 +1429,14 @@ extern "C" int orbx_dev_pnp_candidates(orbx_ctx* ctx, int slot, int n, const orb
         std::memcpy(d.cam, cam, 16);
         std::memcpy(d.Tcw_in, p.best_Tcw, 64);
     }
-    ORBX_HIP_CHECK(hipMemcpyAsync(q.extra, blob.data(), o_res, hipMemcpyHostToDevice, ctx->stream));
-    ORBX_HIP_CHECK(hipMemsetAsync(q.extra + o_res, 0, res_bytes, ctx->stream));
-    if ((r = launch_pnp(ctx, n, reinterpret_cast<const PnpCand*>(q.extra), q.extra + o_res, L)) != ORBX_OK) return r;
+    ResultBlocks res(ctx, st.behind(), n, L.stride);
+    if ((r = st.upload()) != ORBX_OK || (r = res.zero()) != ORBX_OK) return r;
+    if ((r = launch_pnp(ctx, n, st.dev(cands), res.dev, L)) != ORBX_OK) return r;
     if ((r = read_bow_queued(ctx, q, q.out_len, matches_f, n_matches)) != ORBX_OK) return r;
-    bool taps = false;
-    for (int k = 0; k < n; k++) taps = taps || wants_taps(out[k]);
-    std::unique_ptr<uint8_t[]> res;
-    size_t pitch = 0;
-    if ((r = read_results(ctx, q.extra + o_res, n, L, taps, res, &pitch)) != ORBX_OK) return r;
-    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if ((r = res.read(read_bytes(L, n, out))) != ORBX_OK) return r;
     for (int k = 0; k < n; k++) {
         if (n_matches[k] < 0) return ORBX_ERR_UNSUPPORTED;
-        const uint8_t* blk = res.get() + (size_t)k * pitch;
+        const uint8_t* blk = res.block(k);
         discarded[k] = reinterpret_cast<const PnpHdr*>(blk)->discarded;
         scatter(blk, L, nf, &out[k]);
     }

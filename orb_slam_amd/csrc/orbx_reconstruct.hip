@@ -33,6 +33,7 @@
 #include "orbx_internal.h"
 #include "orbx_jacobi.h"
 #include "orbx_linalg.h"
+#include "orbx_stage.h"
 
 namespace orbx {
 
@@ -72,20 +73,15 @@ struct RecLayout {
 static RecLayout rec_layout(int cap)
 {
     RecLayout L;
-    long long o = 0;
-    auto take = [&](long long bytes) {
-        const long long r = o;
-        o += (bytes + 15) & ~15ll;
-        return r;
-    };
-    take(sizeof(RecHdr));
-    L.o_v4 = take((long long)kRecMaxHyp * cap * 16);
-    L.o_cos = take((long long)kRecMaxHyp * cap * 4);
-    L.o_pts = take((long long)kRecMaxHyp * cap * 12);
-    L.o_flag = take((long long)kRecMaxHyp * cap);
-    L.o_p3d = take((long long)cap * 12);
-    L.o_tri = take(cap);
-    L.stride = o;
+    BlockOffsets o;
+    o.take(sizeof(RecHdr));
+    L.o_v4 = o.take((long long)kRecMaxHyp * cap * 16);
+    L.o_cos = o.take((long long)kRecMaxHyp * cap * 4);
+    L.o_pts = o.take((long long)kRecMaxHyp * cap * 12);
+    L.o_flag = o.take((long long)kRecMaxHyp * cap);
+    L.o_p3d = o.take((long long)cap * 12);
+    L.o_tri = o.take(cap);
+    L.stride = o.end;
     L.cap = cap;
     return L;
 }
@@ -664,8 +660,6 @@ __global__ __launch_bounds__(256) void k_rec_select(const RecPair* __restrict__ 
 // ---------------------------------------------------------------------------
 namespace {
 
-inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 int launch_reconstruct(orbx_ctx* ctx, int P, const RecPair* descs, uint8_t* res, const RecLayout& L, float rh_threshold)
 {
     if (P <= 0) return ORBX_OK;
@@ -741,24 +735,21 @@ extern "C" int orbx_init_reconstruct_batch(orbx_ctx* ctx, int B, orbx_reconstruc
     }
     ctx_enter(ctx);
     const RecLayout L = rec_layout(cap);
-    // one upload: descriptors | (u1, v1, u2, v2) | (i1, i2) | inliers
-    const size_t o_xy = up16((size_t)B * sizeof(RecPair));
-    const size_t o_pairs = up16(o_xy + n_m * 16);
-    const size_t o_inl = up16(o_pairs + n_m * 8);
-    const size_t o_res = up16(o_inl + n_m);
-    const size_t res_bytes = (size_t)B * L.stride;
-    int r = ensure_scratch(ctx, o_res + res_bytes);
+    // one upload: descriptors | (u1, v1, u2, v2) | (i1, i2) | inliers (each array the queries' end to end)
+    PackedStage st(ctx);
+    const Region<RecPair> descs = st.take<RecPair>(B);
+    const Region<float4> xys = st.take<float4>(n_m);
+    const Region<int2> prs = st.take<int2>(n_m);
+    const Region<uint8_t> inl = st.take<uint8_t>(n_m);
+    int r = st.open((size_t)B * L.stride);
     if (r != ORBX_OK) return r;
-    uint8_t* dev = static_cast<uint8_t*>(ctx->scratch);
-    std::vector<uint8_t> blob(o_res, 0);
-    RecPair* descs = reinterpret_cast<RecPair*>(blob.data());
     size_t mm = 0;
     for (int b = 0; b < B; b++) {
         const orbx_reconstruct_query& q = qs[b];
-        RecPair& d = descs[b];
-        d.xy = reinterpret_cast<const float4*>(dev + o_xy) + mm;
-        d.pairs = reinterpret_cast<const int2*>(dev + o_pairs) + mm;
-        d.inl_h = d.inl_f = dev + o_inl + mm;
+        RecPair& d = st.host(descs)[b];
+        d.xy = st.dev(xys) + mm;
+        d.pairs = st.dev(prs) + mm;
+        d.inl_h = d.inl_f = st.dev(inl) + mm;
         d.init = nullptr;
         d.n1_ptr = nullptr;
         d.N = Ns[b];
@@ -770,8 +761,8 @@ extern "C" int orbx_init_reconstruct_batch(orbx_ctx* ctx, int B, orbx_reconstruc
         d.sigma = q.sigma;
         d.min_parallax = q.min_parallax;
         // mvMatches12 in i1 order (:54-63)
-        float* xy = reinterpret_cast<float*>(blob.data() + o_xy) + 4 * mm;
-        int32_t* pr = reinterpret_cast<int32_t*>(blob.data() + o_pairs) + 2 * mm;
+        float* xy = reinterpret_cast<float*>(st.host(xys) + mm);
+        int32_t* pr = reinterpret_cast<int32_t*>(st.host(prs) + mm);
         int k = 0;
         for (int i = 0; i < q.n1; i++) {
             const int j = q.matches12[i];
@@ -784,16 +775,14 @@ extern "C" int orbx_init_reconstruct_batch(orbx_ctx* ctx, int B, orbx_reconstruc
             pr[2 * k + 1] = j;
             k++;
         }
-        if (Ns[b]) std::memcpy(blob.data() + o_inl + mm, q.inliers, (size_t)Ns[b]);
+        if (Ns[b]) std::memcpy(st.host(inl) + mm, q.inliers, (size_t)Ns[b]);
         mm += (size_t)Ns[b];
     }
-    ORBX_HIP_CHECK(hipMemcpyAsync(dev, blob.data(), o_res, hipMemcpyHostToDevice, ctx->stream));
-    r = launch_reconstruct(ctx, B, reinterpret_cast<const RecPair*>(dev), dev + o_res, L, 0.f);
-    if (r != ORBX_OK) return r;
-    std::vector<uint8_t> out(res_bytes);
-    ORBX_HIP_CHECK(hipMemcpyAsync(out.data(), dev + o_res, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    for (int b = 0; b < B; b++) scatter(out.data() + (size_t)b * L.stride, L, &qs[b]);
+    ResultBlocks res(ctx, st.behind(), B, L.stride);
+    if ((r = st.upload()) != ORBX_OK) return r;
+    if ((r = launch_reconstruct(ctx, B, st.dev(descs), res.dev, L, 0.f)) != ORBX_OK) return r;
+    if ((r = res.read()) != ORBX_OK) return r;
+    for (int b = 0; b < B; b++) scatter(res.block(b), L, &qs[b]);
     return ORBX_OK;
 }
 
@@ -842,14 +831,13 @@ extern "C" int orbx_dev_init_reconstruct(orbx_ctx* ctx, int first, int count, in
         ctx->rec_res_bytes = (size_t)P * L.stride;
     }
     if (P > 0) {
-        int r = ensure_scratch(ctx, up16((size_t)P * sizeof(RecPair)));
-        if (r != ORBX_OK) return r;
-        // descs is freed on return: the copy is waited for, the kernels are not
-        ORBX_HIP_CHECK(hipMemcpyAsync(ctx->scratch, descs.data(), (size_t)P * sizeof(RecPair), hipMemcpyHostToDevice,
-                                      ctx->stream));
+        PackedStage st(ctx);
+        const Region<RecPair> pairs = st.take(P, descs.data());
+        int r;
+        if ((r = st.open(0)) != ORBX_OK || (r = st.upload()) != ORBX_OK) return r;
+        // the blob is freed on return: the copy is waited for, the kernels are not
         ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        r = launch_reconstruct(ctx, P, static_cast<const RecPair*>(ctx->scratch), static_cast<uint8_t*>(ctx->rec_res), L,
-                               rh_threshold);
+        r = launch_reconstruct(ctx, P, st.dev(pairs), static_cast<uint8_t*>(ctx->rec_res), L, rh_threshold);
         if (r != ORBX_OK) return r;
     }
     ctx->rec_first = first;
@@ -866,14 +854,13 @@ extern "C" int orbx_dev_read_init_reconstruct(orbx_ctx* ctx, int slot, orbx_reco
     if (p < 0) return ORBX_ERR_ARG;   // a sequence start has no pair
     ctx_enter(ctx);
     const RecLayout L = rec_layout(ctx->rec_cap);
-    std::vector<uint8_t> blk(L.stride);
-    ORBX_HIP_CHECK(hipMemcpyAsync(blk.data(), static_cast<uint8_t*>(ctx->rec_res) + (size_t)p * L.stride, L.stride,
-                                  hipMemcpyDeviceToHost, ctx->stream));
-    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    const RecHdr* h = reinterpret_cast<const RecHdr*>(blk.data());
+    ResultBlocks blk(ctx, static_cast<uint8_t*>(ctx->rec_res) + (size_t)p * L.stride, 1, L.stride);
+    const int r = blk.read();
+    if (r != ORBX_OK) return r;
+    const RecHdr* h = reinterpret_cast<const RecHdr*>(blk.block(0));
     if (model) *model = h->model;
     if (h->n1 > 0 && (!out->p3d || !out->triangulated)) return ORBX_ERR_ARG;
     if (out->cap < h->n1) return ORBX_ERR_CAPACITY;
-    scatter(blk.data(), L, out);
+    scatter(blk.block(0), L, out);
     return ORBX_OK;
 }

@@ -32,6 +32,7 @@
 #include "orbx_device.h"
 #include "orbx_internal.h"
 #include "orbx_jacobi.h"
+#include "orbx_stage.h"
 
 namespace orbx {
 
@@ -80,29 +81,24 @@ struct Sim3Layout {
 inline Sim3Layout sim3_layout(int M, int cap)
 {
     Sim3Layout L;
-    long long o = 0;
-    auto take = [&](long long bytes) {
-        const long long r = o;
-        o += (bytes + 15) & ~15ll;
-        return (int)r;
-    };
-    take(sizeof(Sim3Hdr));
-    L.o_idx = take((long long)cap * 4);
-    L.o_x1 = take((long long)cap * 12);
-    L.o_x2 = take((long long)cap * 12);
-    L.o_p1 = take((long long)cap * 8);
-    L.o_p2 = take((long long)cap * 8);
-    L.o_l1 = take((long long)cap * 4);
-    L.o_l2 = take((long long)cap * 4);
-    L.o_sets = take((long long)M * 12);
-    L.o_q = take((long long)M * 16);
-    L.o_R = take((long long)M * 36);
-    L.o_s = take((long long)M * 4);
-    L.o_T12 = take((long long)M * 64);
-    L.o_T21 = take((long long)M * 64);
-    L.o_cnt = take((long long)M * 4);
-    L.o_inl = take(cap);
-    L.stride = o;
+    BlockOffsets o;
+    o.take(sizeof(Sim3Hdr));
+    L.o_idx = o.take((long long)cap * 4);
+    L.o_x1 = o.take((long long)cap * 12);
+    L.o_x2 = o.take((long long)cap * 12);
+    L.o_p1 = o.take((long long)cap * 8);
+    L.o_p2 = o.take((long long)cap * 8);
+    L.o_l1 = o.take((long long)cap * 4);
+    L.o_l2 = o.take((long long)cap * 4);
+    L.o_sets = o.take((long long)M * 12);
+    L.o_q = o.take((long long)M * 16);
+    L.o_R = o.take((long long)M * 36);
+    L.o_s = o.take((long long)M * 4);
+    L.o_T12 = o.take((long long)M * 64);
+    L.o_T21 = o.take((long long)M * 64);
+    L.o_cnt = o.take((long long)M * 4);
+    L.o_inl = o.take(cap);
+    L.stride = o.end;
     L.M = M;
     L.cap = cap;
     return L;
@@ -631,8 +627,6 @@ __global__ __launch_bounds__(1024) void k_sim3_check(const Sim3Pair* __restrict_
 // ---------------------------------------------------------------------------
 namespace {
 
-inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 int launch_sim3(orbx_ctx* ctx, int P, const Sim3Pair* descs, uint8_t* res, const Sim3Layout& L)
 {
     hipStream_t st = ctx->stream;
@@ -660,17 +654,11 @@ int launch_sim3(orbx_ctx* ctx, int P, const Sim3Pair* descs, uint8_t* res, const
 int ransac_max_its(int N, int min_inliers, double probability, int max_iterations)
 {
     if (N < min_inliers) return 0;
-    int nIterations;
-    if (min_inliers == N)
-        nIterations = 1;
-    else {
-        const float epsilon = (float)min_inliers / N;
-        const double v = std::ceil(std::log(1 - probability) / std::log(1 - std::pow((double)epsilon, 3)));
-        nIterations = !(v < 2147483647.0) ? 2147483647 : (v < 1.0 ? 1 : (int)v);
-    }
+    const int nIterations = min_inliers == N ? 1 : ransac_iterations((float)min_inliers / N, probability);
     return std::max(1, std::min(nIterations, max_iterations));
 }
 
+// Stricter than orbx_pnp.hip's: the kernels convert 9.210 * sigma2 to int.
 bool sigma2_ok(const float* s, int nlevels)
 {
     if (!s) return false;
@@ -743,10 +731,19 @@ using namespace orbx;
 extern "C" int orbx_sim3_ransac_batch(orbx_ctx* ctx, int B, orbx_sim3_query* qs)
 {
     if (!ctx || !qs || B < 1) return ORBX_ERR_ARG;
-    // argument rules, before any device work
+    // argument rules, before any device work; what travels is taken as it is checked:
+    // descriptors | per pair: keypoints, matches, idx1, draws, positions, sigma2, flags
+    struct Staged {
+        Region<orbx_keypoint> k1, k2;
+        Region<int32_t> m12, idx1, draws;
+        Region<float> pos1, pos2, sigma2_1, sigma2_2;
+        Region<uint8_t> valid1, valid2;
+    };
     int Mmax = 0, cap = 1;
     std::vector<int> Ns(B);
-    size_t bytes = up16((size_t)B * sizeof(Sim3Pair));
+    std::vector<Staged> at(B);
+    PackedStage st(ctx);
+    const Region<Sim3Pair> descs = st.take<Sim3Pair>(B);
     for (int b = 0; b < B; b++) {
         const orbx_sim3_query& q = qs[b];
         if (q.n1 < 0 || q.n2 < 0 || (q.n1 > 0 && (!q.keys1 || !q.matches12 || !q.pos1 || !q.valid1 || !q.inliers)) ||
@@ -758,10 +755,7 @@ extern "C" int orbx_sim3_ransac_batch(orbx_ctx* ctx, int B, orbx_sim3_query* qs)
         if (q.nlevels < 1 || q.nlevels > kMaxLevels || !sigma2_ok(q.sigma2_1, q.nlevels) || !sigma2_ok(q.sigma2_2, q.nlevels))
             return ORBX_ERR_ARG;
         if (q.n1 > kMaxFeatures || q.n2 > kMaxFeatures) return ORBX_ERR_UNSUPPORTED;
-        for (int i = 0; i < q.n1; i++)
-            if (q.keys1[i].octave < 0 || q.keys1[i].octave >= q.nlevels) return ORBX_ERR_ARG;
-        for (int i = 0; i < q.n2; i++)
-            if (q.keys2[i].octave < 0 || q.keys2[i].octave >= q.nlevels) return ORBX_ERR_ARG;
+        if (!octaves_ok(q.keys1, q.n1, q.nlevels) || !octaves_ok(q.keys2, q.n2, q.nlevels)) return ORBX_ERR_ARG;
         int N = 0;
         for (int i = 0; i < q.n1; i++) {
             const int i2 = q.matches12[i];
@@ -774,48 +768,34 @@ extern "C" int orbx_sim3_ransac_batch(orbx_ctx* ctx, int B, orbx_sim3_query* qs)
         Ns[b] = N;
         Mmax = std::max(Mmax, q.n_iter);
         cap = std::max(cap, q.n1);
-        bytes += up16((size_t)q.n1 * sizeof(orbx_keypoint)) + up16((size_t)q.n2 * sizeof(orbx_keypoint)) +
-                 2 * up16((size_t)q.n1 * 4) +
-                 up16((size_t)q.n1 * 12) + up16((size_t)q.n2 * 12) + up16(q.n1) + up16(q.n2) +
-                 2 * up16((size_t)q.nlevels * 4) + up16((size_t)q.n_iter * 12);
+        at[b] = {st.take(q.n1, q.keys1), st.take(q.n2, q.keys2), st.take(q.n1, q.matches12),
+                 st.take(q.idx1 ? q.n1 : 0, q.idx1), st.take((size_t)q.n_iter * 3, q.draws),
+                 st.take((size_t)q.n1 * 3, q.pos1), st.take((size_t)q.n2 * 3, q.pos2), st.take(q.nlevels, q.sigma2_1),
+                 st.take(q.nlevels, q.sigma2_2), st.take<uint8_t>(q.n1), st.take<uint8_t>(q.n2)};
     }
     ctx_enter(ctx);
     const Sim3Layout L = sim3_layout(Mmax, cap);
-    const size_t o_res = up16(bytes);
-    const size_t res_bytes = (size_t)B * L.stride;
-    int r = ensure_scratch(ctx, o_res + res_bytes);
+    int r = st.open((size_t)B * L.stride);
     if (r != ORBX_OK) return r;
-    uint8_t* dev = static_cast<uint8_t*>(ctx->scratch);
-    // one upload: descriptors | per pair: keypoints, matches, idx1, positions, flags, sigma2, draws
-    std::vector<uint8_t> blob(o_res, 0);
-    Sim3Pair* descs = reinterpret_cast<Sim3Pair*>(blob.data());
-    size_t o = up16((size_t)B * sizeof(Sim3Pair));
-    auto put = [&](const void* src, size_t n) {
-        const size_t at = o;
-        if (n) std::memcpy(blob.data() + at, src, n);
-        o += up16(n);
-        return dev + at;
-    };
-    auto flags = [&](const uint8_t* src, int n) {   // any non-zero flag is a good map point
-        const size_t at = o;
-        for (int i = 0; i < n; i++) blob[at + i] = src[i] ? 1 : 0;
-        o += up16(n);
-        return dev + at;
+    auto flags = [&](Region<uint8_t> to, const uint8_t* src) {   // any non-zero flag is a good map point
+        for (size_t i = 0; i < to.count; i++) st.host(to)[i] = src[i] ? 1 : 0;
+        return st.dev(to);
     };
     for (int b = 0; b < B; b++) {
         const orbx_sim3_query& q = qs[b];
-        Sim3Pair& d = descs[b];
-        d.k1 = reinterpret_cast<const orbx_keypoint*>(put(q.keys1, (size_t)q.n1 * sizeof(orbx_keypoint)));
-        d.k2 = reinterpret_cast<const orbx_keypoint*>(put(q.keys2, (size_t)q.n2 * sizeof(orbx_keypoint)));
-        d.m12 = reinterpret_cast<const int32_t*>(put(q.matches12, (size_t)q.n1 * 4));
-        d.idx1 = q.idx1 ? reinterpret_cast<const int32_t*>(put(q.idx1, (size_t)q.n1 * 4)) : nullptr;
-        d.pos1 = reinterpret_cast<const float*>(put(q.pos1, (size_t)q.n1 * 12));
-        d.pos2 = reinterpret_cast<const float*>(put(q.pos2, (size_t)q.n2 * 12));
-        d.valid1 = flags(q.valid1, q.n1);
-        d.valid2 = flags(q.valid2, q.n2);
-        d.sigma2_1 = reinterpret_cast<const float*>(put(q.sigma2_1, (size_t)q.nlevels * 4));
-        d.sigma2_2 = reinterpret_cast<const float*>(put(q.sigma2_2, (size_t)q.nlevels * 4));
-        d.draws = reinterpret_cast<const int32_t*>(put(q.draws, (size_t)q.n_iter * 12));
+        const Staged& a = at[b];
+        Sim3Pair& d = st.host(descs)[b];
+        d.k1 = st.dev(a.k1);
+        d.k2 = st.dev(a.k2);
+        d.m12 = st.dev(a.m12);
+        d.idx1 = q.idx1 ? st.dev(a.idx1) : nullptr;
+        d.pos1 = st.dev(a.pos1);
+        d.pos2 = st.dev(a.pos2);
+        d.valid1 = flags(a.valid1, q.valid1);
+        d.valid2 = flags(a.valid2, q.valid2);
+        d.sigma2_1 = st.dev(a.sigma2_1);
+        d.sigma2_2 = st.dev(a.sigma2_2);
+        d.draws = st.dev(a.draws);
         d.its_table = nullptr;
         d.n_matches = nullptr;
         d.n1 = q.n1;
@@ -832,15 +812,11 @@ extern "C" int orbx_sim3_ransac_batch(orbx_ctx* ctx, int B, orbx_sim3_query* qs)
         std::memcpy(d.cam1, q.cam1, 16);
         std::memcpy(d.cam2, q.cam2, 16);
     }
-    if (o > o_res) return ORBX_ERR_NOMEM;   // the sizes above and the layout here disagree
-    ORBX_HIP_CHECK(hipMemcpyAsync(dev, blob.data(), o_res, hipMemcpyHostToDevice, ctx->stream));
-    ORBX_HIP_CHECK(hipMemsetAsync(dev + o_res, 0, res_bytes, ctx->stream));
-    r = launch_sim3(ctx, B, reinterpret_cast<const Sim3Pair*>(dev), dev + o_res, L);
-    if (r != ORBX_OK) return r;
-    std::vector<uint8_t> out(res_bytes);
-    ORBX_HIP_CHECK(hipMemcpyAsync(out.data(), dev + o_res, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    for (int b = 0; b < B; b++) scatter(out.data() + (size_t)b * L.stride, L, qs[b].n1, qs[b].n_iter, &qs[b]);
+    ResultBlocks res(ctx, st.behind(), B, L.stride);
+    if ((r = st.upload()) != ORBX_OK || (r = res.zero()) != ORBX_OK) return r;
+    if ((r = launch_sim3(ctx, B, st.dev(descs), res.dev, L)) != ORBX_OK) return r;
+    if ((r = res.read()) != ORBX_OK) return r;
+    for (int b = 0; b < B; b++) scatter(res.block(b), L, qs[b].n1, qs[b].n_iter, &qs[b]);
     return ORBX_OK;
 }
 
@@ -874,45 +850,46 @@ extern "C" int orbx_dev_sim3_candidates(orbx_ctx* ctx, int slot1, const orbx_sim
     const Sim3Layout L = sim3_layout(n_iter, len);
     // what the solver adds to the search's upload: descriptors | its table |
     // KF1: positions, sigma2 | per candidate: positions, sigma2, draws | result blocks
-    const size_t o_tab = up16((size_t)n * sizeof(Sim3Pair));
-    const size_t o_kf1 = o_tab + up16((size_t)(kMaxFeatures + 1) * 4);
-    const size_t kf_bytes = up16((size_t)len * 12) + up16((size_t)nl * 4);
-    const size_t cand_bytes = kf_bytes + up16((size_t)n_iter * 12);
-    const size_t o_cand = o_kf1 + kf_bytes;
-    const size_t o_res = (o_cand + (size_t)n * cand_bytes + 255) & ~(size_t)255;
-    const size_t res_bytes = (size_t)n * L.stride;
+    struct Kf {
+        Region<float> pos, sigma2;
+    };
+    PackedStage st(ctx);
+    auto take_kf = [&](const orbx_sim3_kf& k) { return Kf{st.take<float>((size_t)len * 3), st.take(nl, k.sigma2)}; };
+    const Region<Sim3Pair> descs = st.take<Sim3Pair>(n);
+    const Region<int32_t> table = st.take<int32_t>(kMaxFeatures + 1);
+    const Kf at1 = take_kf(*kf1);
+    std::vector<Kf> at2(n);
+    std::vector<Region<int32_t>> at_draws(n);
     std::vector<const uint8_t*> mp2s(n);
-    for (int k = 0; k < n; k++) mp2s[k] = kf2s[k].mp;
+    for (int k = 0; k < n; k++) {
+        at2[k] = take_kf(kf2s[k]);
+        at_draws[k] = st.take((size_t)n_iter * 3, draws + (size_t)k * n_iter * 3);
+        mp2s[k] = kf2s[k].mp;
+    }
+    st.align_end(256);
     BowQueued q;
     r = queue_bow_slots(ctx, 1, slot1, kf1->mp, n, slots2, mp2s.data(), nnratio, check_ori, nullptr, nullptr, 0, cap,
-                            o_res + res_bytes, nullptr, &q);
+                        st.total + (size_t)n * L.stride, nullptr, &q);
     if (r != ORBX_OK) return r;
-    std::vector<uint8_t> blob(o_res, 0);
-    Sim3Pair* descs = reinterpret_cast<Sim3Pair*>(blob.data());
-    int32_t* table = reinterpret_cast<int32_t*>(blob.data() + o_tab);
-    for (int N = 0; N <= kMaxFeatures; N++) table[N] = ransac_max_its(N, min_inliers, probability, max_iterations);
-    auto put_kf = [&](size_t at, const orbx_sim3_kf& k, int count) {
-        std::memcpy(blob.data() + at, k.pos, (size_t)count * 12);
-        std::memcpy(blob.data() + at + up16((size_t)len * 12), k.sigma2, (size_t)nl * 4);
-    };
-    put_kf(o_kf1, *kf1, q.n1);
+    // the search knows the slots' keypoint counts: that many positions of each keyframe
+    st.later(at1.pos.part(0, (size_t)q.n1 * 3), kf1->pos);
+    for (int k = 0; k < n; k++) st.later(at2[k].pos.part(0, (size_t)q.n2[k] * 3), kf2s[k].pos);
+    st.bind(q.extra);
+    for (int N = 0; N <= kMaxFeatures; N++) st.host(table)[N] = ransac_max_its(N, min_inliers, probability, max_iterations);
     for (int k = 0; k < n; k++) {
-        const size_t at = o_cand + (size_t)k * cand_bytes;
-        put_kf(at, kf2s[k], q.n2[k]);
-        std::memcpy(blob.data() + at + kf_bytes, draws + (size_t)k * n_iter * 3, (size_t)n_iter * 12);
-        Sim3Pair& d = descs[k];
+        Sim3Pair& d = st.host(descs)[k];
         d.k1 = q.k1;
         d.k2 = q.k2[k];
         d.m12 = q.out[k];
         d.idx1 = nullptr;
-        d.pos1 = reinterpret_cast<const float*>(q.extra + o_kf1);
-        d.pos2 = reinterpret_cast<const float*>(q.extra + at);
+        d.pos1 = st.dev(at1.pos);
+        d.pos2 = st.dev(at2[k].pos);
         d.valid1 = q.mp1;
         d.valid2 = q.mp2[k];
-        d.sigma2_1 = reinterpret_cast<const float*>(q.extra + o_kf1 + up16((size_t)len * 12));
-        d.sigma2_2 = reinterpret_cast<const float*>(q.extra + at + up16((size_t)len * 12));
-        d.draws = reinterpret_cast<const int32_t*>(q.extra + at + kf_bytes);
-        d.its_table = reinterpret_cast<const int32_t*>(q.extra + o_tab);
+        d.sigma2_1 = st.dev(at1.sigma2);
+        d.sigma2_2 = st.dev(at2[k].sigma2);
+        d.draws = st.dev(at_draws[k]);
+        d.its_table = st.dev(table);
         d.n_matches = q.out_n[k];
         d.n1 = q.n1;
         d.n2 = q.n2[k];
@@ -928,16 +905,14 @@ extern "C" int orbx_dev_sim3_candidates(orbx_ctx* ctx, int slot1, const orbx_sim
         std::memcpy(d.cam1, kf1->cam, 16);
         std::memcpy(d.cam2, kf2s[k].cam, 16);
     }
-    ORBX_HIP_CHECK(hipMemcpyAsync(q.extra, blob.data(), o_res, hipMemcpyHostToDevice, ctx->stream));
-    ORBX_HIP_CHECK(hipMemsetAsync(q.extra + o_res, 0, res_bytes, ctx->stream));
-    if ((r = launch_sim3(ctx, n, reinterpret_cast<const Sim3Pair*>(q.extra), q.extra + o_res, L)) != ORBX_OK) return r;
+    ResultBlocks res(ctx, st.behind(), n, L.stride);
+    if ((r = st.upload()) != ORBX_OK || (r = res.zero()) != ORBX_OK) return r;
+    if ((r = launch_sim3(ctx, n, st.dev(descs), res.dev, L)) != ORBX_OK) return r;
     if ((r = read_bow_queued(ctx, q, q.out_len, matches12, n_matches)) != ORBX_OK) return r;
-    std::vector<uint8_t> res(res_bytes);
-    ORBX_HIP_CHECK(hipMemcpyAsync(res.data(), q.extra + o_res, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if ((r = res.read()) != ORBX_OK) return r;
     for (int k = 0; k < n; k++) {
         if (n_matches[k] < 0) return ORBX_ERR_UNSUPPORTED;
-        const uint8_t* blk = res.data() + (size_t)k * L.stride;
+        const uint8_t* blk = res.block(k);
         discarded[k] = reinterpret_cast<const Sim3Hdr*>(blk)->discarded;
         scatter(blk, L, q.n1, n_iter, &out[k]);
     }

@@ -51,6 +51,7 @@
 #include "orbx_internal.h"
 #include "orbx_match_common.h"
 #include "orbx_se3.h"
+#include "orbx_stage.h"
 
 namespace orbx {
 
@@ -103,23 +104,18 @@ struct Sim3OptLayout {
 inline Sim3OptLayout sim3opt_layout(int cap, bool taps)
 {
     Sim3OptLayout L;
-    long long o = 0;
-    auto take = [&](long long bytes) {
-        const long long r = o;
-        o += (bytes + 15) & ~15ll;
-        return (int)r;
-    };
-    take(sizeof(Sim3OptHdr));
-    L.o_x1 = take((long long)cap * 12);
-    L.o_x2 = take((long long)cap * 12);
-    L.o_obs = take((long long)cap * 16);
-    L.o_w = take((long long)cap * 8);
-    L.o_flag = take(cap);
-    L.o_it = take(taps ? (long long)kSoLm * sizeof(Sim3OptIter) : 0);
-    L.o_err = take(taps ? (long long)cap * 32 : 0);
-    L.o_J = take(taps ? (long long)cap * 224 : 0);
-    L.o_chi = take(taps ? (long long)cap * 32 : 0);
-    L.stride = o;
+    BlockOffsets o;
+    o.take(sizeof(Sim3OptHdr));
+    L.o_x1 = o.take((long long)cap * 12);
+    L.o_x2 = o.take((long long)cap * 12);
+    L.o_obs = o.take((long long)cap * 16);
+    L.o_w = o.take((long long)cap * 8);
+    L.o_flag = o.take(cap);
+    L.o_it = o.take(taps ? (long long)kSoLm * sizeof(Sim3OptIter) : 0);
+    L.o_err = o.take(taps ? (long long)cap * 32 : 0);
+    L.o_J = o.take(taps ? (long long)cap * 224 : 0);
+    L.o_chi = o.take(taps ? (long long)cap * 32 : 0);
+    L.stride = o.end;
     L.cap = cap;
     return L;
 }
@@ -750,8 +746,6 @@ using namespace orbx;
 
 namespace {
 
-inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 bool finite_all(const float* v, int n)
 {
     for (int i = 0; i < n; i++)
@@ -883,15 +877,44 @@ void fill_prob(Sim3OptProb& d, const orbx_sim3_opt_query& q, int n, int nlevels,
     d.delta = (double)std::sqrt(q.th2);   // const float deltaHuber = sqrt(th2) (:840)
 }
 
-int launch_sim3opt(orbx_ctx* ctx, int P, const Sim3OptProb* descs, uint8_t* res, const Sim3OptLayout& L)
+// Where one candidate's arrays lie in the call's packed inputs.
+struct Sim3OptStaged {
+    Region<orbx_keypoint> k1, k2;   // host form only: the slot form reads the context's keypoints
+    Region<int32_t> ci, cj;
+    Region<float> pos1, pos2, isig1, sig2;   // taken in this order
+};
+
+void point_prob(Sim3OptProb& d, const PackedStage& st, const Sim3OptStaged& a)
 {
+    d.ci = st.dev(a.ci);
+    d.cj = st.dev(a.cj);
+    d.pos1 = st.dev(a.pos1);
+    d.pos2 = st.dev(a.pos2);
+    d.isig1 = st.dev(a.isig1);
+    d.sig2 = st.dev(a.sig2);
+}
+
+// Upload, launch (a lone candidate gets the wide workgroup), read back and scatter.
+int run_sim3opt(PackedStage& st, Region<Sim3OptProb> descs, const Sim3OptLayout& L,
+                const std::vector<std::vector<int32_t>>& ci, bool taps, orbx_sim3_opt_query* qs)
+{
+    orbx_ctx* ctx = st.ctx;
+    const int P = (int)descs.count;
+    int r = st.upload();
+    if (r != ORBX_OK) return r;
+    ResultBlocks res(ctx, st.behind(), P, L.stride);
     timer_begin(ctx, "sim3opt");
     if (P == 1)
-        hipLaunchKernelGGL(k_sim3_opt<kSoWide>, dim3(1), dim3(64 * kSoWide), 0, ctx->stream, descs, res, L);
+        hipLaunchKernelGGL(k_sim3_opt<kSoWide>, dim3(1), dim3(64 * kSoWide), 0, ctx->stream, st.dev(descs), res.dev, L);
     else
-        hipLaunchKernelGGL(k_sim3_opt<1>, dim3(P), dim3(64), 0, ctx->stream, descs, res, L);
+        hipLaunchKernelGGL(k_sim3_opt<1>, dim3(P), dim3(64), 0, ctx->stream, st.dev(descs), res.dev, L);
     timer_end(ctx, "sim3opt");
     ORBX_HIP_CHECK(hipGetLastError());
+    if ((r = res.read()) != ORBX_OK) return r;
+    for (int k = 0; k < P; k++) {
+        if (ci[k].empty()) scatter_empty(&qs[k]);
+        else scatter(res.block(k), L, ci[k], taps, &qs[k]);
+    }
     return ORBX_OK;
 }
 
@@ -900,11 +923,14 @@ int launch_sim3opt(orbx_ctx* ctx, int P, const Sim3OptProb* descs, uint8_t* res,
 extern "C" int orbx_optimize_sim3_batch(orbx_ctx* ctx, int B, orbx_sim3_opt_query* qs)
 {
     if (!ctx || !qs || B < 1) return ORBX_ERR_ARG;
-    // argument rules, before any device work
+    // argument rules, before any device work; what travels is taken as it is checked:
+    // descriptors | per candidate: keypoints, correspondence lists, positions, level tables
     std::vector<std::vector<int32_t>> ci(B), cj(B);
+    std::vector<Sim3OptStaged> at(B);
     int cap = 1, work = 0;
     bool taps = false;
-    size_t bytes = up16((size_t)B * sizeof(Sim3OptProb));
+    PackedStage st(ctx);
+    const Region<Sim3OptProb> descs = st.take<Sim3OptProb>(B);
     for (int b = 0; b < B; b++) {
         const orbx_sim3_opt_query& q = qs[b];
         if (q.n1 < 0 || q.n2 < 0 || (q.n1 > 0 && (!q.keys1 || !q.pos1 || !q.valid1)) ||
@@ -915,19 +941,16 @@ extern "C" int orbx_optimize_sim3_batch(orbx_ctx* ctx, int B, orbx_sim3_opt_quer
         if (r != ORBX_OK) return r;
         if (q.nlevels < 1 || q.nlevels > kMaxLevels) return ORBX_ERR_ARG;
         if (q.n1 > kMaxFeatures || q.n2 > kMaxFeatures) return ORBX_ERR_UNSUPPORTED;
-        for (int i = 0; i < q.n1; i++)
-            if (q.keys1[i].octave < 0 || q.keys1[i].octave >= q.nlevels) return ORBX_ERR_ARG;
-        for (int i = 0; i < q.n2; i++)
-            if (q.keys2[i].octave < 0 || q.keys2[i].octave >= q.nlevels) return ORBX_ERR_ARG;
+        if (!octaves_ok(q.keys1, q.n1, q.nlevels) || !octaves_ok(q.keys2, q.n2, q.nlevels)) return ORBX_ERR_ARG;
         if ((r = correspondences(q.matches12, q.n1, q.n2, q.valid1, 0, q.valid2, 0, &ci[b], &cj[b])) != ORBX_OK) return r;
         const int n = (int)ci[b].size();
         if (any_corr_tap(q) && q.cap < n) return ORBX_ERR_CAPACITY;
         taps = taps || any_tap(q);
         cap = std::max(cap, n);
         work += n > 0;
-        bytes += up16((size_t)q.n1 * sizeof(orbx_keypoint)) + up16((size_t)q.n2 * sizeof(orbx_keypoint)) +
-                 2 * up16((size_t)n * 4) + up16((size_t)q.n1 * 12) + up16((size_t)q.n2 * 12) +
-                 2 * up16((size_t)q.nlevels * 4);
+        at[b] = {st.take(q.n1, q.keys1), st.take(q.n2, q.keys2), st.take(n, ci[b].data()), st.take(n, cj[b].data()),
+                 st.take((size_t)q.n1 * 3, q.pos1), st.take((size_t)q.n2 * 3, q.pos2),
+                 st.take(q.nlevels, q.inv_sigma2_1), st.take(q.nlevels, q.sigma2_2)};
     }
     if (work == 0) {
         for (int b = 0; b < B; b++) scatter_empty(&qs[b]);
@@ -935,46 +958,17 @@ extern "C" int orbx_optimize_sim3_batch(orbx_ctx* ctx, int B, orbx_sim3_opt_quer
     }
     ctx_enter(ctx);
     const Sim3OptLayout L = sim3opt_layout(cap, taps);
-    const size_t o_res = up16(bytes);
-    const size_t res_bytes = (size_t)B * L.stride;
-    int r = ensure_scratch(ctx, o_res + res_bytes);
+    int r = st.open((size_t)B * L.stride);
     if (r != ORBX_OK) return r;
-    uint8_t* dev = static_cast<uint8_t*>(ctx->scratch);
-    // one upload: descriptors | per candidate: keypoints, correspondence lists, positions, level tables
-    std::vector<uint8_t> blob(o_res, 0);
-    Sim3OptProb* descs = reinterpret_cast<Sim3OptProb*>(blob.data());
-    size_t o = up16((size_t)B * sizeof(Sim3OptProb));
-    auto put = [&](const void* src, size_t nbytes) {
-        const size_t at = o;
-        if (nbytes) std::memcpy(blob.data() + at, src, nbytes);
-        o += up16(nbytes);
-        return dev + at;
-    };
     for (int b = 0; b < B; b++) {
         const orbx_sim3_opt_query& q = qs[b];
-        Sim3OptProb& d = descs[b];
-        const int n = (int)ci[b].size();
-        d.k1 = reinterpret_cast<const orbx_keypoint*>(put(q.keys1, (size_t)q.n1 * sizeof(orbx_keypoint)));
-        d.k2 = reinterpret_cast<const orbx_keypoint*>(put(q.keys2, (size_t)q.n2 * sizeof(orbx_keypoint)));
-        d.ci = reinterpret_cast<const int32_t*>(put(ci[b].data(), (size_t)n * 4));
-        d.cj = reinterpret_cast<const int32_t*>(put(cj[b].data(), (size_t)n * 4));
-        d.pos1 = reinterpret_cast<const float*>(put(q.pos1, (size_t)q.n1 * 12));
-        d.pos2 = reinterpret_cast<const float*>(put(q.pos2, (size_t)q.n2 * 12));
-        d.isig1 = reinterpret_cast<const float*>(put(q.inv_sigma2_1, (size_t)q.nlevels * 4));
-        d.sig2 = reinterpret_cast<const float*>(put(q.sigma2_2, (size_t)q.nlevels * 4));
-        fill_prob(d, q, n, q.nlevels, q.T1w, q.T2w, q.cam1, q.cam2, taps);
+        Sim3OptProb& d = st.host(descs)[b];
+        d.k1 = st.dev(at[b].k1);
+        d.k2 = st.dev(at[b].k2);
+        point_prob(d, st, at[b]);
+        fill_prob(d, q, (int)ci[b].size(), q.nlevels, q.T1w, q.T2w, q.cam1, q.cam2, taps);
     }
-    if (o > o_res) return ORBX_ERR_NOMEM;   // the sizes above and the layout here disagree
-    ORBX_HIP_CHECK(hipMemcpyAsync(dev, blob.data(), o_res, hipMemcpyHostToDevice, ctx->stream));
-    if ((r = launch_sim3opt(ctx, B, reinterpret_cast<const Sim3OptProb*>(dev), dev + o_res, L)) != ORBX_OK) return r;
-    std::vector<uint8_t> out(res_bytes);
-    ORBX_HIP_CHECK(hipMemcpyAsync(out.data(), dev + o_res, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    for (int b = 0; b < B; b++) {
-        if (ci[b].empty()) scatter_empty(&qs[b]);
-        else scatter(out.data() + (size_t)b * L.stride, L, ci[b], taps, &qs[b]);
-    }
-    return ORBX_OK;
+    return run_sim3opt(st, descs, L, ci, taps, qs);
 }
 
 extern "C" int orbx_optimize_sim3(orbx_ctx* ctx, orbx_sim3_opt_query* q) { return orbx_optimize_sim3_batch(ctx, 1, q); }
@@ -999,72 +993,43 @@ extern "C" int orbx_dev_optimize_sim3(orbx_ctx* ctx, int slot1, const orbx_sim3_
     if (nf > kMaxFeatures) return ORBX_ERR_UNSUPPORTED;
     ctx_enter(ctx);
     // the slots' feature counts bound the arrays the caller passes
-    std::vector<int32_t> cnt(ctx->slots);
-    ORBX_HIP_CHECK(hipMemcpyAsync(cnt.data(), ctx->out_n, sizeof(int32_t) * ctx->slots, hipMemcpyDeviceToHost, ctx->stream));
-    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    std::vector<int32_t> cnt;
+    int r = read_slot_counts(ctx, cnt);
+    if (r != ORBX_OK) return r;
     auto count = [&](int slot) { return std::max(0, std::min<int>(cnt[slot], nf)); };
     const int n1 = count(slot1);
     const int nl = kf1->nlevels;
     std::vector<std::vector<int32_t>> ci(n), cj(n);
+    std::vector<Sim3OptStaged> at(n);
     int cap = 1, work = 0;
     bool taps = false;
-    size_t bytes = up16((size_t)n * sizeof(Sim3OptProb)) + up16((size_t)n1 * 12) + up16((size_t)nl * 4);
+    // what travels: descriptors | KF1: positions, inverse sigma2 | per candidate: lists, positions, sigma2
+    PackedStage st(ctx);
+    const Region<Sim3OptProb> descs = st.take<Sim3OptProb>(n);
+    const Region<float> pos1 = st.take((size_t)n1 * 3, kf1->pos), isig1 = st.take(nl, inv_sigma2_1);
     for (int k = 0; k < n; k++) {
         const int n2 = count(slots2[k]);
-        const int r = correspondences(out[k].matches12, n1, n2, kf1->mp, 1, kf2s[k].mp, 1, &ci[k], &cj[k]);
-        if (r != ORBX_OK) return r;
+        if ((r = correspondences(out[k].matches12, n1, n2, kf1->mp, 1, kf2s[k].mp, 1, &ci[k], &cj[k])) != ORBX_OK) return r;
         const int nc = (int)ci[k].size();
         if (any_corr_tap(out[k]) && out[k].cap < nc) return ORBX_ERR_CAPACITY;
         taps = taps || any_tap(out[k]);
         cap = std::max(cap, nc);
         work += nc > 0;
-        bytes += 2 * up16((size_t)nc * 4) + up16((size_t)n2 * 12) + up16((size_t)nl * 4);
+        at[k] = {{}, {}, st.take(nc, ci[k].data()), st.take(nc, cj[k].data()), pos1,
+                 st.take((size_t)n2 * 3, kf2s[k].pos), isig1, st.take(nl, kf2s[k].sigma2)};
     }
     if (work == 0) {
         for (int k = 0; k < n; k++) scatter_empty(&out[k]);
         return ORBX_OK;
     }
     const Sim3OptLayout L = sim3opt_layout(cap, taps);
-    const size_t o_res = up16(bytes);
-    const size_t res_bytes = (size_t)n * L.stride;
-    int r = ensure_scratch(ctx, o_res + res_bytes);
-    if (r != ORBX_OK) return r;
-    uint8_t* dev = static_cast<uint8_t*>(ctx->scratch);
-    // what travels: descriptors | KF1: positions, inverse sigma2 | per candidate: lists, positions, sigma2
-    std::vector<uint8_t> blob(o_res, 0);
-    Sim3OptProb* descs = reinterpret_cast<Sim3OptProb*>(blob.data());
-    size_t o = up16((size_t)n * sizeof(Sim3OptProb));
-    auto put = [&](const void* src, size_t nbytes) {
-        const size_t at = o;
-        if (nbytes) std::memcpy(blob.data() + at, src, nbytes);
-        o += up16(nbytes);
-        return dev + at;
-    };
-    const float* d_pos1 = reinterpret_cast<const float*>(put(kf1->pos, (size_t)n1 * 12));
-    const float* d_isig1 = reinterpret_cast<const float*>(put(inv_sigma2_1, (size_t)nl * 4));
+    if ((r = st.open((size_t)n * L.stride)) != ORBX_OK) return r;
     for (int k = 0; k < n; k++) {
-        Sim3OptProb& d = descs[k];
-        const int n2 = count(slots2[k]);
-        const int nc = (int)ci[k].size();
+        Sim3OptProb& d = st.host(descs)[k];
         d.k1 = slot_frame_dev(ctx, slot1, nullptr).kps;
         d.k2 = slot_frame_dev(ctx, slots2[k], nullptr).kps;
-        d.ci = reinterpret_cast<const int32_t*>(put(ci[k].data(), (size_t)nc * 4));
-        d.cj = reinterpret_cast<const int32_t*>(put(cj[k].data(), (size_t)nc * 4));
-        d.pos1 = d_pos1;
-        d.pos2 = reinterpret_cast<const float*>(put(kf2s[k].pos, (size_t)n2 * 12));
-        d.isig1 = d_isig1;
-        d.sig2 = reinterpret_cast<const float*>(put(kf2s[k].sigma2, (size_t)nl * 4));
-        fill_prob(d, out[k], nc, nl, kf1->Tcw, kf2s[k].Tcw, kf1->cam, kf2s[k].cam, taps);
+        point_prob(d, st, at[k]);
+        fill_prob(d, out[k], (int)ci[k].size(), nl, kf1->Tcw, kf2s[k].Tcw, kf1->cam, kf2s[k].cam, taps);
     }
-    if (o > o_res) return ORBX_ERR_NOMEM;
-    ORBX_HIP_CHECK(hipMemcpyAsync(dev, blob.data(), o_res, hipMemcpyHostToDevice, ctx->stream));
-    if ((r = launch_sim3opt(ctx, n, reinterpret_cast<const Sim3OptProb*>(dev), dev + o_res, L)) != ORBX_OK) return r;
-    std::vector<uint8_t> res(res_bytes);
-    ORBX_HIP_CHECK(hipMemcpyAsync(res.data(), dev + o_res, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < n; k++) {
-        if (ci[k].empty()) scatter_empty(&out[k]);
-        else scatter(res.data() + (size_t)k * L.stride, L, ci[k], taps, &out[k]);
-    }
-    return ORBX_OK;
+    return run_sim3opt(st, descs, L, ci, taps, out);
 }

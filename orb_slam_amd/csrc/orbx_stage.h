@@ -1,46 +1,35 @@
-// Host-side staging of one matcher call in the context scratch: where each
-// array lies, and the two ways its bytes travel.
+// Host-side staging of one call in the context scratch: where each array
+// lies, and the three ways its bytes travel.
 //
 // A call lays its arrays out with take<T>(count).  The Region<T> it gets back
 // is the only statement of that array's offset and length: the device pointer
-// and every copy are derived from it.  Every region starts on a 256-byte
-// boundary and owns at least 256 bytes, so no two regions share an address,
-// an empty one included.
+// and every copy are derived from it.
 //
-// BlockStage moves the call through the context's page-locked buffer: put /
-// fill write at the region's own offset, one copy takes [0, end) up, one copy
-// and a sync bring the read-back range down.  ArrayStage moves each array on
-// its own between the caller's memory and the device.
+// Layout (BlockStage, ArrayStage), for the matcher calls' few large arrays:
+// every region starts on a 256-byte boundary and owns at least 256 bytes, so no
+// two regions share an address, an empty one included.  BlockStage moves the
+// call through the context's page-locked buffer: put / fill write at the
+// region's own offset, one copy takes [0, end) up, one copy and a sync bring
+// the read-back range down.  ArrayStage moves each array on its own between
+// the caller's memory and the device.
+//
+// PackedStage (orbx_pack.h's PackedLayout), for the batched solver calls' ten
+// small arrays per query: 16-byte granularity, a call-owned pageable blob, one
+// upload; the result blocks behind the inputs come back through ResultBlocks.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstring>
+#include <memory>
+#include <new>
 #include <vector>
 
 #include "orbx_internal.h"
+#include "orbx_pack.h"
 
 namespace orbx {
 
 inline size_t align256(size_t bytes) { return (bytes + 255) & ~size_t(255); }
-
-template <typename T>
-struct Region {
-    size_t off = 0, count = 0;
-    size_t bytes() const { return count * sizeof(T); }
-    size_t end() const { return off + bytes(); }
-    // n elements of U starting byte_off into this region (rows of an image,
-    // one struct of an array, the arrays behind a header)
-    template <typename U = T>
-    Region<U> part(size_t byte_off, size_t n) const
-    {
-        return Region<U>{off + byte_off, n};
-    }
-};
-
-template <typename T>
-T* region_ptr(void* base, Region<T> r)
-{
-    return reinterpret_cast<T*>(static_cast<uint8_t*>(base) + r.off);
-}
 
 struct Layout {
     size_t total = 0;
@@ -135,14 +124,8 @@ struct BlockStage : Layout {
 // One copy per array between the caller's memory and the scratch.  An input
 // named at take() goes up in upload(), in the order taken; put() copies at
 // once (after open()).  Empty arrays are not copied.
-struct ArrayStage : Layout {
+struct ArrayStage : Layout, PendingCopies {
     orbx_ctx* ctx;
-    struct Pending {
-        size_t off;
-        const void* src;
-        size_t bytes;
-    };
-    std::vector<Pending> pending;
     explicit ArrayStage(orbx_ctx* c) : ctx(c) {}
     template <typename T>
     Region<T> take(size_t count, const T* src = nullptr)
@@ -150,11 +133,6 @@ struct ArrayStage : Layout {
         const Region<T> r = Layout::take<T>(count);
         later(r, src);
         return r;
-    }
-    template <typename T>
-    void later(Region<T> r, const T* src)
-    {
-        if (src && r.count) pending.push_back({r.off, src, r.bytes()});
     }
     int open() { return ensure_scratch(ctx, total); }
     int upload()
@@ -201,5 +179,79 @@ struct ArrayStage : Layout {
         return get(dst, r, r.count);
     }
 };
+
+// The packed inputs of a batched solver call on the context stream.
+struct PackedStage : PackedLayout {
+    orbx_ctx* ctx;
+    explicit PackedStage(orbx_ctx* c) : ctx(c) {}
+    // in the context scratch, `behind` bytes of result blocks after the inputs
+    // (a call that follows a queued search binds to BowQueued::extra instead)
+    int open(size_t behind)
+    {
+        const int r = ensure_scratch(ctx, total + behind);
+        if (r == ORBX_OK) bind(ctx->scratch);
+        return r;
+    }
+    uint8_t* behind() const { return base + total; }
+    int upload()
+    {
+        if (total) ORBX_HIP_CHECK(hipMemcpyAsync(base, blob.data(), total, hipMemcpyHostToDevice, ctx->stream));
+        return ORBX_OK;
+    }
+};
+
+// P result blocks of `stride` bytes on the device and their host copy.
+struct ResultBlocks {
+    orbx_ctx* ctx;
+    uint8_t* dev;
+    size_t P, stride, pitch = 0;
+    std::unique_ptr<uint8_t[]> h;
+    ResultBlocks(orbx_ctx* c, uint8_t* d, size_t blocks, size_t s) : ctx(c), dev(d), P(blocks), stride(s) {}
+    // for the kernels that count on zeroed blocks
+    int zero()
+    {
+        ORBX_HIP_CHECK(hipMemsetAsync(dev, 0, P * stride, ctx->stream));
+        return ORBX_OK;
+    }
+    // the first `head` bytes of every block (0: all of it), waited for
+    int read(size_t head = 0)
+    {
+        pitch = head ? head : stride;
+        h.reset(new (std::nothrow) uint8_t[pitch * P]);
+        if (!h) return ORBX_ERR_NOMEM;
+        if (pitch == stride)
+            ORBX_HIP_CHECK(hipMemcpyAsync(h.get(), dev, P * stride, hipMemcpyDeviceToHost, ctx->stream));
+        else
+            ORBX_HIP_CHECK(hipMemcpy2DAsync(h.get(), pitch, dev, stride, pitch, P, hipMemcpyDeviceToHost, ctx->stream));
+        ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        return ORBX_OK;
+    }
+    const uint8_t* block(size_t k) const { return h.get() + k * pitch; }
+};
+
+// Every slot's feature count (ctx->out_n), waited for.
+inline int read_slot_counts(orbx_ctx* ctx, std::vector<int32_t>& cnt)
+{
+    cnt.resize(ctx->slots);
+    ORBX_HIP_CHECK(hipMemcpyAsync(cnt.data(), ctx->out_n, sizeof(int32_t) * ctx->slots, hipMemcpyDeviceToHost, ctx->stream));
+    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return ORBX_OK;
+}
+
+// Every keypoint's octave indexes a table of nlevels entries.
+inline bool octaves_ok(const orbx_keypoint* k, int n, int nlevels)
+{
+    for (int i = 0; i < n; i++)
+        if (k[i].octave < 0 || k[i].octave >= nlevels) return false;
+    return true;
+}
+
+// ceil(log(1 - p) / log(1 - eps^3)) of both SetRansacParameters (Sim3Solver.cc:114-138, PnPsolver.cc:93-124)
+// as the int the device tables hold: a quotient past INT_MAX (or a NaN) saturates, one below 1 is 1.
+inline int ransac_iterations(float eps, double probability)
+{
+    const double v = std::ceil(std::log(1 - probability) / std::log(1 - std::pow((double)eps, 3)));
+    return !(v < 2147483647.0) ? 2147483647 : (v < 1.0 ? 1 : (int)v);
+}
 
 }  // namespace orbx

@@ -220,3 +220,22 @@ def test_device_resident_pairs(async_match):
             layer1(got[s], k1, k2, m, draws[s], M)
     finally:
         c.close()
+
+
+def test_batch_of_packed_lengths_in_either_order(ctx):
+    """Three pairs in one batch whose first frames have 17, 0 and 31
+    keypoints and which draw 17, 1 and 31 sets: nothing is a multiple of the
+    16-byte packing step and an empty pair lies between the others.  Every
+    result is the single call's and the outer ones pass layer 1, in either
+    order."""
+    qs = [small_pair(60, 10, M=17), small_pair(61, 0, M=1, extra1=0, extra2=0), small_pair(62, 24, M=31)]
+    assert [len(q[0]) for q in qs] == [17, 0, 31]
+    single = [ctx.init_models(*q, taps=True) for q in qs]
+    assert [r["n_matches"] for r in single] == [10, 0, 24]
+    for order in ((0, 1, 2), (2, 1, 0)):
+        out = ctx.init_models_batch([qs[k] for k in order], taps=True)
+        for r, k in zip(out, order):
+            same_result(r, single[k])
+            if k != 1:
+                layer1(r, *qs[k][:4], qs[k][5])
+        assert out[1]["best_h"] == out[1]["best_f"] == -1 and out[1]["H21"] is None and out[1]["F21"] is None

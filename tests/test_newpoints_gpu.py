@@ -327,3 +327,26 @@ def test_timer_counts_the_launches(ctx, chain_case):
         assert ctx.kernel_time("triangulate")[0] == len(V2s)
     finally:
         ctx.timing(False)
+
+
+def test_neighbours_of_packed_lengths_in_either_order(ctx, big):
+    """Three neighbours in one call with 31, 0 and 17 keypoints against 17 of
+    KF1: nothing is a multiple of the 16-byte packing step and an empty
+    neighbour lies between the others.  The outer ones pass layer 1, the empty
+    one creates nothing, and every neighbour's result is its single call's, in
+    either order."""
+    keys1, g1, keys2, g2s, m = cut(big, 17, 3)
+    keys2 = [keys2[0][:31], keys2[1][:0], keys2[2][:17]]
+    m = [np.where(t < len(k), t, -1).astype(np.int32) for t, k in zip(m, keys2)]
+    assert [len(k) for k in keys2] == [31, 0, 17] and (m[0] >= 0).any() and (m[2] >= 0).any()
+    single = [ctx.triangulate_matches(keys1, g1, [keys2[k]], [g2s[k]], [m[k]], v4=True) for k in range(3)]
+    for order in ((0, 1, 2), (2, 1, 0)):
+        dev = ctx.triangulate_matches(keys1, g1, [keys2[k] for k in order], [g2s[k] for k in order],
+                                      [m[k] for k in order], v4=True)
+        for pos, k in enumerate(order):
+            for name in ("status", "xyz", "v4"):
+                assert dev[name][pos].tobytes() == single[k][name][0].tobytes(), (name, k)
+            assert dev["n_created"][pos] == single[k]["n_created"][0]
+        assert not dev["status"][1].any() and dev["n_created"][1] == 0 and not dev["xyz"][1].any()
+    for k in (0, 2):
+        assert_layer1(single[k], keys1, g1, [keys2[k]], [g2s[k]], [m[k]])

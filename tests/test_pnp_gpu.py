@@ -603,3 +603,35 @@ def test_slot_form_equals_search_then_batch():
         if voc:
             ox.lib().orbx_vocab_destroy(voc)
         c.close()
+
+
+def test_batch_of_packed_lengths_in_either_order(ctx):
+    """Three candidates in one batch whose arrays have 17, 0 and 31 entries
+    (draws included): nothing but the 16-byte draws is a multiple of the
+    packing step and an empty candidate lies between the others; the first
+    asks for taps, the others do not.  Every result is the single call's, the
+    tapped one passes layer 1, in either order."""
+    scs = [pn.scene(10, seed=40), None, pn.scene(24, seed=41)]
+    scs[1] = {k: (v[:0] if k in ("keys", "pos", "valid") else v) for k, v in pn.frame_of(scs[0]).items()}
+    assert [len(s["keys"]) for s in scs] == [17, 0, 31]
+    T = (17, 1, 31)
+    draws = [pn.draws_for(50 + k, T[k]) for k in range(3)]
+    params = [dict(pn.RELOC, max_iterations=T[k], n_iter=T[k]) for k in range(3)]
+    taps = (True, False, False)
+    frames = [pn.frame_of(s) if "R" in s else s for s in scs]
+    single = [ctx.pnp_ransac(frames[k], draws[k], taps=taps[k], **params[k]) for k in range(3)]
+    assert [r["N"] for r in single] == [10, 0, 24]
+    for order in ((0, 1, 2), (2, 1, 0)):
+        built = [ox.pnp_query(frames[k], draws[k], taps=taps[k], **params[k]) for k in order]
+        arr = (ox.PnpQuery * 3)(*[b[0] for b in built])
+        assert ox.lib().orbx_pnp_ransac_batch(ctx.handle, 3, arr) == 0
+        for pos, k in enumerate(order):
+            r = ox.pnp_result(arr[pos], built[pos][1], taps[k])
+            same_call(r, single[k])
+            if taps[k]:
+                for name in ("sets", "count", "rec", "refit_rec", "refit_count", "record_iter", "p2d", "p3d", "max_err",
+                             "kp_index"):
+                    assert canon(r[name]) == canon(single[k][name]), name
+                layer1(r, scs[k], draws[k], params[k])
+            if k == 1:
+                assert r["no_more"] == 1 and r["iters_run"] == 0 and not r["found"]

@@ -439,3 +439,26 @@ def test_device_resident_pairs(async_match):
             c.read_init_reconstruct(1)
     finally:
         c.close()
+
+
+def test_batch_of_packed_lengths_in_either_order(ctx):
+    """Three queries in one batch with 17, 0 and 31 matches (a homography and
+    a fundamental matrix at the ends): nothing is a multiple of the 16-byte
+    packing step and an empty query lies between the others.  Every result
+    is the single call's and the outer ones pass layer 1, in either order."""
+    def query(seed, N, model, plane=None):
+        k1, k2, m, truth = rn.scene(seed, N, plane=plane, extra1=0, extra2=5)
+        return (k1, k2, m, np.ones(N, np.uint8), model, rn.true_model(model, truth, plane), rn.CAM)
+
+    a, b = query(130, 17, 1), query(131, 31, 0, rn.PLANE_CLEAR)
+    none = (a[0][:0], a[1][:0], np.zeros(0, np.int32), np.zeros(0, np.uint8), 1, a[5], a[6])
+    qs = [a, none, b]
+    single = [ctx.init_reconstruct(*q, taps=True) for q in qs]
+    assert [r["n_inliers"] for r in single] == [17, 0, 31]
+    for order in ((0, 1, 2), (2, 1, 0)):
+        out = ctx.init_reconstruct_batch([qs[k] for k in order], taps=True)
+        for r, k in zip(out, order):
+            same_result(r, single[k])
+            if k != 1:
+                assert_layer1(r, qs[k])
+        assert out[1]["ok"] == 0 and out[1]["n_hyp"] == 0 and not out[1]["p3d"].any()

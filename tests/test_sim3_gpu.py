@@ -398,3 +398,29 @@ def test_slot_form_equals_search_then_batch():
         if voc:
             ox.lib().orbx_vocab_destroy(voc)
         c.close()
+
+
+def test_batch_of_packed_lengths_in_either_order(ctx):
+    """Three pairs in one batch whose arrays have 17, 0 and 31 entries (draws
+    included): nothing is a multiple of the 16-byte packing step and an empty
+    pair lies between the others; the first has idx1, the last does not.
+    Every result is the single call's and passes layer 1, in either order."""
+    a, b = s3.scene(60, 11, use_idx1=True, unmatched=2, invalid=1), s3.scene(61, 27, unmatched=2, invalid=1)
+    assert len(a[0]["keys"]) == 17 and len(b[0]["keys"]) == 31 and a[3] is not None and b[3] is None
+
+    def none_of(kf):
+        return dict(kf, keys=kf["keys"][:0], pos=kf["pos"][:0], valid=kf["valid"][:0])
+
+    qs = [(a[0], a[1], a[2], s3.make_draws(62, 17), dict(idx1=a[3], min_inliers=6)),
+          (none_of(a[0]), none_of(a[1]), np.zeros(0, np.int32), s3.make_draws(63, 1), dict(idx1=None, min_inliers=6)),
+          (b[0], b[1], b[2], s3.make_draws(64, 31), dict(idx1=None, min_inliers=6))]
+    single = [ctx.sim3_ransac(*q[:4], taps=True, **q[4]) for q in qs]
+    assert [r["N"] for r in single] == [11, 0, 27]
+    for order in ((0, 1, 2), (2, 1, 0)):
+        out = ctx.sim3_ransac_batch([qs[k] for k in order], taps=True)
+        for r, k in zip(out, order):
+            same_result(r, single[k])
+            if k != 1:
+                layer1(r, *qs[k])
+        e = out[1]
+        assert e["no_more"] == 1 and e["iters_run"] == 0 and e["ransac_max_its"] == 0 and not e["found"]

@@ -288,3 +288,32 @@ def test_slot_form_equals_the_host_array_form():
         assert dev[1]["returned_early"] and dev[1]["n_corr"] > 100
     finally:
         c.close()
+
+
+def test_batch_of_packed_lengths_in_either_order(ctx):
+    """Three candidates in one batch whose keyframes have 17, 0 and 31
+    keypoints: nothing is a multiple of the 16-byte packing step and an empty
+    candidate lies between the others; the first asks for taps, the others do
+    not.  Every result is the single call's, in either order."""
+    kw = dict(null=2, invalid=2, unobserved=2, extra2=6, gross=0.2)
+    args = [so.scene(520, 9, **kw), None, so.scene(521, 23, **kw)]
+    kf1, kf2 = args[0][:2]
+
+    def none_of(kf):
+        return dict(kf, keys=kf["keys"][:0], pos=kf["pos"][:0], valid=kf["valid"][:0])
+
+    args[1] = (none_of(kf1), none_of(kf2), np.zeros(0, np.int32), args[0][3])
+    args = [(a[0], a[1], a[2], *a[3]) for a in args]
+    assert [len(a[0]["keys"]) for a in args] == [17, 0, 31]
+    taps = (True, False, False)
+    single = [ctx.optimize_sim3(*args[k], th2=TH2, taps=taps[k]) for k in range(3)]
+    assert [s["n_corr"] for s in single] == [9, 0, 23]
+    for order in ((0, 1, 2), (2, 1, 0)):
+        built = [ox.sim3_opt_query(*args[k], th2=TH2, taps=taps[k]) for k in order]
+        arr = (ox.Sim3OptQuery * 3)(*[b[0] for b in built])
+        assert ox.lib().orbx_optimize_sim3_batch(ctx.handle, 3, arr) == 0
+        for pos, k in enumerate(order):
+            same(ox.sim3_opt_result(arr[pos], built[pos][1], taps[k]), single[k])
+    pb = so.build_problem(args[0][0], args[0][1], args[0][2], TH2)
+    assert bits(single[0]["corr_index"]) == bits(pb["idx"]) and bits(single[0]["x3dc1"]) == bits(pb["x3dc1"])
+    assert single[1]["returned_early"] == 1 and single[1]["n_in"] == 0
