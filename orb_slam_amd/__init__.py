@@ -619,6 +619,7 @@ def _declare(L):
         "orbx_debug_describe_patch": ([vp, i, i, i, i, vp], i),
         "orbx_debug_describe_moments": ([vp, i, i, i, i, vp], i),
         "orbx_debug_level0_direct": ([vp], i),
+        "orbx_debug_write_features": ([vp, i, vp, vp, i], i),
         "orbx_debug_fast_instance": ([vp, vp], i),
         "orbx_debug_fast_lists": ([vp, i, vp, i, vp, i, vp], i),
         "orbx_debug_fast_list_cap": ([vp, i], i),
@@ -844,6 +845,16 @@ class Context:
         _check(lib().orbx_dev_read_features(self._h, slot, _ptr(kps), _ptr(desc), self.nfeatures,
                                             ctypes.byref(n)), "orbx_dev_read_features")
         return kps[:n.value].copy(), desc[:n.value].copy()
+
+    def write_features(self, slot, kps, desc):
+        """Debug (orbx_debug_write_features): host keypoint records and
+        descriptors become the slot's device outputs and count, so the slot
+        matchers can be given inputs that extraction never produces."""
+        kps = np.ascontiguousarray(kps, KEYPOINT)
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(len(kps), 32)
+        _check(lib().orbx_debug_write_features(self._h, slot, _ptr(kps) if len(kps) else None,
+                                               _ptr(desc) if len(kps) else None, len(kps)),
+               "orbx_debug_write_features")
 
     def matches(self, slot):
         m = np.zeros(self.nfeatures, np.int32)

@@ -535,6 +535,25 @@ int orbx_dev_read_features(orbx_ctx* ctx, int slot, orbx_keypoint* kps, uint8_t*
     return ORBX_OK;
 }
 
+// Debug: host keypoint records and descriptors into a slot's device outputs
+// and count, as if extraction had left them there (the slot matchers then run
+// on inputs the extractor never produces).  No other path calls it.
+extern "C" int orbx_debug_write_features(orbx_ctx* ctx, int slot, const orbx_keypoint* kps, const uint8_t* desc, int n)
+{
+    if (!ctx || slot < 0 || slot >= ctx->slots || n < 0 || n > ctx->geom.nfeatures || (n > 0 && (!kps || !desc)))
+        return ORBX_ERR_ARG;
+    ctx_enter(ctx);
+    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    const size_t nf = ctx->geom.nfeatures;
+    const int32_t n32 = n;
+    if (n > 0) {
+        ORBX_HIP_CHECK(hipMemcpy(ctx->out_kps + slot * nf, kps, n * sizeof(orbx_keypoint), hipMemcpyHostToDevice));
+        ORBX_HIP_CHECK(hipMemcpy(ctx->out_desc + slot * nf * 32, desc, (size_t)n * 32, hipMemcpyHostToDevice));
+    }
+    ORBX_HIP_CHECK(hipMemcpy(ctx->out_n + slot, &n32, sizeof(int32_t), hipMemcpyHostToDevice));
+    return ORBX_OK;
+}
+
 int orbx_dev_read_matches(orbx_ctx* ctx, int slot, int32_t* matches12, int cap, int* n_matches, int* n1)
 {
     if (!ctx || slot < 0 || slot >= ctx->slots) return ORBX_ERR_ARG;

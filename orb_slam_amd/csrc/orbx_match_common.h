@@ -353,6 +353,63 @@ __device__ inline void sfi_query_fill(const InitLDS& s, int nc, int4 qa, float2 
     }
 }
 
+// The same two passes where the candidate slots are ordered by grid column
+// (the batch instance of the routine below): the query's cell columns
+// [min_cx, max_cx] are the slot range [lo, hi), carried in the upper bits of
+// qarea's first two words (min_cx | lo << 8, max_cx | hi << 8), and only
+// that range is scanned.  in_area_rec is the same test: it alone decides
+// membership, the range only leaves out slots whose column fails it.
+struct ColsQuery {
+    AreaQuery q;
+    int lo, hi;
+};
+
+__device__ inline ColsQuery cols_query_of(const int4 qa)
+{
+    ColsQuery c;
+    c.q.min_cx = qa.x & 0xFF; c.q.max_cx = qa.y & 0xFF; c.q.min_cy = qa.z; c.q.max_cy = qa.w; c.q.empty = false;
+    // wave-uniform (one query per wave): scalar loop bounds
+    c.lo = __builtin_amdgcn_readfirstlane(qa.x >> 8);
+    c.hi = __builtin_amdgcn_readfirstlane(qa.y >> 8);
+    return c;
+}
+
+// the count from the ballots' scalar popcounts
+__device__ inline int sfi_query_count_cols(const InitLDS& s, int4 qa, float2 qp, float r, int lane)
+{
+    const ColsQuery c = cols_query_of(qa);
+    int cnt = 0;
+    for (int j0 = c.lo; j0 < c.hi; j0 += 64) {
+        const int j = j0 + lane;
+        const bool ok = in_area_rec(c.q, s.rec[min(j, c.hi - 1)], qp.x, qp.y, r) & (j < c.hi);
+        cnt += __popcll(__ballot(ok));
+    }
+    return cnt;
+}
+
+__device__ inline void sfi_query_fill_cols(const InitLDS& s, int4 qa, float2 qp, uint4 d1a, uint4 d1b, float r,
+                                           uint32_t* out, int lane)
+{
+    const ColsQuery c = cols_query_of(qa);
+    const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    int w = 0;
+    for (int j0 = c.lo; j0 < c.hi; j0 += 64) {
+        const int j = j0 + lane;
+        bool ok = false;
+        float4 rc;
+        if (j < c.hi) {
+            rc = s.rec[j];
+            ok = in_area_rec(c.q, rc, qp.x, qp.y, r);
+        }
+        const unsigned long long bal = __ballot(ok);
+        if (ok) {
+            const int dist = hamming256(d1a, d1b, s.desc[2 * j], s.desc[2 * j + 1]);
+            out[w + __popcll(bal & lt_mask)] = ((uint32_t)dist << 23) | ((uint32_t)__float_as_int(rc.w) << 11) | (uint32_t)j;
+        }
+        w += __popcll(bal);
+    }
+}
+
 // a list of w <= 64 distinct keys into ascending order (each lane's rank),
 // from src to dst (may be the same array)
 __device__ inline void sfi_sort_short(const uint32_t* src, uint32_t* dst, int w, int lane)
@@ -386,7 +443,34 @@ __device__ inline void search_for_init_block(const FrameDev& F1, const FrameDev&
     constexpr bool kSortLists = kT > kBlock;
     const int tid = threadIdx.x, lane = tid & 63;
     MP_T0();
-    // F2 octave-0 keypoints in index order -> candidate slots
+    // The batch instance orders the candidate slots by grid column (kOrd):
+    // F2's octave-0 keypoints in a stable order by cx, ties in index order,
+    // keypoints outside the grid last.  A query's cell columns are then a
+    // slot range and its two passes scan only that.  Within a grid cell the
+    // slots stay in index order, so the key (dist, cell, slot) orders
+    // candidates as before; idx[slot] gives the frame index.
+    constexpr bool kOrd = kT == kBlock && !kPre;
+    auto stage_slot = [&](int pos, int i2, const orbx_keypoint& k, int cell) {
+        s.x[pos] = k.x;
+        s.y[pos] = k.y;
+        s.ang[pos] = k.angle;
+        s.cell[pos] = cell;
+        s.rec[pos] = make_float4(k.x, k.y, __int_as_float(cell < 0 ? -1 : ((cell / kGridRows) | ((cell % kGridRows) << 8))),
+                                 __int_as_float(cell));
+        s.idx[pos] = i2;
+        s.mdist[pos] = 0x7fffffff;
+        s.m21[pos] = -1;
+        const uint4* d = reinterpret_cast<const uint4*>(F2.desc + (size_t)i2 * 32);
+        s.desc[2 * pos] = d[0];
+        s.desc[2 * pos + 1] = d[1];
+    };
+    // F2 octave-0 keypoints in index order -> candidate slots (kOrd: -> their
+    // sort words cx << 24 | index, in the query descriptors' space: 16-byte
+    // aligned, 2048 words >= cap_c, free until the first group is staged; an
+    // index is below kMaxFeatures)
+    uint32_t* const sortw = reinterpret_cast<uint32_t*>(s.qdesc);
+    static_assert(kInitMaxCand <= 2 * 256 * 4, "the sort words fit the query descriptors' space");
+    static_assert(kMaxFeatures <= 1 << 24, "cx << 24 | index");
     int nc = 0;
     for (int base = 0; base < F2.n; base += kT) {
         const int i2 = base + tid;
@@ -399,19 +483,9 @@ __device__ inline void search_for_init_block(const FrameDev& F1, const FrameDev&
         int tot;
         const int pos = nc + block_exclusive_scan(ok ? 1 : 0, &tot, bs, (base / kT) & 1);
         if (ok && pos < s.cap_c) {
-            s.x[pos] = k.x;
-            s.y[pos] = k.y;
-            s.ang[pos] = k.angle;
             const int cell = grid_cell(F2, k.x, k.y);
-            s.cell[pos] = cell;
-            s.rec[pos] = make_float4(k.x, k.y, __int_as_float(cell < 0 ? -1 : ((cell / kGridRows) | ((cell % kGridRows) << 8))),
-                                     __int_as_float(cell));
-            s.idx[pos] = i2;
-            s.mdist[pos] = 0x7fffffff;
-            s.m21[pos] = -1;
-            const uint4* d = reinterpret_cast<const uint4*>(F2.desc + (size_t)i2 * 32);
-            s.desc[2 * pos] = d[0];
-            s.desc[2 * pos + 1] = d[1];
+            if constexpr (kOrd) sortw[pos] = (uint32_t)(cell < 0 ? kGridCols : cell / kGridRows) << 24 | (uint32_t)i2;
+            else stage_slot(pos, i2, k, cell);
         }
         nc += tot;
     }
@@ -421,6 +495,25 @@ __device__ inline void search_for_init_block(const FrameDev& F1, const FrameDev&
             *out_n = ORBX_ERR_CAPACITY;
         }
         return;
+    }
+    if constexpr (kOrd) {
+        // a candidate's slot is the number of sort words below its own (they
+        // are distinct, and ascending in (cx, index)): the plain count, four
+        // words per LDS read
+        __syncthreads();
+        for (int p = tid; p < nc; p += kT) {
+            const uint32_t mine = sortw[p];
+            int rank = 0;
+            const uint4* k4 = reinterpret_cast<const uint4*>(sortw);
+            for (int q = 0; q < (nc >> 2); q++) {
+                const uint4 v = k4[q];
+                rank += (v.x < mine) + (v.y < mine) + (v.z < mine) + (v.w < mine);
+            }
+            for (int q = nc & ~3; q < nc; q++) rank += sortw[q] < mine;
+            const int i2 = (int)(mine & 0xFFFFFFu);
+            const orbx_keypoint k = F2.kps[i2];
+            stage_slot(rank, i2, k, grid_cell(F2, k.x, k.y));
+        }
     }
     // queries are the F1 octave-0 keypoints: the groups below stop after the
     // last one (extractor output is level-major, so they are a prefix)
@@ -453,6 +546,22 @@ __device__ inline void search_for_init_block(const FrameDev& F1, const FrameDev&
                     qp = make_float2(prev_xy ? prev_xy[2 * i1] : k1.x, prev_xy ? prev_xy[2 * i1 + 1] : k1.y);
                     const AreaQuery q = area_cells(F2, qp.x, qp.y, r);
                     if (!q.empty) qa = make_int4(q.min_cx, q.max_cx, q.min_cy, q.max_cy);
+                    if (kOrd && !q.empty && q.min_cx <= q.max_cx) {
+                        // the columns' slot range [first slot of a column
+                        // >= min_cx, first of a column > max_cx): slots
+                        // ascend in column, outside the grid (kGridCols) last
+                        auto first_slot = [&](int col) {
+                            int lo = 0, hi = nc;
+                            while (lo < hi) {
+                                const int m = (lo + hi) >> 1, c = __float_as_int(s.rec[m].z);
+                                if ((c < 0 ? kGridCols : (c & 0xFF)) < col) lo = m + 1;
+                                else hi = m;
+                            }
+                            return lo;
+                        };
+                        qa.x |= first_slot(q.min_cx) << 8;
+                        qa.y |= first_slot(q.max_cx + 1) << 8;
+                    }
                     load_desc(F1.desc + (size_t)i1 * 32, s.qdesc[2 * tid], s.qdesc[2 * tid + 1]);
                 }
             }
@@ -465,7 +574,9 @@ __device__ inline void search_for_init_block(const FrameDev& F1, const FrameDev&
         // count pass, one wave per query (lanes over the candidates): balanced
         // whatever the window population of individual queries
         for (int t = wv; t < gn; t += kW) {
-            const int cnt = kPre ? pre_cnt[g0 + t] : sfi_query_count(s, nc, s.qarea[t], s.qxy[t], r, lane);
+            const int cnt = kPre   ? pre_cnt[g0 + t]
+                            : kOrd ? sfi_query_count_cols(s, s.qarea[t], s.qxy[t], r, lane)
+                                   : sfi_query_count(s, nc, s.qarea[t], s.qxy[t], r, lane);
             if (lane == 0) s.offs[t] = cnt;
         }
         if (g0 == 0) MP_MARK(4);
@@ -501,7 +612,10 @@ __device__ inline void search_for_init_block(const FrameDev& F1, const FrameDev&
                 const int n = s.offs[t + 1] - s.offs[t];
                 if (n == 0) continue;
                 uint32_t* out = s.keys + (s.offs[t] - base_off);
-                sfi_query_fill(s, nc, s.qarea[t], s.qxy[t], s.qdesc[2 * t], s.qdesc[2 * t + 1], r, out, lane);
+                if constexpr (kOrd)
+                    sfi_query_fill_cols(s, s.qarea[t], s.qxy[t], s.qdesc[2 * t], s.qdesc[2 * t + 1], r, out, lane);
+                else
+                    sfi_query_fill(s, nc, s.qarea[t], s.qxy[t], s.qdesc[2 * t], s.qdesc[2 * t + 1], r, out, lane);
                 // a list that fits one wave is left in ascending key order
                 // (rank of each key among the list; keys are distinct)
                 if (kSortLists && n <= 64) sfi_sort_short(out, out, n, lane);
