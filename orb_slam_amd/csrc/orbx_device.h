@@ -82,17 +82,34 @@ __host__ __device__ inline int reflect101(int p, int len)
 
 // GaussianBlur 7x7 sigma 2 (OpenCV 2.4 8U fixed point, kernel {18,34,49,55,49,34,18}):
 // Horizontal 7-tap sums of the 4 pixels of dword wc (wl / wr: the dwords to
-// its left / right): taps j-3..j as one v_dot4_u32_u8 with {18,34,49,55},
-// taps j+1..j+3 as a second with {49,34,18,0}.
-__device__ inline void blur_hsum_w(uint32_t wl, uint32_t wc, uint32_t wr, int hs[4])
+// its left / right), from the aligned words: the taps of output byte j fall
+// on fixed bytes of wl, wc and wr, so the shift sits in the weight constants
+// (byte 0 in the low byte) and not in the data.  Two v_dot4_u32_u8 per sum;
+// bytes 1 and 2 share e = (wl.b2, wl.b3, wr.b0, wr.b1), the one word built.
+//   h0 = wl . {0,18,34,49} + wc . {55,49,34,18}
+//   h1 = e  . {18,34,18,0} + wc . {49,55,49,34}
+//   h2 = e  . {0,18,34,18} + wc . {34,49,55,49}
+//   h3 = wr . {49,34,18,0} + wc . {18,34,49,55}
+// bias: what the sums are added to.  With kBlurBias, the bits of the float
+// 2^23, hs[j] are the bits of the float 2^23 + h_j (h_j <= 255 * 257 < 2^23
+// lands in the mantissa): blur_hrow takes the 2^23 off again, exactly.
+constexpr uint32_t kBlurBias = 0x4B000000u;
+__device__ inline void blur_hsum_w(uint32_t wl, uint32_t wc, uint32_t wr, uint32_t bias, uint32_t hs[4])
 {
-    constexpr uint32_t kWA = 0x37312212u, kWB = 0x00122231u;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const uint32_t A = j == 3 ? wc : __builtin_amdgcn_alignbyte(wc, wl, j + 1);   // bytes j-3 .. j
-        const uint32_t B = j == 3 ? wr : __builtin_amdgcn_alignbyte(wr, wc, j + 1);   // bytes j+1 .. j+4
-        hs[j] = (int)__builtin_amdgcn_udot4(B, kWB, __builtin_amdgcn_udot4(A, kWA, 0u, false), false);
-    }
+    const uint32_t e = __builtin_amdgcn_perm(wr, wl, 0x05040302u);
+    hs[0] = __builtin_amdgcn_udot4(wc, 0x12223137u, __builtin_amdgcn_udot4(wl, 0x31221200u, bias, false), false);
+    hs[1] = __builtin_amdgcn_udot4(wc, 0x22313731u, __builtin_amdgcn_udot4(e, 0x00122212u, bias, false), false);
+    hs[2] = __builtin_amdgcn_udot4(wc, 0x31373122u, __builtin_amdgcn_udot4(e, 0x12221200u, bias, false), false);
+    hs[3] = __builtin_amdgcn_udot4(wc, 0x37312212u, __builtin_amdgcn_udot4(wr, 0x00122231u, bias, false), false);
+}
+// kBlurBias in a vector register the compiler cannot see through (one per
+// kernel, ahead of the rows): as a known constant it would be a second
+// scalar operand of every v_dot4, which takes one, or a move per use.
+__device__ inline uint32_t blur_bias()
+{
+    uint32_t b = kBlurBias;
+    asm("" : "+v"(b));
+    return b;
 }
 
 // cvRound of a float (SSE2 cvtsd2si, round half to even).

@@ -1946,12 +1946,15 @@ typedef float orbx_f2 __attribute__((ext_vector_type(2)));
 
 // Horizontal pass of one dword (4 pixels; wl / wr: its left / right
 // neighbours): the four row sums as two packed float pairs.
-__device__ __forceinline__ void blur_hrow(uint32_t wl, uint32_t wc, uint32_t wr, orbx_f2 (&o)[2])
+// bias: blur_bias().  The sums arrive as the floats 2^23 + h; one packed
+// subtraction of 2^23 per pair (exact) leaves the floats (float)h.
+__device__ __forceinline__ void blur_hrow(uint32_t wl, uint32_t wc, uint32_t wr, uint32_t bias, orbx_f2 (&o)[2])
 {
-    int hs[4];
-    blur_hsum_w(wl, wc, wr, hs);
-    o[0] = orbx_f2{(float)hs[0], (float)hs[1]};
-    o[1] = orbx_f2{(float)hs[2], (float)hs[3]};
+    uint32_t hs[4];
+    blur_hsum_w(wl, wc, wr, bias, hs);
+    const orbx_f2 kOff = {8388608.0f, 8388608.0f};
+    o[0] = orbx_f2{__uint_as_float(hs[0]), __uint_as_float(hs[1])} - kOff;
+    o[1] = orbx_f2{__uint_as_float(hs[2]), __uint_as_float(hs[3])} - kOff;
 }
 
 // Vertical pass of one dword over the 7 rows of horizontal sums R, in packed
@@ -2058,7 +2061,8 @@ __device__ __forceinline__ void blur_block(const ExtractArgs& a, const int4* til
             any_tail = any_tail || tail_col[j];
         }
         orbx_f2 R[7][2];
-        auto hrow = [&](uint32_t c, orbx_f2 (&o)[2]) { blur_hrow(left(c), c, right(c), o); };
+        const uint32_t bias = blur_bias();
+        auto hrow = [&](uint32_t c, orbx_f2 (&o)[2]) { blur_hrow(left(c), c, right(c), bias, o); };
         uint32_t C[3];   // raw centre words of rows y, y+1, y+2 (loaded as rows y'+3 earlier)
         {
             uint32_t w0[6];
@@ -2258,6 +2262,7 @@ __device__ __forceinline__ void describe_blur_window(uint8_t* win, int X, int Y,
     }
     const int yi0 = Y - kBrR + j0 - kEdge;   // level row of the strip's first output row
     uint32_t outw[kWinStripRows];
+    const uint32_t bias = blur_bias();
     // tail: some lane of the wave has a tail column (rare: a keypoint within
     // 18 columns of the right edge of a level whose width is not vectorised
     // to the end); the common instance carries no tail arithmetic
@@ -2274,7 +2279,7 @@ __device__ __forceinline__ void describe_blur_window(uint8_t* win, int X, int Y,
         auto hrow = [&](int r, orbx_f2 (&o)[2]) {
             const uint32_t l = w[0], c = w[1], rr = w[2];
             if (r + 1 <= kWinStripRows + 5) ldrow(r + 1);
-            blur_hrow(l, c, rr, o);
+            blur_hrow(l, c, rr, bias, o);
             __builtin_amdgcn_sched_barrier(0);
             return c;
         };
