@@ -61,8 +61,12 @@ extern "C" {
  *      orbx_pnp_ransac_batch, orbx_dev_pnp_candidates); additions only.
  *  11: the Sim3 optimisation of loop closing (orbx_sim3_opt_query,
  *      orbx_optimize_sim3, orbx_optimize_sim3_batch, orbx_dev_optimize_sim3);
+ *      additions only.
+ *  12: the keyframe database in HBM (orbx_kfdb_create / destroy / clear /
+ *      size, orbx_kfdb_add, orbx_kfdb_add_slot, orbx_kfdb_erase,
+ *      orbx_kfdb_set_neighbours, orbx_kfdb_query, orbx_kfdb_score);
  *      additions only. */
-#define ORBX_ABI_VERSION 11
+#define ORBX_ABI_VERSION 12
 int orbx_abi_version(void);
 
 #define ORBX_OK               0
@@ -1272,6 +1276,112 @@ int orbx_dev_pnp_candidates(orbx_ctx* ctx, int slot, int n, const orbx_bow_view*
                             const float* cam, const float* sigma2, int nlevels, float nnratio, int check_ori,
                             int min_matches, int32_t* const* matches_f, int cap, int* n_matches, int* discarded,
                             orbx_pnp_query* out);
+
+/* KeyFrameDatabase (src/KeyFrameDatabase.cc): the BowVectors of the map's
+ * keyframes in HBM, and DetectRelocalisationCandidates (:198-308) /
+ * DetectLoopCandidates (:75-196) as one call per query, the latter with
+ * DetectLoop's reference score (src/LoopClosing.cc:119-139) in front.  The
+ * result is the reference's vector: the same keyframes in the same order.
+ *
+ * Members are named by the caller's ids in [0, capacity) (KeyFrame::mnId as it
+ * is; nothing is renumbered).  capacity is at most ORBX_KFDB_MAX_MEMBERS and
+ * max_words (the longest BowVector of a member or a query) at most
+ * ORBX_KFDB_MAX_WORDS; above either orbx_kfdb_create returns
+ * ORBX_ERR_UNSUPPORTED (the select kernel orders the sharing list in one
+ * workgroup's LDS; the scan kernel keeps the query there).  A database
+ * belongs to the device of the context it was created with and is used with
+ * contexts of that device, one thread at a time.
+ *
+ * The inverted file's list order is kept as an add counter per database:
+ * lKFsSharingWords is ordered by (smallest common word, add order), erase
+ * keeps the others' order and an id added again goes to the back.  The counter
+ * holds 2^32 - 1 adds between two orbx_kfdb_clear calls (ORBX_ERR_UNSUPPORTED
+ * after).
+ *
+ * KeyFrame::mRelocScore is kept per member across relocalisation queries, as
+ * the reference's field is: written for the members that pass a query's word
+ * gate, read for a neighbour that shares a word but failed it.  The reference
+ * never initialises the field (src/KeyFrame.cc:33), so its first read there
+ * is indeterminate; here it is 0.0f from orbx_kfdb_add / _add_slot on.  The
+ * loop query's mLoopScore is only ever read after this query wrote it, so it
+ * keeps no state. */
+#define ORBX_KFDB_MAX_MEMBERS 8192
+#define ORBX_KFDB_MAX_WORDS   4096
+#define ORBX_KFDB_NEIGHBOURS  10     /* GetBestCovisibilityKeyFrames(10) */
+#define ORBX_KFDB_RELOC 0
+#define ORBX_KFDB_LOOP  1
+typedef struct orbx_kfdb orbx_kfdb;
+int orbx_kfdb_create(orbx_ctx* ctx, int capacity, int max_words, orbx_kfdb** out);
+void orbx_kfdb_destroy(orbx_kfdb* db);
+/* KeyFrameDatabase::clear: no members, every neighbour row and score reset. */
+int orbx_kfdb_clear(orbx_ctx* ctx, orbx_kfdb* db);
+int orbx_kfdb_size(const orbx_kfdb* db);   /* members; ORBX_ERR_ARG for NULL */
+/* KeyFrameDatabase::add from host arrays: words strictly ascending (a
+ * BowVector's iteration order), values finite.  ORBX_ERR_ARG: id outside
+ * [0, capacity) or in use, unordered words, a value that is not finite;
+ * ORBX_ERR_CAPACITY: n_words > max_words.  The arrays are free at return. */
+int orbx_kfdb_add(orbx_ctx* ctx, orbx_kfdb* db, int id, int n_words, const uint32_t* words, const double* values);
+/* add of the BowVector orbx_dev_compute_bow left in `slot`: a device-to-device
+ * copy queued on the context's stream, the word count read on the device, no
+ * synchronisation.  ORBX_ERR_ARG: a slot without valid BoW; ORBX_ERR_CAPACITY:
+ * max_words below the context's nfeatures (the most words a slot can hold). */
+int orbx_kfdb_add_slot(orbx_ctx* ctx, orbx_kfdb* db, int id, int slot);
+/* KeyFrameDatabase::erase: frees the id, clears the member's neighbour row
+ * and its relocalisation score.  ORBX_ERR_ARG: not a member. */
+int orbx_kfdb_erase(orbx_ctx* ctx, orbx_kfdb* db, int id);
+/* The rows GetBestCovisibilityKeyFrames(10) returns for members ids[0, n)
+ * (call it where KeyFrame::UpdateBestCovisibles runs): neigh is n x 10 member
+ * ids in that order, padded with -1; stored in HBM.  An entry that does not
+ * name a member when a query runs is skipped by that query.  ORBX_ERR_ARG:
+ * an id of ids that is not a member. */
+int orbx_kfdb_set_neighbours(orbx_ctx* ctx, orbx_kfdb* db, int n, const int32_t* ids, const int32_t* neigh);
+
+typedef struct {
+    /* in */
+    int mode;                             /* ORBX_KFDB_RELOC or ORBX_KFDB_LOOP                  */
+    int slot;                             /* >= 0: the query is the BowVector of this slot, read
+                                             in HBM (max_words >= nfeatures, as for add_slot);
+                                             -1: the host arrays below                          */
+    int n_words; const uint32_t* words; const double* values;   /* as for orbx_kfdb_add        */
+    /* loop only (ignored for relocalisation) */
+    float min_score;                      /* DetectLoop's start value (1), or DetectLoopCandidates'
+                                             minScore itself with n_ref = 0                     */
+    int n_ref; const int32_t* ref;        /* GetVectorCovisibleKeyFrames: min_score_used is the
+                                             minimum of min_score and the scores against these  */
+    int n_exclude; const int32_t* exclude;   /* GetConnectedKeyFrames: never listed             */
+    /* out */
+    int32_t* candidates; int cap;         /* the returned vector, in order                      */
+    int n_candidates;                     /* its size (ORBX_ERR_CAPACITY when above cap; cap
+                                             entries are written then)                          */
+    float min_score_used;                 /* loop: minScore; relocalisation: 0                  */
+    int max_common_words;                 /* maxCommonWords (0: nothing shares a word)          */
+    int n_sharing;                        /* lKFsSharingWords.size()                            */
+    int n_scored;                         /* nscores                                            */
+    /* optional taps per member id, capacity entries each (NULL: not read back) */
+    int32_t* tap_words;                   /* mnRelocWords / mnLoopWords of a listed member, else 0 */
+    float* tap_score;                     /* relocalisation: mRelocScore after the query; loop:
+                                             mLoopScore of a member that passed the gate, else 0 */
+    float* tap_acc; int32_t* tap_best;    /* accScore and pBestKF of a member of lScoreAndMatch,
+                                             else 0 and -1                                      */
+    int32_t* tap_pos;                     /* position in lKFsSharingWords, else -1              */
+} orbx_kfdb_query_args;
+
+/* One query: one upload (the query's arrays and the two lists; the lists alone
+ * for a slot query), the scan and select kernels, one read-back (the header
+ * and cap candidates; the taps only when asked for).  ref and exclude ids lie
+ * in [0, capacity) (ORBX_ERR_ARG otherwise); one that is not a member is
+ * skipped, as DetectLoop skips a bad keyframe.  An empty database, an empty
+ * query and a query that shares no word return ORBX_OK with n_candidates = 0.
+ * ORBX_ERR_ARG: a null pointer, another mode, a slot without valid BoW, host
+ * words out of order, cap < 0; ORBX_ERR_CAPACITY: n_words > max_words, a slot
+ * query with max_words below nfeatures, n_candidates > cap. */
+int orbx_kfdb_query(orbx_ctx* ctx, orbx_kfdb* db, orbx_kfdb_query_args* q);
+/* mpVoc->score(query, member ids[k]) as the float the reference stores, for n
+ * named members (DetectLoop's loop on its own): the scan kernel alone.  The
+ * query is given as in orbx_kfdb_query (slot >= 0, or -1 and host arrays).
+ * ORBX_ERR_ARG: an id that is not a member. */
+int orbx_kfdb_score(orbx_ctx* ctx, orbx_kfdb* db, int slot, int n_words, const uint32_t* words, const double* values,
+                    int n, const int32_t* ids, float* scores);
 
 /* ------------------------------------------------------------------------ */
 /* C. Local bundle adjustment                                                */

@@ -654,6 +654,16 @@ def _declare(L):
         "orbx_optimize_sim3": ([vp, vp], i),
         "orbx_optimize_sim3_batch": ([vp, i, vp], i),
         "orbx_dev_optimize_sim3": ([vp, i, vp, vp, i, vp, vp, vp], i),
+        "orbx_kfdb_create": ([vp, i, i, ctypes.POINTER(vp)], i),
+        "orbx_kfdb_destroy": ([vp], None),
+        "orbx_kfdb_clear": ([vp, vp], i),
+        "orbx_kfdb_size": ([vp], i),
+        "orbx_kfdb_add": ([vp, vp, i, i, vp, vp], i),
+        "orbx_kfdb_add_slot": ([vp, vp, i, i], i),
+        "orbx_kfdb_erase": ([vp, vp, i], i),
+        "orbx_kfdb_set_neighbours": ([vp, vp, i, vp, vp], i),
+        "orbx_kfdb_query": ([vp, vp, vp], i),
+        "orbx_kfdb_score": ([vp, vp, i, i, vp, vp, i, vp, vp], i),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(L, name)
@@ -1395,6 +1405,143 @@ class Vocabulary:
             self.close()
         except Exception:
             pass
+
+
+class KfdbQuery(ctypes.Structure):
+    """orbx_kfdb_query_args (include/orbx.h)."""
+    _fields_ = [("mode", ctypes.c_int), ("slot", ctypes.c_int), ("n_words", ctypes.c_int),
+                ("words", ctypes.c_void_p), ("values", ctypes.c_void_p), ("min_score", ctypes.c_float),
+                ("n_ref", ctypes.c_int), ("ref", ctypes.c_void_p), ("n_exclude", ctypes.c_int),
+                ("exclude", ctypes.c_void_p), ("candidates", ctypes.c_void_p), ("cap", ctypes.c_int),
+                ("n_candidates", ctypes.c_int), ("min_score_used", ctypes.c_float),
+                ("max_common_words", ctypes.c_int), ("n_sharing", ctypes.c_int), ("n_scored", ctypes.c_int),
+                ("tap_words", ctypes.c_void_p), ("tap_score", ctypes.c_void_p), ("tap_acc", ctypes.c_void_p),
+                ("tap_best", ctypes.c_void_p), ("tap_pos", ctypes.c_void_p)]
+
+
+KFDB_RELOC, KFDB_LOOP = 0, 1
+KFDB_MAX_MEMBERS, KFDB_MAX_WORDS, KFDB_NEIGHBOURS = 8192, 4096, 10
+_KFDB_TAPS = (("words", np.int32), ("score", np.float32), ("acc", np.float32), ("best", np.int32), ("pos", np.int32))
+
+
+class KeyFrameDatabase:
+    """ORB_SLAM::KeyFrameDatabase in HBM (orbx_kfdb_*): members are named by
+    the caller's ids in [0, capacity) (KeyFrame::mnId).  A query is a slot of
+    the context (an int: the BowVector compute_bow left there) or a
+    (words, values) pair of arrays, words ascending."""
+
+    def __init__(self, ctx, capacity, max_words):
+        self._ctx = ctx
+        self.capacity, self.max_words = int(capacity), int(max_words)
+        self._h = ctypes.c_void_p()
+        _check(lib().orbx_kfdb_create(ctx.handle, capacity, max_words, ctypes.byref(self._h)), "orbx_kfdb_create")
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if self._h:
+            lib().orbx_kfdb_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return lib().orbx_kfdb_size(self._h)
+
+    def clear(self):
+        _check(lib().orbx_kfdb_clear(self._ctx.handle, self._h), "orbx_kfdb_clear")
+
+    @staticmethod
+    def _bow(bow):
+        w = np.ascontiguousarray(bow[0], np.uint32).reshape(-1)
+        v = np.ascontiguousarray(bow[1], np.float64).reshape(-1)
+        if len(w) != len(v):
+            raise ValueError("a BowVector has as many values as words")
+        return w, v
+
+    def add(self, kf_id, words, values):
+        """KeyFrameDatabase::add from host arrays."""
+        w, v = self._bow((words, values))
+        _check(lib().orbx_kfdb_add(self._ctx.handle, self._h, int(kf_id), len(w), _ptr(w), _ptr(v)), "orbx_kfdb_add")
+
+    def add_slot(self, kf_id, slot):
+        """add of the BowVector compute_bow left in `slot` (device to device)."""
+        _check(lib().orbx_kfdb_add_slot(self._ctx.handle, self._h, int(kf_id), int(slot)), "orbx_kfdb_add_slot")
+
+    def erase(self, kf_id):
+        _check(lib().orbx_kfdb_erase(self._ctx.handle, self._h, int(kf_id)), "orbx_kfdb_erase")
+
+    def set_neighbours(self, ids, neigh):
+        """GetBestCovisibilityKeyFrames(10) of members `ids`: a list of id
+        lists (at most 10 each) or an n x 10 array padded with -1."""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        rows = np.full((len(ids), KFDB_NEIGHBOURS), -1, np.int32)
+        for k, row in enumerate(neigh):
+            row = np.asarray(row, np.int32).reshape(-1)
+            if len(row) > KFDB_NEIGHBOURS:
+                raise ValueError("a neighbour row holds at most 10 ids")
+            rows[k, :len(row)] = row
+        _check(lib().orbx_kfdb_set_neighbours(self._ctx.handle, self._h, len(ids), _ptr(ids), _ptr(rows)),
+               "orbx_kfdb_set_neighbours")
+
+    def _query_bow(self, query):
+        if isinstance(query, (int, np.integer)):
+            return int(query), 0, None, None
+        w, v = self._bow(query)
+        return -1, len(w), w, v
+
+    def score(self, query, ids):
+        """mpVoc->score(query, member) as float32 for the named members."""
+        slot, n, w, v = self._query_bow(query)
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        out = np.zeros(len(ids), np.float32)
+        _check(lib().orbx_kfdb_score(self._ctx.handle, self._h, slot, n, _ptr(w) if n else None,
+                                     _ptr(v) if n else None, len(ids), _ptr(ids), _ptr(out)), "orbx_kfdb_score")
+        return out
+
+    def _detect(self, mode, query, min_score, ref, exclude, taps, cap):
+        q = KfdbQuery()
+        q.mode = mode
+        q.slot, q.n_words, w, v = self._query_bow(query)
+        if q.n_words:
+            q.words, q.values = w.ctypes.data, v.ctypes.data
+        ref = np.ascontiguousarray(ref, np.int32).reshape(-1)
+        exclude = np.ascontiguousarray(exclude, np.int32).reshape(-1)
+        q.min_score, q.n_ref, q.n_exclude = float(min_score), len(ref), len(exclude)
+        q.ref, q.exclude = (ref.ctypes.data if len(ref) else None), (exclude.ctypes.data if len(exclude) else None)
+        q.cap = self.capacity if cap is None else int(cap)
+        cand = np.zeros(max(q.cap, 1), np.int32)
+        q.candidates = cand.ctypes.data
+        keep = {}
+        if taps:
+            for name, dt in _KFDB_TAPS:
+                keep[name] = np.zeros(self.capacity, dt)
+                setattr(q, "tap_" + name, keep[name].ctypes.data)
+        _check(lib().orbx_kfdb_query(self._ctx.handle, self._h, ctypes.byref(q)), "orbx_kfdb_query")
+        info = dict(n_candidates=q.n_candidates, min_score_used=np.float32(q.min_score_used),
+                    max_common_words=q.max_common_words, n_sharing=q.n_sharing, n_scored=q.n_scored)
+        info.update(keep)
+        return cand[:q.n_candidates].copy(), info
+
+    def detect_relocalisation_candidates(self, query, taps=False, cap=None, info=False):
+        """DetectRelocalisationCandidates(F): the candidate ids in the
+        reference's order; with taps or info also a dict of the header
+        (max_common_words, n_sharing, n_scored) and the per-id taps."""
+        c, i = self._detect(KFDB_RELOC, query, 0.0, (), (), taps, cap)
+        return (c, i) if (taps or info) else c
+
+    def detect_loop_candidates(self, query, min_score=1.0, ref=(), exclude=(), taps=False, cap=None, info=False):
+        """DetectLoop's minScore over `ref` (GetVectorCovisibleKeyFrames,
+        starting at min_score) and DetectLoopCandidates with `exclude`
+        (GetConnectedKeyFrames)."""
+        c, i = self._detect(KFDB_LOOP, query, min_score, ref, exclude, taps, cap)
+        return (c, i) if (taps or info) else c
 
 
 def describe_levels(w, h, nfeatures=1000, scale_factor=1.2, nlevels=8, fast_th=20):

@@ -495,10 +495,39 @@ int main()
         std::printf("\"pnp_same\": %d, \"pnp_n\": %d, \"pnp_found\": %d, \"pnp_refined\": %d, \"pnp_inliers\": %d, "
                     "\"pnp_iterations\": %d, \"pnp_calls\": %d, \"pnp_pose_error\": %.3g, \"pnp_max_its\": %d, "
                     "\"pnp_find_found\": %d, \"pnp_find_iterations\": %d, \"pnp_find_max_its\": %d, "
-                    "\"pnp_find_best\": %d}\n",
+                    "\"pnp_find_best\": %d, ",
                     pnp_same ? 1 : 0, pq.N, pq.found, pq.refined, pq.n_inliers, pq.iter_done, pnp_ccalls, pnp_err,
                     pq.ransac_max_its == pnp.mRansacMaxIts ? pnp.mRansacMaxIts : -1, pnp2_T.empty() ? 0 : 1,
                     pnp2.mnIterations, pnp2.mRansacMaxIts, pnp2.mnBestInliers);
+        // KeyFrameDatabase: four keyframes added in the order 9, 2, 7, 5, each sharing two of the query's four
+        // words (every score 0.5); the sharing list goes by smallest common word, then add order: 7 5 2 9.
+        // Erased and added again, 7 goes behind 5.  Then LoopClosing::DetectLoop's pair of calls in one: the
+        // covisible 2 and 9 give minScore 0.5, the connected 5 is left out
+        KeyFrameDatabase kfdb(ex.context(), 16, 8);
+        const BowVector kq({10, 20, 30, 40}, {.25, .25, .25, .25});
+        kfdb.add(9, BowVector({30, 40}, {.5, .5}));
+        kfdb.add(2, BowVector({20, 40}, {.5, .5}));
+        kfdb.add(7, BowVector({10, 40}, {.5, .5}));
+        kfdb.add(5, BowVector({10, 30}, {.5, .5}));
+        kfdb.SetBestCovisibles(9, {3});   // 3 is not in the database: skipped
+        const std::vector<int> kf_reloc = kfdb.DetectRelocalisationCandidates(kq);
+        kfdb.erase(7);
+        kfdb.add(7, BowVector({10, 20}, {.5, .5}));
+        const std::vector<int> kf_reloc2 = kfdb.DetectRelocalisationCandidates(kq);
+        const std::vector<int> kf_loop = kfdb.DetectLoopCandidates(kq, std::vector<int>{2, 9}, std::vector<int>{5});
+        const float kf_min = kfdb.mMinScore;
+        const std::vector<int> kf_loop_hi = kfdb.DetectLoopCandidates(kq, 0.75f, std::vector<int>());
+        const std::vector<float> kf_scores = kfdb.score(kq, {5, 9});
+        kfdb.clear();
+        auto digits = [](const std::vector<int>& v) {   // ids below 10, as one decimal number
+            int d = 0;
+            for (int x : v) d = d * 10 + x;
+            return d;
+        };
+        std::printf("\"kfdb_reloc\": %d, \"kfdb_reloc_readded\": %d, \"kfdb_loop\": %d, \"kfdb_min_score\": %.6f, "
+                    "\"kfdb_loop_above\": %zu, \"kfdb_score\": [%.6f, %.6f], \"kfdb_size_after_clear\": %d}\n",
+                    digits(kf_reloc), digits(kf_reloc2), digits(kf_loop), (double)kf_min, kf_loop_hi.size(),
+                    (double)kf_scores[0], (double)kf_scores[1], kfdb.size());
         return 0;
     } catch (const orbx_error& e) {
         std::fprintf(stderr, "%s\n", e.what());

@@ -10,6 +10,7 @@
 //                                                           include/Optimizer.h:42
 //   ORB_SLAM_AMD::Initializer    <- ORB_SLAM::Initializer    include/Initializer.h:33-96
 //                                   (FindHomography + FindFundamental)
+//   ORB_SLAM_AMD::KeyFrameDatabase <- ORB_SLAM::KeyFrameDatabase include/KeyFrameDatabase.h:42-66
 //
 // Error behaviour: the reference has no error codes.  Like the reference, an
 // empty image returns without touching the outputs (src/ORBextractor.cc:
@@ -26,6 +27,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/orbx.h"
@@ -1037,6 +1039,121 @@ private:
     double mRansacProb = 0.99;
     int mMinInliersArg = 8, mMaxIterationsArg = 300, mRansacMinSet = 4;   // the caller's arguments
     float mEpsilonArg = 0.4f, mRansacTh = 5.991f;
+};
+
+// ---------------------------------------------------------------------------
+// KeyFrameDatabase (include/KeyFrameDatabase.h:42-66, src/KeyFrameDatabase.cc)
+// in HBM.  Keyframes are named by KeyFrame::mnId (below `capacity`); where the
+// reference takes a KeyFrame* or Frame* for its mBowVec, this takes a
+// BowVector: the slot the frame is resident in (after orbx_dev_compute_bow) or
+// the map's (word, value) pairs in iteration order.
+// ---------------------------------------------------------------------------
+struct BowVector {
+    int slot = -1;
+    std::vector<uint32_t> words;
+    std::vector<double> values;
+    BowVector() = default;
+    explicit BowVector(int device_slot) : slot(device_slot) {}
+    BowVector(std::vector<uint32_t> w, std::vector<double> v) : words(std::move(w)), values(std::move(v)) {}
+};
+
+class KeyFrameDatabase {
+public:
+    KeyFrameDatabase(orbx_ctx* ctx, int capacity, int maxWords) : ctx_(ctx), capacity_(capacity)
+    {
+        if (orbx_abi_version() != ORBX_ABI_VERSION) throw orbx_error(ORBX_ERR_UNSUPPORTED, "orbx_abi_version");
+        check(orbx_kfdb_create(ctx, capacity, maxWords, &db_), "KeyFrameDatabase");
+    }
+    ~KeyFrameDatabase() { orbx_kfdb_destroy(db_); }
+    KeyFrameDatabase(const KeyFrameDatabase&) = delete;
+    KeyFrameDatabase& operator=(const KeyFrameDatabase&) = delete;
+
+    // void add(KeyFrame* pKF) (:39-45)
+    void add(int mnId, const BowVector& bow)
+    {
+        if (bow.slot >= 0) check(orbx_kfdb_add_slot(ctx_, db_, mnId, bow.slot), "KeyFrameDatabase::add");
+        else
+            check(orbx_kfdb_add(ctx_, db_, mnId, (int)bow.words.size(), bow.words.data(), bow.values.data()),
+                  "KeyFrameDatabase::add");
+    }
+    // void erase(KeyFrame* pKF) (:47-66)
+    void erase(int mnId) { check(orbx_kfdb_erase(ctx_, db_, mnId), "KeyFrameDatabase::erase"); }
+    // void clear() (:68-72)
+    void clear() { check(orbx_kfdb_clear(ctx_, db_), "KeyFrameDatabase::clear"); }
+    int size() const { return orbx_kfdb_size(db_); }
+
+    // Where KeyFrame::UpdateBestCovisibles runs (src/KeyFrame.cc:141-160): what
+    // GetBestCovisibilityKeyFrames(10) returns for keyframe mnId from now on.
+    void SetBestCovisibles(int mnId, const std::vector<int>& vpOrdered)
+    {
+        int32_t row[ORBX_KFDB_NEIGHBOURS];
+        for (int k = 0; k < ORBX_KFDB_NEIGHBOURS; k++) row[k] = k < (int)vpOrdered.size() ? vpOrdered[k] : -1;
+        const int32_t id = mnId;
+        check(orbx_kfdb_set_neighbours(ctx_, db_, 1, &id, row), "KeyFrameDatabase::SetBestCovisibles");
+    }
+
+    // vector<KeyFrame*> DetectLoopCandidates(KeyFrame* pKF, float minScore) (:75-196);
+    // spConnectedKeyFrames is pKF->GetConnectedKeyFrames()
+    std::vector<int> DetectLoopCandidates(const BowVector& pKF, float minScore,
+                                          const std::vector<int>& spConnectedKeyFrames)
+    {
+        return run(ORBX_KFDB_LOOP, pKF, minScore, std::vector<int>(), spConnectedKeyFrames);
+    }
+    // LoopClosing::DetectLoop's minScore loop over vpCovisible =
+    // GetVectorCovisibleKeyFrames() (src/LoopClosing.cc:122-136) and the call
+    // above, in one device call; mMinScore holds the score used.
+    std::vector<int> DetectLoopCandidates(const BowVector& pKF, const std::vector<int>& vpCovisible,
+                                          const std::vector<int>& spConnectedKeyFrames)
+    {
+        return run(ORBX_KFDB_LOOP, pKF, 1.0f, vpCovisible, spConnectedKeyFrames);
+    }
+    // vector<KeyFrame*> DetectRelocalisationCandidates(Frame* F) (:198-308)
+    std::vector<int> DetectRelocalisationCandidates(const BowVector& F)
+    {
+        return run(ORBX_KFDB_RELOC, F, 0.f, std::vector<int>(), std::vector<int>());
+    }
+    // mpVoc->score(query, keyframe) for the named keyframes
+    std::vector<float> score(const BowVector& q, const std::vector<int>& ids)
+    {
+        std::vector<float> s(ids.size());
+        const std::vector<int32_t> i32(ids.begin(), ids.end());
+        check(orbx_kfdb_score(ctx_, db_, q.slot >= 0 ? q.slot : -1, (int)q.words.size(), q.words.data(), q.values.data(),
+                              (int)ids.size(), i32.data(), s.data()),
+              "KeyFrameDatabase::score");
+        return s;
+    }
+
+    float mMinScore = 0.f;                       // the last loop query's minScore
+    int mMaxCommonWords = 0, mnScores = 0;       // the last query's maxCommonWords and nscores
+
+private:
+    std::vector<int> run(int mode, const BowVector& b, float minScore, const std::vector<int>& ref,
+                         const std::vector<int>& exclude)
+    {
+        const std::vector<int32_t> r32(ref.begin(), ref.end()), e32(exclude.begin(), exclude.end());
+        std::vector<int32_t> cand((size_t)capacity_);
+        orbx_kfdb_query_args q{};
+        q.mode = mode;
+        q.slot = b.slot >= 0 ? b.slot : -1;
+        q.n_words = (int)b.words.size();
+        q.words = b.words.data();
+        q.values = b.values.data();
+        q.min_score = minScore;
+        q.n_ref = (int)r32.size();
+        q.ref = r32.data();
+        q.n_exclude = (int)e32.size();
+        q.exclude = e32.data();
+        q.candidates = cand.data();
+        q.cap = capacity_;
+        check(orbx_kfdb_query(ctx_, db_, &q), "KeyFrameDatabase::Detect");
+        mMinScore = q.min_score_used;
+        mMaxCommonWords = q.max_common_words;
+        mnScores = q.n_scored;
+        return std::vector<int>(cand.begin(), cand.begin() + q.n_candidates);
+    }
+    orbx_ctx* ctx_;
+    orbx_kfdb* db_ = nullptr;
+    int capacity_;
 };
 
 }  // namespace ORB_SLAM_AMD
