@@ -1392,7 +1392,9 @@ int orbx_kfdb_score(orbx_ctx* ctx, orbx_kfdb* db, int slot, int n_words, const u
  * + translation; ids are the g2o vertex ids (KF mnId; points mnId+maxKFid+1)
  * which fix the Hessian ordering (sparse_optimizer.cpp:166-190, 482-487).
  * Edges are EdgeSE3ProjectXYZ in insertion order (points in local-list order,
- * observations in the caller's map<KeyFrame*,size_t> order). */
+ * observations in the caller's map<KeyFrame*,size_t> order).  huber_delta
+ * and chi2_threshold are per problem: in a batch (orbx_lba_solve_batch,
+ * orbx_lba_stage) every problem is solved and gated with its own pair. */
 typedef struct {
     int n_poses, n_points, n_edges;
     double* pose_q;             /* [n_poses][4] x,y,z,w   (in/out)           */

@@ -134,6 +134,7 @@ struct LbaDev {
     const long long* r_pose_id;
     const long long* r_point_id;
     double huber_delta;
+    double chi2_threshold;         // the outlier passes' chi2 gate (per problem, like huber_delta)
     // LM state
     double lambda, ni, current_chi, last_chi, chi2_initial;
     double hmax, bmax;             // this linearisation's max Hpp diagonal and max |b| (fixed-point scales)
@@ -2081,7 +2082,7 @@ __global__ __launch_bounds__(kLbaThreads) void k_lba_split(LbaDev* probs, int it
 // computeActiveErrors (P.err: the last trial's, accepted or not).
 template <class Rec>
 __global__ __launch_bounds__(256) void k_lba_outliers(LbaDev* probs, int* nobs_all, uint8_t* status_all,
-                                                      uint8_t* bad_all, int pass, double thr, int* n_out,
+                                                      uint8_t* bad_all, int pass, int* n_out,
                                                       const long long* offs, LbaStatRec* stat, unsigned* split_bar,
                                                       int* split_failed)
 {
@@ -2091,6 +2092,7 @@ __global__ __launch_bounds__(256) void k_lba_outliers(LbaDev* probs, int* nobs_a
     int* nobs = nobs_all + po;
     uint8_t* st = status_all + eo;
     uint8_t* bad = bad_all + po;
+    const double thr = P.chi2_threshold;
     if (threadIdx.x == 0) s_cnt = 0;
     LBA_SYNC();
     int cnt = 0;
@@ -2589,7 +2591,6 @@ struct LbaPlan {
     size_t result_bytes = 0, base_bytes = 0, o_all_nobs = 0, o_all_st = 0, o_all_bad = 0, o_offs = 0, o_nout = 0;
     size_t o_stats = 0, o_failed = 0;   // LbaStatRec [2][P], k_lba_split's failed flag: the end of the readback block
     size_t o_devs = 0, o_devs1 = 0, staged_end = 0, o_err = 0, err_bytes = 0, dev_end = 0;
-    double chi2_threshold = 0;
 };
 
 // Plans the layout of P problems at device base d (nullptr: plan only, to
@@ -2632,7 +2633,6 @@ static int lba_plan_stage(orbx_ctx* ctx, int P, const orbx_ba_problem* probs, ui
     const size_t rec_bytes = float_rec ? sizeof(EdgeRecF) : sizeof(EdgeRecD);
     L.P = P;
     L.d = d;
-    L.chi2_threshold = P > 0 ? probs[0].chi2_threshold : 0;
     L.pl.resize(P);
     L.offs.assign(3 * (size_t)P, 0);
     L.n_poses.resize(P);
@@ -2823,6 +2823,7 @@ static int lba_plan_stage(orbx_ctx* ctx, int P, const orbx_ba_problem* probs, ui
             D.r_pose_id = reinterpret_cast<const long long*>(d + q[5]);
             D.r_point_id = reinterpret_cast<const long long*>(d + q[6]);
             D.huber_delta = p.huber_delta;
+            D.chi2_threshold = p.chi2_threshold;
             D.status = kRunning;
             D.ni = 2;
         };
@@ -3027,7 +3028,7 @@ static int lba_launch_t(orbx_ctx* ctx, const LbaPlan& L, int iters0, int iters1,
         timer_begin(ctx, "lba_outliers");
         hipLaunchKernelGGL(k_lba_outliers<Rec>, dim3(P, G > 1 ? 16 : 1), dim3(256), 0, ctx->stream, dd,
                            reinterpret_cast<int*>(d + L.o_all_nobs), d + L.o_all_st, d + L.o_all_bad, pass + 1,
-                           L.chi2_threshold, n_out + pass * P, reinterpret_cast<const long long*>(d + L.o_offs),
+                           n_out + pass * P, reinterpret_cast<const long long*>(d + L.o_offs),
                            reinterpret_cast<LbaStatRec*>(d + L.o_stats) + pass * P, X.bar, failed);
         timer_end(ctx, "lba_outliers");
         ORBX_HIP_CHECK(hipGetLastError());

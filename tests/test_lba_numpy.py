@@ -163,6 +163,8 @@ class Graph:
         pi = {k: 6 * i for i, k in enumerate(poses)}
         li = {p: 6 * len(poses) + 3 * i for i, p in enumerate(points)}
         n = 6 * len(poses) + 3 * len(points)
+        if n == 0:   # no active vertex: g2o's optimize() returns before its first iteration
+            return 0, 0
         lam = ni = 0.0
         nbad = 0
         trials = 0
@@ -241,6 +243,7 @@ def local_ba(prob, i0=5, i1=10):
     nobs = prob["point_nobs"].astype(np.int64).copy()
     bad = np.zeros(len(nobs), np.uint8)
     status = np.zeros(ne, np.uint8)
+    thr = prob.get("chi2_threshold", CHI2_TH)
     stats = []
     active = list(range(ne))
     for pss, iters in ((1, i0), (2, i1)):
@@ -249,7 +252,7 @@ def local_ba(prob, i0=5, i1=10):
             p = g.ep[e]
             if bad[p]:
                 continue
-            if g.chi2(e) > CHI2_TH or not g.pc(e)[2] > 0.0:
+            if g.chi2(e) > thr or not g.pc(e)[2] > 0.0:
                 nobs[p] -= 1
                 if nobs[p] <= 2:
                     bad[p] = 1
