@@ -619,6 +619,7 @@ def _declare(L):
         "orbx_debug_describe_patch": ([vp, i, i, i, i, vp], i),
         "orbx_debug_describe_moments": ([vp, i, i, i, i, vp], i),
         "orbx_debug_level0_direct": ([vp], i),
+        "orbx_debug_fill_pyramid": ([vp, i, i, i], i),
         "orbx_debug_write_features": ([vp, i, vp, vp, i], i),
         "orbx_debug_fast_instance": ([vp, vp], i),
         "orbx_debug_fast_lists": ([vp, i, vp, i, vp, i, vp], i),
@@ -902,6 +903,14 @@ class Context:
         if r < 0:
             raise OrbxError(r, "orbx_debug_level0_direct")
         return bool(r)
+
+    def fill_pyramid(self, first_slot, count, byte):
+        """Debug (orbx_debug_fill_pyramid): fills the whole raw-pyramid area of
+        slots [first_slot, first_slot + count) with one byte value, after all
+        pending work.  Tests poison the areas with it: the batch extraction
+        writes level interiors only and must not depend on any other byte."""
+        _check(lib().orbx_debug_fill_pyramid(self._h, int(first_slot), int(count), int(byte)),
+               "orbx_debug_fill_pyramid")
 
     def fast_instance(self):
         """The FAST kernel instance of the last extraction: (tile pitch, 0 for

@@ -617,7 +617,9 @@ int orbx_dev_read_level(orbx_ctx* ctx, int slot, int level, int blurred, uint8_t
     const int f = slot;   // work buffers are per slot
     if (f < 0 || f >= ctx->slots) return ORBX_ERR_ARG;
     ctx_enter(ctx);
-    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    // every stream's work on the slot: the parts of a split batch run their
+    // pyramids on streams that are never joined back to the context stream
+    ORBX_HIP_CHECK(hipDeviceSynchronize());
     const LevelGeom& L = ctx->geom.levels[level];
     *pw = L.pw;
     *ph = L.ph;
@@ -625,15 +627,18 @@ int orbx_dev_read_level(orbx_ctx* ctx, int slot, int level, int blurred, uint8_t
     // The extraction path keeps no blurred pyramid (k_describe blurs its own
     // patches): the slot's raw pyramid is blurred now, by the whole-level
     // k_blur, into the one-frame pyr_blur.
-    // Level 0's padded copy is not on the extraction path either (direct
-    // mode reads the frame store): it is rebuilt now from the slot's current
-    // frame, here for the raw level and inside launch_blur_slot.
+    // Nor does it keep the padded levels whole.  Level 0's padded copy is not
+    // written in direct mode (the kernels read the frame store), and the
+    // batch resize writes the interiors of levels >= 1 only: level 0 is
+    // rebuilt now from the slot's current frame and the borders of the other
+    // levels from their interiors, here for the raw level and inside
+    // launch_blur_slot.
     if (blurred) {
         const int r = launch_blur_slot(ctx, f);
         if (r != ORBX_OK) return r;
         ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    } else if (level == 0) {
-        const int r = launch_level0_slot(ctx, f);
+    } else {
+        const int r = level == 0 ? launch_level0_slot(ctx, f) : launch_borders_slot(ctx, f);
         if (r != ORBX_OK) return r;
         ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     }

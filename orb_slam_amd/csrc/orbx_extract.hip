@@ -4,7 +4,16 @@
 //   k_pyr_level0   copyMakeBorder(REFLECT_101) of the input   (:814); not
 //                  launched for frames of w % 16 == 0, whose level 0 the
 //                  kernels below read from the frame store (level_src)
-//   k_pyr_resize   resize INTER_LINEAR + border, level l      (:800, :806)
+//   k_pyr_resize_lds resize INTER_LINEAR, level l              (:800); level
+//                  interiors only: no kernel of the batch path reads a
+//                  border (k_describe stages the windows that leave a level
+//                  from their REFLECT_101 sources inside it)
+//   k_pyr_resize   the same + border (:806), per-pixel gathers: levels whose
+//                  staged strip does not fit LDS
+//   k_pyr_cascade  the whole raw pyramid with borders in one launch
+//                  (orbx_extract's single frame)
+//   k_pyr_borders  the borders of levels >= 1 of one slot (:806), on demand
+//                  for orbx_dev_read_level and k_blur
 //   k_fast_cells   FAST-9/16 + cell-local NMS + threshold-7
 //                  fallback + raster-order compaction, one
 //                  workgroup per grid cell                    (:599-614)
@@ -301,22 +310,31 @@ __global__ __launch_bounds__(256) void k_pyr_resize(ExtractArgs a, int level)
     }
 }
 
-// The same resize with the strip's source rows staged in LDS: one
-// workgroup per (strip of kResRows output rows, frame).  The previous
-// level's rows [lo, hi] feeding the strip are copied with 16-byte loads
-// (padded columns 0 .. kEdge + P.w), together with the level's column and
-// row tables; every output pixel then reads its 2x2 sources from LDS.
+// The same resize with the strip's source rows staged in LDS, for the
+// level's interior only: one workgroup per (strip of kResRows interior rows,
+// frame), rows 1:1 with the row table.  Nothing on the batch path reads a
+// level's border (the next level's resize stages interior sources, FAST and
+// Harris cells lie inside the level, k_describe reflects the windows that
+// leave it), so no border row, border word or row padding is computed or
+// stored here: launch_borders_slot fills them for the readers of a padded
+// level.  The previous level's interior rows [lo, hi] feeding the strip are
+// copied with 16-byte loads from their first interior byte (columns
+// 0 .. P.w - 1 and up to 15 bytes behind them), together with the level's
+// column and row tables; every output pixel then reads its 2x2 sources from
+// LDS.  The bytes behind column P.w - 1 belong to the parent's border or
+// padding (allocated, maybe never written; the frame's next row for the
+// direct level 0, whose width is a multiple of 16, so none is staged there).
+// Only the second tap of the HResizeLinear tail columns reads one of them
+// (sx0 = P.w - 1, tap at +1), with weight a1 = 0: the value never reaches a
+// result.  Every other tap has sx0 + 1 <= P.w - 1 (resize_tables).
 // The host guarantees hi - lo + 1 <= L.res_span (computed from the tables).
 // The level's and its parent's geometry, passed by value: no dependent
 // table read before the staging loads.
 struct ResizeLevel {
     long long off, poff;                 // level / parent offsets in a frame's pyramid
-    int stride, pstride, w, h, pw, ph, ph_parent_h, nvec, span, strip_off, row_off, col_off;
+    int stride, pstride, w, h, ph_parent_h, nvec, span, strip_off, row_off, col_off;
     int packed;                          // every interior word's taps lie within 8 bytes (the packed form applies)
-    // the parent's level index and the left pad of its staged rows: kEdge
-    // (padded columns 0 .. kEdge + P.w), or 0 where the parent is the frame
-    // itself (level 0 in direct mode: columns 0 .. P.w of the image)
-    int plevel, ppad;
+    int plevel;                          // the parent's level index (level_src: level 0 may be the frame itself)
     // Interior words [0, nslide) run the sliding form in whole waves; the
     // other rem = nfast - nslide < 64 go to wave rem_wave as (row group,
     // word) items, rem_n rows per group (0: no remainder).  The host leaves
@@ -330,7 +348,7 @@ __global__ __launch_bounds__(256) void k_pyr_resize_lds(ExtractArgs a, ResizeLev
     __shared__ ResizeRow s_rows[kResRows];
     __shared__ __attribute__((aligned(16))) uint2 s_slide[kResRows];
     const int f = blockIdx.y, tid = threadIdx.x;
-    const int py0 = blockIdx.x * kResRows, nrows = min(kResRows, L.ph - py0);
+    const int y0 = blockIdx.x * kResRows, nrows = min(kResRows, L.h - y0);   // interior rows y0 .. y0 + nrows - 1
     const int nch = pitch >> 4;
     ResizeCol* s_cols = reinterpret_cast<ResizeCol*>(s_dyn + (size_t)L.span * nch);
     uint8_t* s_src = reinterpret_cast<uint8_t*>(s_dyn);
@@ -338,24 +356,24 @@ __global__ __launch_bounds__(256) void k_pyr_resize_lds(ExtractArgs a, ResizeLev
     // load), so the staging loads go out together with the row/column tables
     const int lo = a.res_rows[L.strip_off + blockIdx.x].sy0;
     if (tid < nrows) {
-        const ResizeRow e = a.res_rows[L.row_off + reflect101(py0 + tid - kEdge, L.h)];
+        const ResizeRow e = a.res_rows[L.row_off + y0 + tid];
         s_rows[tid] = e;
         // The sliding form's copy of the entry carries in the free bit 12 of
         // b0 (weights are <= 2048) whether the row's first source row is new:
         // not the previous row's second, which the sliding form still holds.
         // Decided here once per strip, not per wave and row.
-        const ResizeRow p = a.res_rows[L.row_off + reflect101(py0 + max(tid, 1) - 1 - kEdge, L.h)];
+        const ResizeRow p = a.res_rows[L.row_off + y0 + max(tid, 1) - 1];
         const uint32_t first = (tid == 0 || p.sy1 != e.sy0) ? 0x1000u : 0u;
         s_slide[tid] = make_uint2((uint32_t)(uint16_t)e.sy0 | (uint32_t)(uint16_t)e.sy1 << 16,
                                   (uint32_t)(uint16_t)e.b0 | first | (uint32_t)(uint16_t)e.b1 << 16);
     }
     stage_to_lds<4>(s_cols, L.w, tid, (int)blockDim.x, [&](int x) { return a.res_cols[L.col_off + x]; });
     const int nsrc = min(L.span, L.ph_parent_h - lo);
-    // parent row lo from its column kEdge - ppad on: the padded row's first
-    // byte, or the frame row's (there every staged byte lies inside the
-    // frame: rows lo .. lo + nsrc - 1 < P.h, columns 0 .. pitch - 1 = P.w - 1)
+    // parent row lo from its first interior byte (16-byte aligned in the
+    // padded level and in the frame); rows lo .. lo + nsrc - 1 < P.h.  For the
+    // frame every staged byte lies inside it (pitch = P.w)
     const LevelSrc ps = level_src(a, f, L.plevel, L.poff, L.pstride);
-    const uint8_t* pbase = ps.base + (size_t)(lo + kEdge) * ps.stride + (kEdge - L.ppad);
+    const uint8_t* pbase = ps.base + (size_t)(lo + kEdge) * ps.stride + kEdge;
 #ifndef RES_NO_STAGE
     {
         // u / nch as a float product: (u + 1/2) / nch lies at least 1/(2 nch)
@@ -369,7 +387,7 @@ __global__ __launch_bounds__(256) void k_pyr_resize_lds(ExtractArgs a, ResizeLev
     }
 #endif
     __syncthreads();
-    uint8_t* dst = a.pyr_raw + (size_t)f * a.frame_pyr_bytes + L.off + (size_t)py0 * L.stride;
+    uint8_t* dst = a.pyr_raw + (size_t)f * a.frame_pyr_bytes + L.off + (size_t)(kEdge + y0) * L.stride;
 #ifdef RES_NO_COMPUTE
     if (tid < 64) reinterpret_cast<uint32_t*>(dst)[tid] = s_src[tid * 7];
     return;
@@ -380,14 +398,12 @@ __global__ __launch_bounds__(256) void k_pyr_resize_lds(ExtractArgs a, ResizeLev
     //    (x < nvec): the packed form below, one thread per word sliding
     //    down the strip's rows in whole waves, the last nfast % 64 words as
     //    (row group, word) items of one wave (ResizeLevel::nslide);
-    //  * the words holding a scalar-tail column x >= nvec: one (row, word)
-    //    item per thread, in the general form;
-    //  * the reflected border words and the row padding: copies of the
-    //    strip's interior bytes after a barrier (levels narrower than two
-    //    borders and levels not packed: the general form for all of these).
+    //  * the other words holding an interior column (a scalar-tail column
+    //    x >= nvec, a word straddling nvec or w; every interior word of a
+    //    level that is not packed): one (row, word) item per thread, in the
+    //    general form.
     // sx1 is sx0 + 1, or sx0 with a1 = 0 (HResizeLinear tail), so the
     // second tap is always read at offset +1.
-    const int nq = L.stride >> 2;
     const int q_lo = (kEdge + 3) >> 2, q_hi = L.packed ? max(q_lo, (kEdge + min(L.w, L.nvec)) >> 2) : q_lo;
     const int nfast = q_hi - q_lo;
     // Packed form: a word's four source taps lie in 8 bytes (source step
@@ -416,7 +432,7 @@ __global__ __launch_bounds__(256) void k_pyr_resize_lds(ExtractArgs a, ResizeLev
 #pragma unroll
         for (int b = 0; b < 4; b++) {
             const ResizeCol c = s_cols[x0 + b];
-            ca[b] = L.ppad + c.sx0;
+            ca[b] = c.sx0;
             wgt[b] = (uint32_t)(16 * c.a0) | (uint32_t)(16 * c.a1) << 16;
         }
         const int qa = ca[0] & ~3, sh = ca[0] & 3;
@@ -531,20 +547,20 @@ __global__ __launch_bounds__(256) void k_pyr_resize_lds(ExtractArgs a, ResizeLev
         const int r0 = g * L.rem_n;
         if (r0 < nrows) word_rows(std::false_type{}, L.nslide + lane - g * rem, r0, min(r0 + L.rem_n, nrows));
     }
-    // The general form of one output word: per byte the reflected column,
-    // its two taps in both source rows and the column's rounding (SSE2 path
-    // or FixedPtCast<int, uchar, 22>); bytes past the padded width are zero.
+    // The general form of one output word: per byte the column (reflected
+    // for the up to three border bytes behind the last interior column, which
+    // thus hold copyMakeBorder's values), its two taps in both source rows and
+    // the column's rounding (SSE2 path or FixedPtCast<int, uchar, 22>).
     auto general_word = [&](int rr, int q) {
         const int px0 = 4 * q;
         const ResizeRow R = s_rows[rr];
         uint32_t word = 0;
 #pragma unroll
         for (int b = 0; b < 4; b++) {
-            if (px0 + b >= L.pw) continue;   // row padding: zero
             const int x = reflect101(px0 + b - kEdge, L.w);
             const ResizeCol c = s_cols[x];
-            const uint8_t* r0 = s_src + (R.sy0 - lo) * pitch + L.ppad + c.sx0;
-            const uint8_t* r1 = s_src + (R.sy1 - lo) * pitch + L.ppad + c.sx0;
+            const uint8_t* r0 = s_src + (R.sy0 - lo) * pitch + c.sx0;
+            const uint8_t* r1 = s_src + (R.sy1 - lo) * pitch + c.sx0;
             const int S0 = r0[0] * c.a0 + r0[1] * c.a1, S1 = r1[0] * c.a0 + r1[1] * c.a1;
             int v;
             if (x < L.nvec)
@@ -555,51 +571,12 @@ __global__ __launch_bounds__(256) void k_pyr_resize_lds(ExtractArgs a, ResizeLev
         }
         *reinterpret_cast<uint32_t*>(dst + (size_t)rr * L.stride + px0) = word;
     };
-    const int nslow = nq - nfast;
-    if (L.packed && L.w >= 2 * kEdge) {
-        // Borders as copies.  Only the words [q_hi, q_in) that hold an
-        // interior column outside the packed form (the scalar-tail columns
-        // x >= nvec and a word straddling nvec or w) are computed, in the
-        // general form, by the workgroup's last threads (the waves with the
-        // least packed work).  Once the strip's interior is written, every
-        // border byte is copyMakeBorder's REFLECT_101 copy of an interior byte
-        // of its own row: padded byte p < kEdge is padded byte 2 kEdge - p,
-        // p >= kEdge + w is 2 (kEdge + w - 1) - p, both at most kEdge bytes
-        // into the interior (w >= 2 kEdge).  A border word is the byte
-        // reversal of the four source bytes ending at its first byte's
-        // source: two aligned dwords read back from the level (written by
-        // this workgroup, ordered by the barrier), funnel-shifted and
-        // permuted; bytes at and past the padded width are zero.
-        const int q_in = (kEdge + L.w + 3) >> 2, ntail = q_in - q_hi;
-        for (int item = (int)blockDim.x - 1 - tid; item < kResRows * ntail; item += blockDim.x) {
-            const int rr = item % kResRows;
-            if (rr < nrows) general_word(rr, q_hi + item / kResRows);
-        }
-        __syncthreads();
-        const int ncopy = q_lo + nq - q_in;
-        for (int item = tid; item < kResRows * ncopy; item += blockDim.x) {
-            const int rr = item % kResRows, k = item / kResRows;
-            if (rr >= nrows) continue;
-            const int q = k < q_lo ? k : q_in + (k - q_lo), p0 = 4 * q;
-            const int nb = L.pw - p0;   // bytes of the word inside the padded width
-            uint8_t* row = dst + (size_t)rr * L.stride;
-            uint32_t word = 0;
-            if (nb > 0) {
-                const int s = (k < q_lo ? 2 * kEdge : 2 * (kEdge + L.w - 1)) - p0 - 3;   // the lowest source byte
-                const uint32_t* g = reinterpret_cast<const uint32_t*>(row + (s & ~3));
-                const uint32_t v = __builtin_amdgcn_alignbyte(g[1], g[0], s & 3);
-                word = __builtin_amdgcn_perm(0u, v, 0x00010203u);
-                if (nb < 4) word &= (1u << (8 * nb)) - 1u;
-            }
-            *reinterpret_cast<uint32_t*>(row + p0) = word;
-        }
-        return;
-    }
-    // levels narrower than two borders, and the form that is not packed:
-    // every other word in the general form, one (row, word) each
-    for (int item = tid; item < nrows * nslow; item += blockDim.x) {
-        const int rr = item / nslow, k = item - rr * nslow;
-        general_word(rr, k < q_lo ? k : k + nfast);
+    // the words [q_hi, q_in) by the workgroup's last threads (the waves with
+    // the least packed work)
+    const int q_in = (kEdge + L.w + 3) >> 2, ntail = q_in - q_hi;
+    for (int item = (int)blockDim.x - 1 - tid; item < kResRows * ntail; item += blockDim.x) {
+        const int rr = item % kResRows;
+        if (rr < nrows) general_word(rr, q_hi + item / kResRows);
     }
 }
 
@@ -2116,9 +2093,11 @@ __global__ __launch_bounds__(256) void k_blur(ExtractArgs a, const int4* tiles)
 // tap of the 37x37 blurred patch of the descriptor (rotated pattern points
 // reach cvRound(13*sqrt(2)) = 18, the 7x7 filter 3 more).  Keypoints lie in
 // [16, w - 16) x [16, h - 16) of the level and the padded border is 16, so
-// the window stays inside the padded level.  After IC_Angle the half-wave
-// blurs the 37x37 patch in place (describe_blur_window): the whole-level
-// blur pass and its second pyramid are not on the extraction path.
+// the window stays inside the padded level; a window that leaves the level's
+// interior is staged from its REFLECT_101 sources inside the level
+// (describe_stage_reflect), so no border byte is ever read.  After IC_Angle
+// the half-wave blurs the 37x37 patch in place (describe_blur_window): the
+// whole-level blur pass and its second pyramid are not on the extraction path.
 // ---------------------------------------------------------------------------
 constexpr int kIcRows = 2 * kHalfPatch + 1;          // 31
 constexpr int kBrR = 18;                             // pattern reach
@@ -2144,55 +2123,77 @@ __device__ __forceinline__ void wave_lds_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// The window of a level-0 keypoint near the image edge when level 0 is the
-// frame itself (level_src: no border exists there).  The window's first byte
-// is padded position (x0, y0); every byte is fetched from the image position
-// BORDER_REFLECT_101 maps it to, so the staged bytes equal the padded copy's
-// and every address lies inside the frame -- also for the window bytes that
-// the blur never uses.  Keypoints are at least kEdge inside the level, so the
-// window lies within the padded level's kEdge border and one reflection per
-// index is enough (the clamps only keep a degenerate tiny level in bounds).
-// x0, kEdge and lw are multiples of 4, so a window dword lies wholly inside
-// the image columns or wholly outside.  An outside dword at image columns
-// c .. c + 3 is the byte-reversed dword at columns -c - 3 .. -c (c < 0) or
-// 2 lw - 5 - c .. 2 lw - 2 - c (c >= lw): one (unaligned) dword load each,
-// no branch per item, all of a lane's loads in flight together as in the
-// common path.
+// The window of a keypoint near the level's edge.  No border is read: the
+// batch resize writes level interiors only, and the direct level 0 is the
+// frame itself (level_src), where none exists.  The window's first byte is
+// padded position (x0, y0); every byte is fetched from the interior position
+// BORDER_REFLECT_101 maps it to, so the staged bytes equal the padded level's
+// and every address lies inside the level's interior (the frame, for the
+// direct level 0) -- also for the window bytes that the blur never uses.
+// Keypoints are at least kEdge inside the level, so the window lies within
+// the padded level's kEdge border and one reflection per index is enough (the
+// clamps only keep a degenerate tiny level in bounds).
+// x0 and kEdge are multiples of 4, so a window dword at level columns
+// c .. c + 3 lies wholly left of the level (c <= -4) or starts inside it or
+// behind it.  A lane owns one dword column of the window and every second
+// row (lane hl: column hl & 15 of the kWinDw, rows (hl >> 4) + 2 t), so what
+// depends on the column is computed once per lane: the source column of its
+// one (unaligned) dword load d per row, and the byte selector that turns d
+// into the window dword --
+//   c < 0            d = columns -c - 3 .. -c, byte-reversed;
+//   c >= lw          d = columns 2 lw - 5 - c .. 2 lw - 2 - c, byte-reversed;
+//   c <= lw - 4      d = columns c .. c + 3, as loaded;
+//   else (n = lw - c of 1 .. 3 bytes inside; widths that are no multiple of
+//   4): d = columns lw - 4 .. lw - 1.  Byte j < n is column c + j, d's byte
+//   4 - n + j; byte j >= n reflects to column lw - 2 + n - j, d's byte
+//   2 + n - j (n = 1: the reversal again).
+// Per row only the reflected row index and the address remain.  No branch
+// per item, all of a lane's loads in flight together as in the common path;
+// lanes 12 .. 15 of each 16 repeat column 11 and the odd rows' last item
+// repeats row kWinRows - 1 (the same values to the same addresses).
 __device__ __forceinline__ void describe_stage_reflect(const uint8_t* lev, int stride, int lw, int lh, int x0, int y0,
                                                        uint32_t* w32, int hl)
 {
-    constexpr int n = kWinRows * kWinDw, nld = (n + 31) / 32;
-    const uint8_t* img = lev + (long long)kEdge * stride + kEdge;   // the frame's first pixel
+    constexpr int nld = (kWinRows + 1) / 2;
+    static_assert(kWinDw <= 16, "a row's dword columns fit 16 lanes");
+    const uint8_t* img = lev + (long long)kEdge * stride + kEdge;   // the level's first interior pixel
+    const int j = min(hl & 15, kWinDw - 1), ph = hl >> 4;
+    const int c = x0 - kEdge + 4 * j, nin = lw - c;   // nin: bytes of the dword inside the level, where 1 .. 3
+    int col = c < 0 ? -c - 3 : (nin <= 0 ? 2 * lw - 5 - c : c);
+    col = min(max(col, 0), lw - 4);
+    const uint32_t sel = (c < 0 || nin <= 1) ? 0x00010203u : (nin == 2 ? 0x01020302u : (nin == 3 ? 0x02030201u : 0x03020100u));
+    const uint8_t* src = img + col;
+    const int ytop = y0 - kEdge + ph, ymir = 2 * lh - 2;
     uint32_t v[nld];
 #pragma unroll
-    for (int k = 0; k < nld; k++) {
-        const int i = min(hl + 32 * k, n - 1), r = i / kWinDw, c = x0 - kEdge + 4 * (i - r * kWinDw);
-        int y = y0 - kEdge + r;
-        y = y < 0 ? -y : (y >= lh ? 2 * lh - 2 - y : y);
+    for (int t = 0; t < nld; t++) {
+        int y = ytop + (t < nld - 1 ? 2 * t : kWinRows - 1 - ph);
+        y = max(y, -y);
+        y = min(y, ymir - y);
         y = min(max(y, 0), lh - 1);
-        int col = c < 0 ? -c - 3 : (c >= lw ? 2 * lw - 5 - c : c);
-        col = min(max(col, 0), lw - 4);
         uint32_t d;
-        __builtin_memcpy(&d, img + (long long)y * stride + col, 4);
-        v[k] = (c < 0 || c >= lw) ? __builtin_bswap32(d) : d;
+        __builtin_memcpy(&d, src + (uint32_t)(y * stride), 4);
+        v[t] = __builtin_amdgcn_perm(0u, d, sel);
     }
+    uint32_t* dst = w32 + ph * kWinDw + j;
 #pragma unroll
-    for (int k = 0; k < nld; k++) w32[min(hl + 32 * k, n - 1)] = v[k];
+    for (int t = 0; t < nld; t++) dst[(t < nld - 1 ? 2 * t : kWinRows - 1 - ph) * kWinDw] = v[t];
 }
 
 // Stages the raw window of the keypoint at padded level position (X, Y) into
 // win (kWinRows * kBrPitch bytes behind the keypoint's kWinPad), lane hl of
-// 32; lev: the padded level.  A row is kWinPieces 16-byte pieces and win's
+// 32; lev: the padded level's origin (for the direct level 0 the frame's
+// virtual padded origin, level_src), lw x lh the level's size.  The loads
+// below apply when the whole window (kWinRows rows x kBrPitch bytes) lies
+// inside the level's interior; other windows go through
+// describe_stage_reflect -- one rule for every level and mode, whether or not
+// a border was ever written.  A row is kWinPieces 16-byte pieces and win's
 // rows are contiguous, so piece p (row p / 3) goes to win + 16 p: lane hl
 // takes pieces hl, hl + 32, ... with 16-byte loads (the window origin is
 // 4-byte aligned only) and 16-byte LDS stores at a constant distance; the one
 // piece left over after kStageRounds rounds is loaded by every lane and
 // stored by lane 0.  All loads in flight together; 32-bit offsets from the
 // window's first row.  Returns the window centre's byte offset in win.
-// direct: lev is a frame's virtual padded origin (level 0 read from the
-// frame store), lw x lh the level's size.  The loads below then apply when
-// the whole window (kWinRows rows x kBrPitch bytes) lies inside the image;
-// other windows go through describe_stage_reflect.
 typedef uint32_t stage_piece_t __attribute__((ext_vector_type(4), aligned(4)));
 constexpr int kWinPieces = kBrPitch / 16;            // 3 per row
 constexpr int kStagePieces = kWinRows * kWinPieces;   // 129
@@ -2201,11 +2202,11 @@ static_assert(kBrPitch % 16 == 0 && kWinPad % 16 == 0 && kDescWaveBytes % 16 == 
               "every 16-byte piece of a window is 16-byte aligned in LDS");
 static_assert(kStagePieces - 32 * kStageRounds == 1, "one piece is left over after the full rounds");
 static_assert(kStagePieces < 512, "p / 3 == p * 171 >> 9 holds below 512");
-__device__ __forceinline__ int describe_stage_window(const uint8_t* lev, uint32_t stride, bool direct, int lw, int lh,
-                                                     int X, int Y, uint8_t* win, int hl)
+__device__ __forceinline__ int describe_stage_window(const uint8_t* lev, uint32_t stride, int lw, int lh, int X, int Y,
+                                                     uint8_t* win, int hl)
 {
     const int x0 = (X - kWinR) & ~3;
-    if (direct && (Y - kWinR < kEdge || Y + kWinR >= kEdge + lh || x0 < kEdge || x0 + kBrPitch > kEdge + lw)) {
+    if (Y - kWinR < kEdge || Y + kWinR >= kEdge + lh || x0 < kEdge || x0 + kBrPitch > kEdge + lw) {
         describe_stage_reflect(lev, (int)stride, lw, lh, x0, Y - kWinR, reinterpret_cast<uint32_t*>(win), hl);
         return kWinR * kBrPitch + (X - x0);
     }
@@ -2530,8 +2531,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k
         // the raw window; br: its centre, the centre of the blurred patch
         // after describe_blur_window
         const LevelSrc ls = level_src(a, f, level, lev_off, lev_stride);
-        br = win + describe_stage_window(ls.base, (uint32_t)ls.stride, a.l0_direct && level == 0, lev_w, lev_h, X, Y,
-                                         win, hl);
+        br = win + describe_stage_window(ls.base, (uint32_t)ls.stride, lev_w, lev_h, X, Y, win, hl);
         wave_lds_sync();
         // IC_Angle on the unblurred level
         describe_moments(win, X, hl, icw, m01, m10);
@@ -2669,15 +2669,15 @@ namespace orbx {
 
 // Test hook: k_describe's window staging and patch blur for one position of
 // one level, both halves of the wave on the same keypoint; the blurred 37x37
-// patch goes to out, row-major.  lev / stride / direct: the level as
-// k_describe sees it (level_src).
-__global__ __launch_bounds__(64) void k_debug_describe_patch(const uint8_t* lev, int stride, int direct, LevelGeom L,
+// patch goes to out, row-major.  lev / stride: the level as k_describe sees
+// it (level_src).
+__global__ __launch_bounds__(64) void k_debug_describe_patch(const uint8_t* lev, int stride, LevelGeom L,
                                                              int X, int Y, uint8_t* out)
 {
     __shared__ __attribute__((aligned(16))) uint8_t s_patch[2][kDescWaveBytes];
     const int lane = threadIdx.x, half = lane >> 5, hl = lane & 31;
     uint8_t* win = s_patch[half] + kWinPad;
-    const int centre = describe_stage_window(lev, (uint32_t)stride, direct != 0, L.w, L.h, X, Y, win, hl);
+    const int centre = describe_stage_window(lev, (uint32_t)stride, L.w, L.h, X, Y, win, hl);
     wave_lds_sync();
     describe_blur_window(win, X, Y, L.w, L.h, L.nvec_blur, hl);
     if (half == 0)
@@ -2690,7 +2690,7 @@ __global__ __launch_bounds__(64) void k_debug_describe_patch(const uint8_t* lev,
 // Test hook: k_describe's window staging and IC_Angle moments for one position
 // of one level, both halves of the wave on the same keypoint; out: m01, m10 of
 // half 0, then of half 1.
-__global__ __launch_bounds__(64) void k_debug_describe_moments(const uint8_t* lev, int stride, int direct, LevelGeom L,
+__global__ __launch_bounds__(64) void k_debug_describe_moments(const uint8_t* lev, int stride, LevelGeom L,
                                                                const uint32_t* ic_rows, int X, int Y, int* out)
 {
     __shared__ __attribute__((aligned(16))) uint8_t s_patch[2][kDescWaveBytes];
@@ -2698,7 +2698,7 @@ __global__ __launch_bounds__(64) void k_debug_describe_moments(const uint8_t* le
     uint8_t* win = s_patch[half] + kWinPad;
     uint32_t icw[kIcTabDw];
     describe_ic_weights(ic_rows, hl, icw);
-    describe_stage_window(lev, (uint32_t)stride, direct != 0, L.w, L.h, X, Y, win, hl);
+    describe_stage_window(lev, (uint32_t)stride, L.w, L.h, X, Y, win, hl);
     wave_lds_sync();
     int m01, m10;
     describe_moments(win, X, hl, icw, m01, m10);
@@ -2744,12 +2744,55 @@ int launch_level0_slot(orbx_ctx* ctx, int slot)
     return ORBX_OK;
 }
 
+// The borders of levels 1 .. nlevels - 1 of one frame's pyramid (pyr), as
+// copyMakeBorder(BORDER_REFLECT_101) of the level leaves them: one thread per
+// dword of the padded rows that is not wholly interior; each of its bytes
+// inside the padded width is the interior byte its position reflects to, the
+// row padding behind it zero.  Interior bytes are only read (a word that
+// straddles the interior's edge stores its interior bytes back unchanged).
+__global__ __launch_bounds__(256) void k_pyr_borders(const LevelGeom* levels, uint8_t* pyr)
+{
+    const LevelGeom L = cget(levels, 1 + (int)blockIdx.y);
+    const int nq = L.stride >> 2;
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= nq * L.ph) return;
+    const int py = idx / nq, p0 = 4 * (idx - py * nq);
+    if (py >= kEdge && py < kEdge + L.h && p0 >= kEdge && p0 + 4 <= kEdge + L.w) return;
+    uint8_t* lev = pyr + L.off;
+    const uint8_t* src = lev + (size_t)(kEdge + reflect101(py - kEdge, L.h)) * L.stride + kEdge;
+    uint32_t word = 0;
+#pragma unroll
+    for (int b = 0; b < 4; b++)
+        if (p0 + b < L.pw) word |= (uint32_t)src[reflect101(p0 + b - kEdge, L.w)] << (8 * b);
+    *reinterpret_cast<uint32_t*>(lev + (size_t)py * L.stride + p0) = word;
+}
+
+// The batch resize (k_pyr_resize_lds) leaves the borders of levels >= 1
+// unwritten, so the readers of a padded level (orbx_dev_read_level, the
+// whole-level blur) call this first, on the context stream and after the
+// slot's pyramid; the fill depends on the level interiors alone, so it is
+// repeated rather than tracked per slot.  Where the borders were written
+// (the single-frame cascade, k_pyr_resize) it stores the same bytes again.
+int launch_borders_slot(orbx_ctx* ctx, int slot)
+{
+    const Geometry& g = ctx->geom;
+    if (g.nlevels < 2) return ORBX_OK;
+    const LevelGeom& L = g.levels[1];   // the largest of the levels filled
+    const int items = (L.stride / 4) * L.ph;
+    hipLaunchKernelGGL(k_pyr_borders, dim3((items + 255) / 256, g.nlevels - 1), dim3(256), 0, ctx->stream,
+                       ctx->dgeom.levels, ctx->pyr_raw + (size_t)slot * g.frame_pyr_bytes);
+    if (hipGetLastError() != hipSuccess) return ORBX_ERR_HIP;
+    return ORBX_OK;
+}
+
 // The whole-level blur of one slot's raw pyramid into the one-frame
 // ctx->pyr_blur, on the context stream (orbx_dev_read_level's blurred levels).
 int launch_blur_slot(orbx_ctx* ctx, int slot)
 {
     const int r0 = launch_level0_slot(ctx, slot);   // k_blur reads the padded level 0
     if (r0 != ORBX_OK) return r0;
+    const int r1 = launch_borders_slot(ctx, slot);  // and the borders of the levels above it
+    if (r1 != ORBX_OK) return r1;
     ExtractArgs a = {};
     a.levels = ctx->dgeom.levels;
     a.pyr_raw = ctx->pyr_raw + (size_t)slot * ctx->geom.frame_pyr_bytes;
@@ -2784,7 +2827,7 @@ extern "C" int orbx_debug_describe_patch(orbx_ctx* ctx, int slot, int level, int
     const uint8_t* lev = direct ? ctx->frames + ((long long)slot * fw * fh - (long long)kEdge * fw - kEdge)
                                 : ctx->pyr_raw + (size_t)slot * ctx->geom.frame_pyr_bytes + L.off;
     hipLaunchKernelGGL(k_debug_describe_patch, dim3(1), dim3(64), 0, ctx->stream, lev, direct ? (int)fw : L.stride,
-                       direct ? 1 : 0, L, kEdge + x, kEdge + y, d);
+                       L, kEdge + x, kEdge + y, d);
     int r = ORBX_OK;
     if (hipStreamSynchronize(ctx->stream) != hipSuccess ||
         hipMemcpy(out, d, kBrRows * kBrRows, hipMemcpyDeviceToHost) != hipSuccess)
@@ -2813,13 +2856,30 @@ extern "C" int orbx_debug_describe_moments(orbx_ctx* ctx, int slot, int level, i
     const uint8_t* lev = direct ? ctx->frames + ((long long)slot * fw * fh - (long long)kEdge * fw - kEdge)
                                 : ctx->pyr_raw + (size_t)slot * ctx->geom.frame_pyr_bytes + L.off;
     hipLaunchKernelGGL(k_debug_describe_moments, dim3(1), dim3(64), 0, ctx->stream, lev, direct ? (int)fw : L.stride,
-                       direct ? 1 : 0, L, ctx->dgeom.ic_rows, kEdge + x, kEdge + y, d);
+                       L, ctx->dgeom.ic_rows, kEdge + x, kEdge + y, d);
     int r = ORBX_OK;
     if (hipStreamSynchronize(ctx->stream) != hipSuccess ||
         hipMemcpy(out, d, 4 * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
         r = ORBX_ERR_HIP;
     (void)hipFree(d);
     return r;
+}
+
+/* Diagnostics (not in include/orbx.h): fills the whole raw-pyramid area of
+ * slots [first_slot, first_slot + count) with one byte value, after every
+ * pending launch and before every later one (tests poison the areas to show
+ * that no result depends on bytes the extraction does not write). */
+extern "C" int orbx_debug_fill_pyramid(orbx_ctx* ctx, int first_slot, int count, int byte)
+{
+    if (!ctx || first_slot < 0 || count < 0 || first_slot + count > ctx->slots || !ctx->pyr_raw) return ORBX_ERR_ARG;
+    ctx_enter(ctx);
+    if (hipDeviceSynchronize() != hipSuccess) return ORBX_ERR_HIP;   // every part stream's work on the slots
+    const size_t fb = (size_t)ctx->geom.frame_pyr_bytes;
+    if (count > 0 && fb > 0 &&
+        hipMemsetAsync(ctx->pyr_raw + (size_t)first_slot * fb, byte & 0xFF, (size_t)count * fb, ctx->stream) != hipSuccess)
+        return ORBX_ERR_HIP;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return ORBX_ERR_HIP;
+    return ORBX_OK;
 }
 
 /* Diagnostics (not in include/orbx.h): 1 when the last extraction launched on
@@ -3000,10 +3060,9 @@ int launch_extract(orbx_ctx* ctx, int first, int count, const MatchSpec* m)
         for (int l = 1; l < g.nlevels; l++) {
             const LevelGeom& L = g.levels[l];
             const LevelGeom& P = g.levels[l - 1];
-            // staged parent rows: the padded row from its first byte, or the
-            // frame's row (no left pad) when the parent is the direct level 0
-            const int ppad = (l == 1 && x.l0_direct) ? 0 : kEdge;
-            const int pitch = (ppad + P.w + 15) & ~15;
+            // staged parent rows: from the first interior byte, in the padded
+            // level as in the frame (the direct level 0)
+            const int pitch = (P.w + 15) & ~15;
             const size_t lds = (size_t)L.res_span * pitch + (size_t)L.w * sizeof(ResizeCol);
             timer_begin(ctx, "resize", st);
             if (lds <= kResizeLds) {
@@ -3026,11 +3085,12 @@ int launch_extract(orbx_ctx* ctx, int first, int count, const MatchSpec* m)
                     const int groups = 64 / rem;
                     rem_n = (kResRows + groups - 1) / groups;
                 }
-                const ResizeLevel rl{L.off, P.off, L.stride, P.stride, L.w, L.h, L.pw, L.ph, P.h, L.nvec_resize,
-                                     L.res_span, L.res_strip_off, L.res_row_off, L.res_col_off, packed, l - 1, ppad,
+                const ResizeLevel rl{L.off, P.off, L.stride, P.stride, L.w, L.h, P.h, L.nvec_resize,
+                                     L.res_span, L.res_strip_off, L.res_row_off, L.res_col_off, packed, l - 1,
                                      nslide, rem_wave, rem_n};
+                // one workgroup per strip of interior rows (no border rows)
                 for (int rep = 0; rep < kDiagRepeat[0]; rep++)
-                    hipLaunchKernelGGL(k_pyr_resize_lds, dim3((L.ph + kResRows - 1) / kResRows, nb), dim3(threads), lds,
+                    hipLaunchKernelGGL(k_pyr_resize_lds, dim3((L.h + kResRows - 1) / kResRows, nb), dim3(threads), lds,
                                        st, x, rl, pitch);
             } else {   // very wide levels: per-pixel gathers from global memory
                 const int items = (L.stride / 4) * ((L.ph + kPyrRows - 1) / kPyrRows);

@@ -21,12 +21,6 @@ namespace orbx {
 namespace {
 inline int cv_round(double v) { return (int)std::nearbyint(v); }
 inline int cv_floor(double v) { int i = (int)v; return i - (i > v); }
-inline int reflect101(int p, int len)
-{
-    if (len == 1) return 0;
-    while (p < 0 || p >= len) p = p < 0 ? -p : 2 * len - 2 - p;
-    return p;
-}
 inline int16_t sat16(int v) { return (int16_t)std::min(32767, std::max(-32768, v)); }
 
 int vec_count(int width, bool strict4)
@@ -187,11 +181,13 @@ int compute_geometry(Geometry& g, int w, int h)
         if (l > 0) {
             const int r = resize_tables(g, g.levels[l - 1].w, g.levels[l - 1].h, L.w, L.h);
             if (r != ORBX_OK) return r;
-            // source rows feeding each strip of kResRows padded output rows
-            for (int py0 = 0; py0 < L.ph; py0 += kResRows) {
+            // source rows feeding each strip of kResRows interior output rows
+            // (k_pyr_resize_lds writes no border rows: the strips partition
+            // the level's rows 0 .. h - 1, 1:1 with the row table)
+            for (int y0 = 0; y0 < L.h; y0 += kResRows) {
                 int lo = 1 << 30, hi = -1;
-                for (int py = py0; py < std::min(py0 + kResRows, L.ph); py++) {
-                    const ResizeRow& rr = g.res_rows[L.res_row_off + reflect101(py - kEdge, L.h)];
+                for (int y = y0; y < std::min(y0 + kResRows, L.h); y++) {
+                    const ResizeRow& rr = g.res_rows[L.res_row_off + y];
                     lo = std::min(lo, (int)std::min(rr.sy0, rr.sy1));
                     hi = std::max(hi, (int)std::max(rr.sy0, rr.sy1));
                 }
@@ -200,16 +196,16 @@ int compute_geometry(Geometry& g, int w, int h)
         }
     }
     g.frame_pyr_bytes = off;
-    // per (level >= 1, strip of kResRows padded rows): the first source row
+    // per (level >= 1, strip of kResRows interior rows): the first source row
     // the strip reads, appended to the row table so the resize kernel can
     // start its staging loads without a dependent table read
     for (int l = 1; l < g.nlevels; l++) {
         LevelGeom& L = g.levels[l];
         L.res_strip_off = (int)g.res_rows.size();
-        for (int py0 = 0; py0 < L.ph; py0 += kResRows) {
+        for (int y0 = 0; y0 < L.h; y0 += kResRows) {
             int lo = 1 << 30;
-            for (int py = py0; py < std::min(py0 + kResRows, L.ph); py++) {
-                const ResizeRow& rr = g.res_rows[L.res_row_off + reflect101(py - kEdge, L.h)];
+            for (int y = y0; y < std::min(y0 + kResRows, L.h); y++) {
+                const ResizeRow& rr = g.res_rows[L.res_row_off + y];
                 lo = std::min(lo, (int)std::min(rr.sy0, rr.sy1));
             }
             g.res_rows.push_back(ResizeRow{(int16_t)lo, 0, 0, 0});

@@ -83,8 +83,8 @@ struct LevelGeom {
     float patch_size;     // (int)(PATCH_SIZE * scale)
     int res_col_off;      // offset into the resize column table (level >= 1)
     int res_row_off;      // offset into the resize row table
-    int res_span;         // max source rows feeding one strip of kResRows output rows
-    int res_strip_off;    // res_rows index of this level's per-strip entries (sy0 = first source row)
+    int res_span;         // max source rows feeding one strip of kResRows interior output rows
+    int res_strip_off;    // res_rows index of this level's entries per interior strip (sy0 = first source row)
 };
 
 struct CellGeom {
@@ -391,6 +391,11 @@ int launch_blur_slot(orbx_ctx* ctx, int slot);   // k_blur of one slot's raw pyr
 // the context stream: the extraction path reads level 0 from the frame store
 // where it can, so whoever reads the padded level 0 builds it first
 int launch_level0_slot(orbx_ctx* ctx, int slot);
+// The borders of levels 1 .. nlevels - 1 of one slot (REFLECT_101 copies of
+// the level's interior, zero row padding), on the context stream: the batch
+// resize writes level interiors only, so whoever reads a padded level >= 1
+// fills its border first.  The caller orders it after the slot's pyramid.
+int launch_borders_slot(orbx_ctx* ctx, int slot);
 // timing helpers (orbx_api.cpp)
 void timer_begin(orbx_ctx* ctx, const char* name, hipStream_t st = nullptr);
 void timer_end(orbx_ctx* ctx, const char* name, hipStream_t st = nullptr);
