@@ -184,6 +184,37 @@ __device__ inline int wave_max(int v)
     return __builtin_amdgcn_readlane(v, 63);
 }
 
+// Lane `lane`'s double (uniform lane index), the same on every lane.
+__device__ inline double readlane_f64(double v, int lane)
+{
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
+    return __hiloint2double(hi, lo);
+}
+
+// Sum over the 16 lanes of a DPP row, the same bits in every lane: each step
+// adds the partner's partial sum to the lane's own, and the partners of a
+// step hold each other's operands (a + b and b + a).  The steps are DPP
+// moves inside the row, not shuffles through the LDS crossbar (which measured
+// 2 % slower in k_init_solve: the rotations' arithmetic bounds it, DESIGN.md
+// section 3).
+template <int kCtrl>
+__device__ inline double row_dpp(double x)
+{
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), kCtrl, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), kCtrl, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+
+__device__ inline double row_sum16(double x)
+{
+    x += row_dpp<0xB1>(x);    // quad_perm:[1,0,3,2]
+    x += row_dpp<0x4E>(x);    // quad_perm:[2,3,0,1]
+    x += row_dpp<0x141>(x);   // row_half_mirror: the other quad of the half row
+    x += row_dpp<0x140>(x);   // row_mirror: the other half row
+    return x;
+}
+
 // Exclusive prefix of v over threadIdx order; *total = block sum.
 template <int kW>
 __device__ inline int block_exclusive_scan(int v, int* total, BlockScratchN<kW>& s, int buf)

@@ -156,28 +156,6 @@ __global__ __launch_bounds__(256) void k_init_prepare(const orbx_keypoint* __res
 // ---------------------------------------------------------------------------
 // k_init_solve
 // ---------------------------------------------------------------------------
-// Sum over the 16 lanes of a DPP row, the same bits in every lane: each step
-// adds the partner's partial sum to the lane's own, and the partners of a
-// step hold each other's operands (a + b and b + a).  The steps are DPP
-// moves inside the row, not shuffles through the LDS crossbar (which measured
-// 2 % slower: the rotations' arithmetic bounds the kernel).
-template <int kCtrl>
-__device__ inline double row_dpp(double x)
-{
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), kCtrl, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), kCtrl, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ inline double row_sum16(double x)
-{
-    x += row_dpp<0xB1>(x);    // quad_perm:[1,0,3,2]
-    x += row_dpp<0x4E>(x);    // quad_perm:[2,3,0,1]
-    x += row_dpp<0x141>(x);   // row_half_mirror: the other quad of the half row
-    x += row_dpp<0x140>(x);   // row_mirror: the other half row
-    return x;
-}
-
 // Fn = U diag(s1, s2, 0) V^T of the 3x3 Fpre: one-sided Jacobi on its columns
 // (B V = U S), the column of the smallest norm dropped.
 __device__ inline void rank2_3x3(const float* fpre, float* fn)

@@ -105,13 +105,6 @@ __global__ void k_kfdb_neigh(KfdbDev d, int n, const int32_t* ids, const int32_t
     if (i < n * kKfdbNeigh) d.neigh[ids[i / kKfdbNeigh] * kKfdbNeigh + i % kKfdbNeigh] = rows[i];
 }
 
-__device__ inline double readlane_f64(double v, int lane)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-    return __hiloint2double(hi, lo);
-}
-
 // Members [0, hi), a wavefront each.  Dynamic LDS: q_cap doubles, q_cap words.
 // The query's length is nq_host, or *nq_dev for a slot query; at most q_cap
 // entries of it are used.

@@ -50,6 +50,7 @@
 
 #include "orbx_device.h"
 #include "orbx_internal.h"
+#include "orbx_lm.h"
 #include "orbx_se3.h"
 #include "orbx_stage.h"
 
@@ -63,6 +64,9 @@ namespace orbx {
 //   phases between barriers run in other interleavings.  A missing barrier or
 //   an LDS overlap between phases then changes bits; the product build and
 //   both variants must give the same bits.
+// (orbx_lm.h's huber and Levenberg functions are forced inline in every build:
+//  scalar arithmetic with no memory of their own, shared with the pose and
+//  Sim3 kernels.)
 #ifdef ORBX_LBA_NOINLINE
 #define LBA_FN __device__ __noinline__
 #else
@@ -203,6 +207,9 @@ struct DScratch {
     double w[kLbaWaves];
 };
 
+// Not orbx_device.h's row_sum16 / orbx_pose.hip's wave_sum_uniform: these are
+// __shfl_xor butterflies from the far half inwards, another summation order,
+// and every local-BA sum's bits follow it.  They stay as they are.
 LBA_FN double wave_sum_d(double v)
 {
 #pragma unroll
@@ -243,19 +250,10 @@ LBA_FN double block_max_d(double v, DScratch& s)
 // Edge algebra (pose z in the LDS layout: q at z[0..3], t at z[4..6], the
 // rotation matrix at z[7..15], fx fy cx cy at z[16..19])
 // ---------------------------------------------------------------------------
-LBA_FN void huber(double e2, double delta, double* rho0, double* rho1)
-{
-    const double dsqr = delta * delta;
-    if (e2 <= dsqr) {
-        *rho0 = e2;
-        *rho1 = 1.;
-    } else {
-        const double sq = sqrt(e2);
-        *rho0 = 2 * sq * delta - dsqr;
-        *rho1 = delta / sq;
-    }
-}
-
+// residual and jac_point are not orbx_pose.hip's pose_edge_error /
+// pose_edge_terms with their div_* helpers: the two round differently by
+// design (g2o's divisions there, products with 1 / z here), each as its own
+// oracle (ref_pose.cpp, ref_lba.cpp) states it.  They are not to be merged.
 // EdgeSE3ProjectXYZ::computeError (types_six_dof_expmap.h:172-177) with
 // cam_project (.cpp:422-428): e = obs - (fx X / Z + cx, fy Y / Z + cy)
 LBA_FN void residual(const double* c, const double (&pc)[3], double ox, double oy, double& e0, double& e1)
@@ -337,7 +335,7 @@ LBA_FN double point_errors(LbaDev& P, const double* pz, int l, const double (&pt
         P.err[2 * e + 1] = e1;
         const double s = (double)r.isig;
         double r0, r1;
-        huber(e0 * (s * e0) + e1 * (s * e1), P.huber_delta, &r0, &r1);
+        huber(e0 * (s * e0) + e1 * (s * e1), P.huber_delta, r0, r1);
         part += r0;
     }
     return part;
@@ -391,7 +389,7 @@ LBA_FN double point_linearize(LbaDev& P, const double* pz, int l, double (&acc)[
         jac_point(z + 16, z + 7, pc, A);
         const double sg = (double)r.isig;
         double r0, r1;
-        huber(e0 * (sg * e0) + e1 * (sg * e1), P.huber_delta, &r0, &r1);
+        huber(e0 * (sg * e0) + e1 * (sg * e1), P.huber_delta, r0, r1);
         const double w = r1 * sg, om0 = -(sg * e0) * r1, om1 = -(sg * e1) * r1;
         P.ew[j] = w;
         int k = 0;
@@ -429,7 +427,7 @@ LBA_FN void pose_linearize(LbaDev& P, const double* pz, int p, double& hm, doubl
         jac_pose(z + 16, pc, B);
         const double sg = (double)r.isig;
         double r0, r1;
-        huber(e0 * (sg * e0) + e1 * (sg * e1), P.huber_delta, &r0, &r1);
+        huber(e0 * (sg * e0) + e1 * (sg * e1), P.huber_delta, r0, r1);
         const double w = r1 * sg, om0 = -(sg * e0) * r1, om1 = -(sg * e1) * r1;
         int k = 0;
 #pragma unroll
@@ -1128,8 +1126,8 @@ __global__ __launch_bounds__(kLbaThreads) void k_lba_iteration(LbaDev* probs, in
     }
     LBA_SYNC();
     for (int it = iteration; it < iteration + iters && s_it[1] == kRunning; it++) {
-    double lambda = s_lm[0], ni = s_lm[1], currentChi = s_lm[2];
-    int nBad = s_it[0];
+    LmState lm{s_lm[0], s_lm[1], s_it[0]};
+    double currentChi = s_lm[2];
     LBA_T0();
     // computeActiveErrors at the start of the iteration: after the first
     // iteration the state is the previous iteration's accepted trial state,
@@ -1146,10 +1144,7 @@ __global__ __launch_bounds__(kLbaThreads) void k_lba_iteration(LbaDev* probs, in
             m = fmax(m, fabs(P.hp[27 * (item / 6) + up6(item % 6, item % 6)]));
         for (int item = threadIdx.x; item < P.nL * 3; item += kLbaThreads)
             m = fmax(m, fabs(P.hl[9 * (item / 3) + up3(item % 3, item % 3)]));
-        m = block_max_d(m, sc);
-        lambda = 1e-5 * m;
-        ni = 2;
-        nBad = 0;
+        lm_init(lm, block_max_d(m, sc));
     }
     double rho = 0;
     int qmax = 0;
@@ -1161,7 +1156,7 @@ __global__ __launch_bounds__(kLbaThreads) void k_lba_iteration(LbaDev* probs, in
             pbk[i] = pz[kPz * P.iv_pose[p] + k];
         }
         LBA_SYNC();
-        const bool ok2 = trial_solve<Rec, kLds>(P, lds, pz, xp, lambda);
+        const bool ok2 = trial_solve<Rec, kLds>(P, lds, pz, xp, lm.lambda);
         if (ok2)
             for (int p = threadIdx.x; p < P.nP; p += kLbaThreads) {
                 double* z = pz + kPz * P.iv_pose[p];
@@ -1190,7 +1185,7 @@ __global__ __launch_bounds__(kLbaThreads) void k_lba_iteration(LbaDev* probs, in
 #pragma unroll
                 for (int i = 0; i < 3; i++) {
                     bk[i] = pt[i];
-                    scale_part += xl[i] * (lambda * xl[i] + h[6 + i]);
+                    scale_part += xl[i] * (lm.lambda * xl[i] + h[6 + i]);
                     pt[i] += xl[i];
                     pw[i] = pt[i];
                 }
@@ -1199,53 +1194,31 @@ __global__ __launch_bounds__(kLbaThreads) void k_lba_iteration(LbaDev* probs, in
         }
         if (ok2)
             for (int j = threadIdx.x; j < n; j += kLbaThreads)
-                scale_part += xp[j] * (lambda * xp[j] + P.hp[27 * (j / 6) + 21 + (j % 6)]);
-        double tempChi = block_sum_d(chi_part, sc);
+                scale_part += xp[j] * (lm.lambda * xp[j] + P.hp[27 * (j / 6) + 21 + (j % 6)]);
+        const double tempChi = block_sum_d(chi_part, sc);
         LBA_MARK(8);
-        if (!ok2) {
-            tempChi = 1.79769313486231570815e+308;
-            if (threadIdx.x == 0) P.not_posdef++;
-        }
-        double scale = block_sum_d(scale_part, sc);
-        scale += 1e-3;
-        rho = (currentChi - tempChi) / scale;
-        const bool accept = rho > 0 && isfinite(tempChi);
-        if (accept) {
-            double alpha = 1. - pow((2 * rho - 1), 3);
-            alpha = fmin(alpha, 2. / 3.);
-            lambda *= fmax(1. / 3., alpha);
-            ni = 2;
-            currentChi = tempChi;
-        } else {
-            lambda *= ni;
-            ni *= 2;
-            if (ok2) {   // pop: the saved poses and points
-                for (int i = threadIdx.x; i < P.nP * kPbk; i += kLbaThreads) {
-                    const int p = i / kPbk, k = i - kPbk * p;
-                    pz[kPz * P.iv_pose[p] + k] = pbk[i];
-                }
-                for (int i = threadIdx.x; i < P.nL * 3; i += kLbaThreads) {
-                    const int l = i / 3, k = i - 3 * l;
-                    P.point[3 * P.iv_point[l] + k] = P.point_bk[i];
-                }
+        if (!ok2 && threadIdx.x == 0) P.not_posdef++;
+        const LmTrial trial = lm_trial(lm, currentChi, tempChi, ok2, block_sum_d(scale_part, sc));
+        rho = trial.rho;
+        if (!trial.accept && ok2) {   // pop: the saved poses and points
+            for (int i = threadIdx.x; i < P.nP * kPbk; i += kLbaThreads) {
+                const int p = i / kPbk, k = i - kPbk * p;
+                pz[kPz * P.iv_pose[p] + k] = pbk[i];
+            }
+            for (int i = threadIdx.x; i < P.nL * 3; i += kLbaThreads) {
+                const int l = i / 3, k = i - 3 * l;
+                P.point[3 * P.iv_point[l] + k] = P.point_bk[i];
             }
         }
         LBA_SYNC();
         qmax++;
-    } while (rho < 0 && qmax < 10 && !P.abort);
-    int status = kRunning;
-    if (qmax == 10 || rho == 0) {
-        status = kTerminated;
-    } else {
-        if ((iniChi - currentChi) * 1e3 < iniChi) nBad++;
-        else nBad = 0;
-        if (nBad >= 3) status = kTerminated;
-    }
+    } while (lm_retry(rho, qmax) && !P.abort);
+    const int status = lm_stop(lm, qmax, rho, iniChi, currentChi) ? kTerminated : kRunning;
     if (threadIdx.x == 0) {
-        s_lm[0] = lambda;
-        s_lm[1] = ni;
+        s_lm[0] = lm.lambda;
+        s_lm[1] = lm.ni;
         s_lm[2] = currentChi;
-        s_it[0] = nBad;
+        s_it[0] = lm.nBad;
         s_it[1] = status;
         s_it[2]++;
         s_it[3] += qmax;
@@ -1604,7 +1577,7 @@ LBA_FN bool backsub_edgewise(LbaDev& P, const double* pz, const double* pbk, con
         P.err[2 * eo + 1] = e1;
         const double s = (double)r.isig;
         double r0, r1;
-        huber(e0 * (s * e0) + e1 * (s * e1), P.huber_delta, &r0, &r1);
+        huber(e0 * (s * e0) + e1 * (s * e1), P.huber_delta, r0, r1);
         es[e] = r0;   // the terms of step 1 are dead: step 2 is behind the barrier
     }
     LBA_SYNC();
@@ -1666,7 +1639,7 @@ LBA_FN bool linearize_edgewise(LbaDev& P, const double* pz, const int g, const i
         jac_point(z + 16, z + 7, pc, A);
         const double sg = (double)r.isig;
         double r0, r1;
-        huber(e0 * (sg * e0) + e1 * (sg * e1), P.huber_delta, &r0, &r1);
+        huber(e0 * (sg * e0) + e1 * (sg * e1), P.huber_delta, r0, r1);
         const double w = r1 * sg, om0 = -(sg * e0) * r1, om1 = -(sg * e1) * r1;
         P.ew[j] = w;
         double* o = es + 9 * e;
@@ -1713,8 +1686,9 @@ LBA_FN double canon_sum(const double* v, int nL, DScratch& sc)
 // registers it spilled them).  Every thread computes the same values; thread
 // 0 stores them before a barrier.
 struct SplitLM {
-    double lambda, ni, currentChi, chi2_ini, iniChi, hm, bm, sS, sB, rho;
-    int nBad, status, done, trials, not_posdef, ok, ok2, qmax;
+    LmState lm;
+    double currentChi, chi2_ini, iniChi, hm, bm, sS, sB, rho;
+    int status, done, trials, not_posdef, ok, ok2, qmax;
 };
 
 template <class Rec>
@@ -1756,11 +1730,9 @@ __global__ __launch_bounds__(kLbaThreads) void k_lba_split(LbaDev* probs, int it
         pz[kPz * p + (k < 7 ? k : 9 + k)] = k < 7 ? P.pose[7 * p + k] : P.cam[4 * p + (k - 7)];
     }
     if (threadIdx.x == 0) {
-        st.lambda = P.lambda;
-        st.ni = P.ni;
+        st.lm = LmState{P.lambda, P.ni, P.nBad};
         st.currentChi = P.current_chi;
         st.chi2_ini = P.chi2_initial;
-        st.nBad = P.nBad;
         st.status = kRunning;
         st.done = st.trials = st.not_posdef = 0;
         st.ok = 1;
@@ -1820,9 +1792,7 @@ __global__ __launch_bounds__(kLbaThreads) void k_lba_split(LbaDev* probs, int it
                 if (it == 0) {
                     st.currentChi = chi0;
                     st.chi2_ini = chi0;
-                    st.lambda = 1e-5 * fmax(a, c);
-                    st.ni = 2;
-                    st.nBad = 0;
+                    lm_init(st.lm, fmax(a, c));
                 }
                 st.iniChi = st.currentChi;
                 st.rho = 0;
@@ -1838,7 +1808,7 @@ __global__ __launch_bounds__(kLbaThreads) void k_lba_split(LbaDev* probs, int it
             }
             // --- Schur complement, summed over the workgroups
             if (threadIdx.x == 0) {
-                const double hmax = st.hm + st.lambda, bmax = st.bm;
+                const double hmax = st.hm + st.lm.lambda, bmax = st.bm;
                 st.sS = (hmax > 0 && isfinite(hmax)) ? ldexp(1.0, 29 - ilogb(hmax)) : 1.0;
                 st.sB = (bmax > 0 && isfinite(bmax)) ? ldexp(1.0, 23 - ilogb(bmax)) : 1.0;
                 st.ok2 = 1;
@@ -1848,7 +1818,7 @@ __global__ __launch_bounds__(kLbaThreads) void k_lba_split(LbaDev* probs, int it
                 for (int k = threadIdx.x; k < X.limbs; k += kLbaThreads) hi[k] = 0;
                 if (threadIdx.x == 0) s_bad = 0;
                 LBA_SYNC();
-                const double lambda = st.lambda, kS = st.sS * kFxHi, kB = st.sB * kFxHi;
+                const double lambda = st.lm.lambda, kS = st.sS * kFxHi, kB = st.sB * kFxHi;
                 if (g == 0) {
                     for (int item = threadIdx.x; item < P.nP * 21; item += kLbaThreads) {
                         const int p = item / 21, u = item - p * 21;
@@ -1956,7 +1926,7 @@ __global__ __launch_bounds__(kLbaThreads) void k_lba_split(LbaDev* probs, int it
             }
             {   // --- back-substitution, point update, errors of this workgroup's points
                 const bool ok2 = st.ok2;
-                const double lambda = st.lambda;
+                const double lambda = st.lm.lambda;
                 // edge-parallel when the workgroup's points fit the scratch,
                 // else a thread per point (the same bits either way)
                 const bool edgewise = backsub_edgewise<Rec>(P, pz, pbk, xp, g, G, ok2, lambda, X, eA, etab);
@@ -1988,10 +1958,13 @@ __global__ __launch_bounds__(kLbaThreads) void k_lba_split(LbaDev* probs, int it
             LBA_MARK(23);
             const bool ok3 = grid_sync(X, epoch);
             LBA_MARK(24);
-            {   // k_lba_iteration's sums, in its order, and its LM decision
+            {   // k_lba_iteration's sums, in its order, and its LM decision: every
+                // thread takes it on a copy of the state, thread 0 stores the copy
                 const bool ok2 = st.ok2;
-                const double lambda = st.lambda, ni = st.ni, currentChi = st.currentChi;
-                double tempChi = canon_sum(X.chi_pt, P.nL, sc);
+                LmState lm = st.lm;
+                double currentChi = st.currentChi;
+                const double lambda = lm.lambda;
+                const double tempChi = canon_sum(X.chi_pt, P.nL, sc);
                 double scale_part = 0;
                 if (ok2) {
                     for (int l = threadIdx.x; l < P.nL; l += kLbaThreads) {
@@ -2001,12 +1974,8 @@ __global__ __launch_bounds__(kLbaThreads) void k_lba_split(LbaDev* probs, int it
                     }
                     for (int j = threadIdx.x; j < n; j += kLbaThreads) scale_part += xp[j] * (lambda * xp[j] + bpl[j]);
                 }
-                if (!ok2) tempChi = 1.79769313486231570815e+308;
-                double scale = block_sum_d(scale_part, sc);
-                scale += 1e-3;
-                const double rho = (currentChi - tempChi) / scale;
-                const bool accept = rho > 0 && isfinite(tempChi);
-                if (!accept && ok2) {   // pop: the saved poses (every workgroup) and this workgroup's points
+                const LmTrial trial = lm_trial(lm, currentChi, tempChi, ok2, block_sum_d(scale_part, sc));
+                if (!trial.accept && ok2) {   // pop: the saved poses (every workgroup) and this workgroup's points
                     for (int i = threadIdx.x; i < P.nP * kPbk; i += kLbaThreads) {
                         const int p = i / kPbk, k = i - kPbk * p;
                         pz[kPz * P.iv_pose[p] + k] = pbk[i];
@@ -2020,34 +1989,20 @@ __global__ __launch_bounds__(kLbaThreads) void k_lba_split(LbaDev* probs, int it
                 }
                 LBA_SYNC();   // every thread has read st
                 if (threadIdx.x == 0) {
-                    if (accept) {
-                        double alpha = 1. - pow((2 * rho - 1), 3);
-                        alpha = fmin(alpha, 2. / 3.);
-                        st.lambda = lambda * fmax(1. / 3., alpha);
-                        st.ni = 2;
-                        st.currentChi = tempChi;
-                    } else {
-                        st.lambda = lambda * ni;
-                        st.ni = ni * 2;
-                    }
+                    st.lm = lm;
+                    st.currentChi = currentChi;
                     if (!ok2) st.not_posdef++;
-                    st.rho = rho;
+                    st.rho = trial.rho;
                     st.qmax++;
                     st.ok = st.ok && ok3;
                 }
                 LBA_SYNC();
             }
             LBA_MARK(25);
-        } while (st.rho < 0 && st.qmax < 10 && !P.abort && st.ok);
+        } while (lm_retry(st.rho, st.qmax) && !P.abort && st.ok);
         LBA_SYNC();   // every thread has evaluated the loop condition
         if (threadIdx.x == 0) {
-            if (st.qmax == 10 || st.rho == 0) {
-                st.status = kTerminated;
-            } else {
-                if ((st.iniChi - st.currentChi) * 1e3 < st.iniChi) st.nBad++;
-                else st.nBad = 0;
-                if (st.nBad >= 3) st.status = kTerminated;
-            }
+            if (lm_stop(st.lm, st.qmax, st.rho, st.iniChi, st.currentChi)) st.status = kTerminated;
             st.done++;
             st.trials += st.qmax;
         }
@@ -2062,13 +2017,13 @@ __global__ __launch_bounds__(kLbaThreads) void k_lba_split(LbaDev* probs, int it
     }
     if (threadIdx.x == 0) {
         if (iteration == 0) P.chi2_initial = st.chi2_ini;
-        P.lambda = st.lambda;
-        P.ni = st.ni;
+        P.lambda = st.lm.lambda;
+        P.ni = st.lm.ni;
         P.trials += st.trials;
         P.iterations += st.done;
         P.last_chi = st.currentChi;
         P.current_chi = st.currentChi;
-        P.nBad = st.nBad;
+        P.nBad = st.lm.nBad;
         P.status = (st.ok && okf) ? st.status : kTerminated;
         P.not_posdef += st.not_posdef;
     }

@@ -37,6 +37,7 @@
 
 #include "orbx_device.h"
 #include "orbx_internal.h"
+#include "orbx_lm.h"
 #include "orbx_pose_dev.h"
 #include "orbx_se3.h"
 #include "orbx_stage.h"
@@ -64,51 +65,17 @@ constexpr int kPoseWideWaves = ORBX_POSE_WIDE;    // wavefronts per frame of the
 static_assert((kPoseThreads / 64) * kPoseLdsEdges * (6 * sizeof(float) + 1) <= 80 * 1024,
               "two pose workgroups per CU need <= 80 KB of LDS each (gfx950: 160 KB per CU)");
 
-// Wave sum whose result is the same double on every lane: DPP butterflies
-// inside each row of 16 (xor 1, xor 2 by quad_perm; the half-row and row
-// mirrors pair lanes symmetrically), then the four row sums combined by
+// Wave sum whose result is the same double on every lane: the DPP butterfly
+// inside each row of 16 (row_sum16), then the four row sums combined by
 // readlane in a fixed order.
-__device__ inline double dpp_f64(double v, int ctrl_sel)
-{
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    int rlo, rhi;
-    switch (ctrl_sel) {
-    case 0:
-        rlo = __builtin_amdgcn_update_dpp(lo, lo, 0xB1, 0xf, 0xf, false);   // quad_perm [1,0,3,2]
-        rhi = __builtin_amdgcn_update_dpp(hi, hi, 0xB1, 0xf, 0xf, false);
-        break;
-    case 1:
-        rlo = __builtin_amdgcn_update_dpp(lo, lo, 0x4E, 0xf, 0xf, false);   // quad_perm [2,3,0,1]
-        rhi = __builtin_amdgcn_update_dpp(hi, hi, 0x4E, 0xf, 0xf, false);
-        break;
-    case 2:
-        rlo = __builtin_amdgcn_update_dpp(lo, lo, 0x141, 0xf, 0xf, false);  // row_half_mirror
-        rhi = __builtin_amdgcn_update_dpp(hi, hi, 0x141, 0xf, 0xf, false);
-        break;
-    default:
-        rlo = __builtin_amdgcn_update_dpp(lo, lo, 0x140, 0xf, 0xf, false);  // row_mirror
-        rhi = __builtin_amdgcn_update_dpp(hi, hi, 0x140, 0xf, 0xf, false);
-        break;
-    }
-    return __hiloint2double(rhi, rlo);
-}
-
-__device__ inline double lane_f64(double v, int lane)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-    return __hiloint2double(hi, lo);
-}
-
 __device__ inline double wave_sum_uniform(double v)
 {
-    v += dpp_f64(v, 0);
-    v += dpp_f64(v, 1);
-    v += dpp_f64(v, 2);
-    v += dpp_f64(v, 3);
-    return (lane_f64(v, 0) + lane_f64(v, 16)) + (lane_f64(v, 32) + lane_f64(v, 48));
+    v = row_sum16(v);
+    return (readlane_f64(v, 0) + readlane_f64(v, 16)) + (readlane_f64(v, 32) + readlane_f64(v, 48));
 }
 
+// The same tree on ints.  Not orbx_device.h's wave_sum, which is a row-shift
+// scan read at lane 63: another tree, kept apart on purpose.
 __device__ inline int wave_sum_int(int v)
 {
     v += __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xf, 0xf, false);
@@ -119,116 +86,14 @@ __device__ inline int wave_sum_int(int v)
            __builtin_amdgcn_readlane(v, 48);
 }
 
-// Eigen::LDLT<MatrixXd> of the lower triangle of m (row-major 6x6) and the
-// solve of m x = b: the restatement of oracle/ref_pose.cpp ldlt_solve with
-// every index a compile-time constant (the runtime pivot selects among
-// unrolled swap variants), so the matrix stays in registers.
-__device__ inline void swap_d(double& a, double& b)
-{
-    const double t = a;
-    a = b;
-    b = t;
-}
-
-// Packed lower triangle: entry (i, j), j <= i, at i (i + 1) / 2 + j.
-#define LT(i, j) ((i) * ((i) + 1) / 2 + (j))
-
-__device__ inline bool ldlt6_solve(double m[21], const double b[6], double x[6])
-{
-    int tr[6];
-    double temp[6];
-    int sign = 0;   // 0 zero, 1 positive semidefinite, 2 negative semidefinite, 3 indefinite
-#pragma unroll
-    for (int k = 0; k < 6; k++) {
-        int big = k;
-        double bv = fabs(m[LT(k, k)]);
-#pragma unroll
-        for (int i = k + 1; i < 6; i++)
-            if (fabs(m[LT(i, i)]) > bv) {
-                bv = fabs(m[LT(i, i)]);
-                big = i;
-            }
-        tr[k] = big;
-#pragma unroll
-        for (int q = k + 1; q < 6; q++) {
-            if (big == q) {
-#pragma unroll
-                for (int j = 0; j < k; j++) swap_d(m[LT(k, j)], m[LT(q, j)]);
-#pragma unroll
-                for (int i = q + 1; i < 6; i++) swap_d(m[LT(i, k)], m[LT(i, q)]);
-                swap_d(m[LT(k, k)], m[LT(q, q)]);
-#pragma unroll
-                for (int i = k + 1; i < q; i++) swap_d(m[LT(i, k)], m[LT(q, i)]);
-            }
-        }
-        if (k > 0) {
-#pragma unroll
-            for (int j = 0; j < k; j++) temp[j] = m[LT(j, j)] * m[LT(k, j)];
-            double acc = m[LT(k, 0)] * temp[0];
-#pragma unroll
-            for (int j = 1; j < k; j++) acc += m[LT(k, j)] * temp[j];
-            m[LT(k, k)] -= acc;
-#pragma unroll
-            for (int i = k + 1; i < 6; i++)
-#pragma unroll
-                for (int j = 0; j < k; j++) m[LT(i, k)] -= m[LT(i, j)] * temp[j];
-        }
-        const double akk = m[LT(k, k)];
-        if (k < 5 && fabs(akk) > 0.0) {
-#pragma unroll
-            for (int i = k + 1; i < 6; i++) m[LT(i, k)] /= akk;
-        }
-        if (sign == 1) {
-            if (akk < 0) sign = 3;
-        } else if (sign == 2) {
-            if (akk > 0) sign = 3;
-        } else if (sign == 0) {
-            if (akk > 0) sign = 1;
-            else if (akk < 0) sign = 2;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 6; i++) x[i] = b[i];
-#pragma unroll
-    for (int k = 0; k < 6; k++)
-#pragma unroll
-        for (int q = k + 1; q < 6; q++)
-            if (tr[k] == q) swap_d(x[k], x[q]);
-#pragma unroll
-    for (int i = 0; i < 6; i++)
-#pragma unroll
-        for (int j = 0; j < i; j++) x[i] -= m[LT(i, j)] * x[j];
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        if (fabs(m[LT(i, i)]) > 2.2250738585072014e-308) x[i] /= m[LT(i, i)];
-        else x[i] = 0.0;
-    }
-#pragma unroll
-    for (int i = 4; i >= 0; i--) {
-        double s = m[LT(i + 1, i)] * x[i + 1];
-#pragma unroll
-        for (int j = i + 2; j < 6; j++) s += m[LT(j, i)] * x[j];
-        x[i] -= s;
-    }
-#pragma unroll
-    for (int k = 5; k >= 0; k--)
-#pragma unroll
-        for (int q = k + 1; q < 6; q++)
-            if (tr[k] == q) swap_d(x[k], x[q]);
-    return sign == 1 || sign == 0;
-}
-
-
-struct Cam {
-    double fx, fy, cx, cy;
-};
-
 // EdgeSE3ProjectXYZ::computeError (types_six_dof_expmap.h:172-177) at pose
 // (q x y z w, t): e = obs - (fx X/Z + cx, fy Y/Z + cy), Xc = q Xw + t.
+// (Kept apart from orbx_lba.hip's residual / jac_point, which round
+// differently by design: see there.)
 __device__ inline bool div_safe(double x, double y, double z);
 __device__ inline double div_rcp(double d);
 __device__ inline double div_by(double n, double d, double y);
-__device__ inline void pose_edge_error(const double* pose, const double X[3], double o0, double o1, const Cam& c,
+__device__ inline void pose_edge_error(const double* pose, const double X[3], double o0, double o1, const CamD& c,
                                        double pc[3], double& e0, double& e1)
 {
     se3_map(pose, X, pc);
@@ -243,20 +108,6 @@ __device__ inline void pose_edge_error(const double* pose, const double X[3], do
     }
     e0 = o0 - u;
     e1 = o1 - v;
-}
-
-// RobustKernelHuber::robustify (robust_kernel_impl.cpp:78-91)
-__device__ inline void huber2(double e2, double delta, double& rho0, double& rho1)
-{
-    const double dsqr = delta * delta;
-    if (e2 <= dsqr) {
-        rho0 = e2;
-        rho1 = 1.;
-    } else {
-        const double sq = sqrt(e2);
-        rho0 = 2 * sq * delta - dsqr;
-        rho1 = delta / sq;
-    }
 }
 
 // Double division with the reciprocal shared between quotients of one
@@ -303,7 +154,7 @@ __device__ inline bool div_safe(double x, double y, double z)
 // (they start at +0.0, and round-to-nearest never makes -0.0 of it), so each
 // term adds the same value to every sum as g2o's.  Elsewhere the original
 // expressions, division by division.
-__device__ inline void pose_edge_terms(const double* pose, const Cam& cam, double delta, float fo0, float fo1, float fis,
+__device__ inline void pose_edge_terms(const double* pose, const CamD& cam, double delta, float fo0, float fo1, float fis,
                                        float fx_, float fy_, float fz_, double (&c)[28])
 {
     const double X[3] = {(double)fx_, (double)fy_, (double)fz_};
@@ -318,7 +169,7 @@ __device__ inline void pose_edge_terms(const double* pose, const Cam& cam, doubl
         er0 = (double)fo0 - (x_z * cam.fx + cam.cx);
         er1 = (double)fo1 - (y_z * cam.fy + cam.cy);
         double rho0, rho1;
-        huber2(er0 * (s * er0) + er1 * (s * er1), delta, rho0, rho1);
+        huber(er0 * (s * er0) + er1 * (s * er1), delta, rho0, rho1);
         c[0] = rho0;
         const double fx = cam.fx, fy = cam.fy;
         const double xy_z2 = div_by(x * y, z_2, yz2);
@@ -358,7 +209,7 @@ __device__ inline void pose_edge_terms(const double* pose, const Cam& cam, doubl
         er1 = (double)fo1 - v;
     }
     double rho0, rho1;
-    huber2(er0 * (s * er0) + er1 * (s * er1), delta, rho0, rho1);
+    huber(er0 * (s * er0) + er1 * (s * er1), delta, rho0, rho1);
     c[0] = rho0;
     const double x = pc[0], y = pc[1], z = pc[2], z_2 = z * z;
     const double fx = cam.fx, fy = cam.fy;
@@ -424,7 +275,7 @@ __global__ __launch_bounds__(kW == 1 ? kPoseThreads : 64 * kW) void k_pose_opt(c
     const PoseHdr& H = hdrs[prob];
     const long long e0 = H.e0;
     const int nE = H.nE;
-    const Cam cam{(double)H.cam[0], (double)H.cam[1], (double)H.cam[2], (double)H.cam[3]};
+    const CamD cam{(double)H.cam[0], (double)H.cam[1], (double)H.cam[2], (double)H.cam[3]};
     // Converter::toSE3Quat (src/Converter.cc:38-48)
     double pose[7], errpose[7];
     {
@@ -618,8 +469,7 @@ __global__ __launch_bounds__(kW == 1 ? kPoseThreads : 64 * kW) void k_pose_opt(c
         double r_chi = 0;
         rounds = it + 1;
         if (n_active > 0) {
-            double lambda = 0, ni = 2;
-            int nBadLM = 0;
+            LmState lm{0, 2, 0};
             // kExact: a trial pass sums the whole system at the trial pose
             // (lane q holds sum q), which the next iteration takes when the
             // trial is accepted -- the sums computeActiveErrors + buildSystem
@@ -642,11 +492,11 @@ __global__ __launch_bounds__(kW == 1 ? kPoseThreads : 64 * kW) void k_pose_opt(c
                             pose_edge_terms(pose, cam, delta, fo0, fo1, fis, fx_, fy_, fz_, c);
                         });
                     have_sys = false;
-                    currentChi = lane_f64(sys_sum, 0);
+                    currentChi = readlane_f64(sys_sum, 0);
 #pragma unroll
-                    for (int k = 0; k < 21; k++) h[k] = lane_f64(sys_sum, 1 + k);
+                    for (int k = 0; k < 21; k++) h[k] = readlane_f64(sys_sum, 1 + k);
 #pragma unroll
-                    for (int k = 0; k < 6; k++) bv[k] = lane_f64(sys_sum, 22 + k);
+                    for (int k = 0; k < 6; k++) bv[k] = readlane_f64(sys_sum, 22 + k);
                 } else {
                 for_edges([&](float fo0, float fo1, float fis, float fx_, float fy_, float fz_) {
                     // computeError, the Huber kernel, linearizeOplus's pose
@@ -678,13 +528,11 @@ __global__ __launch_bounds__(kW == 1 ? kPoseThreads : 64 * kW) void k_pose_opt(c
                 currentChi = chi;
                 }
                 const double iniChi = currentChi;
-                if (iter == 0) {   // computeLambdaInit (levenberg.cpp:166-180)
+                if (iter == 0) {
                     double mx = 0;
 #pragma unroll
-                    for (int j = 0; j < 6; j++) mx = fmax(fabs(h[LT(j, j)]), mx);
-                    lambda = 1e-5 * mx;
-                    ni = 2;
-                    nBadLM = 0;
+                    for (int j = 0; j < 6; j++) mx = fmax(fabs(h[lt_idx(j, j)]), mx);
+                    lm_init(lm, mx);
                 }
                 double rho = 0;
                 int qmax = 0;
@@ -697,8 +545,8 @@ __global__ __launch_bounds__(kW == 1 ? kPoseThreads : 64 * kW) void k_pose_opt(c
 #pragma unroll
                         for (int k = 0; k < 21; k++) m[k] = h[k];
 #pragma unroll
-                        for (int j = 0; j < 6; j++) m[LT(j, j)] += lambda;
-                        ok2 = ldlt6_solve(m, bv, xs);
+                        for (int j = 0; j < 6; j++) m[lt_idx(j, j)] += lm.lambda;
+                        ok2 = ldlt_solve<6>(m, bv, xs);
 #pragma unroll
                         for (int i = 0; i < 7; i++) tp[i] = pose[i];
                         if (ok2) {
@@ -732,7 +580,7 @@ __global__ __launch_bounds__(kW == 1 ? kPoseThreads : 64 * kW) void k_pose_opt(c
                         double pc[3], er0, er1;
                         pose_edge_error(tp, X, (double)fo0, (double)fo1, cam, pc, er0, er1);
                         double rho0, rho1;
-                        huber2(er0 * (s * er0) + er1 * (s * er1), delta, rho0, rho1);
+                        huber(er0 * (s * er0) + er1 * (s * er1), delta, rho0, rho1);
                         return rho0;
                     };
                     double tempChi, tsum = 0;
@@ -741,7 +589,7 @@ __global__ __launch_bounds__(kW == 1 ? kPoseThreads : 64 * kW) void k_pose_opt(c
                                                 double (&c)[28]) {
                             pose_edge_terms(tp, cam, delta, fo0, fo1, fis, fx_, fy_, fz_, c);
                         });
-                        tempChi = lane_f64(tsum, 0);
+                        tempChi = readlane_f64(tsum, 0);
                     } else {
                         double tchi = 0;
                         for_edges([&](float fo0, float fo1, float fis, float fx_, float fy_, float fz_) {
@@ -752,37 +600,22 @@ __global__ __launch_bounds__(kW == 1 ? kPoseThreads : 64 * kW) void k_pose_opt(c
                     }
 #pragma unroll
                     for (int i = 0; i < 7; i++) errpose[i] = tp[i];
-                    if (!ok2) tempChi = 1.79769313486231570815e+308;
-                    double scale = 0;
-#pragma unroll
-                    for (int j = 0; j < 6; j++) scale += xs[j] * (lambda * xs[j] + bv[j]);
-                    scale += 1e-3;
-                    rho = (currentChi - tempChi) / scale;
-                    if (rho > 0 && isfinite(tempChi)) {
-                        double alpha = 1. - pow((2 * rho - 1), 3);
-                        alpha = fmin(alpha, 2. / 3.);
-                        lambda *= fmax(1. / 3., alpha);
-                        ni = 2;
-                        currentChi = tempChi;
+                    const LmTrial trial = lm_trial(lm, currentChi, tempChi, ok2, lm_scale(xs, lm.lambda, bv));
+                    rho = trial.rho;
+                    if (trial.accept) {
 #pragma unroll
                         for (int i = 0; i < 7; i++) pose[i] = tp[i];
                         if constexpr (kExact) {
                             sys_sum = tsum;
                             have_sys = true;
                         }
-                    } else {
-                        lambda *= ni;
-                        ni *= 2;
                     }
                     qmax++;
-                } while (rho < 0 && qmax < 10);
+                } while (lm_retry(rho, qmax));
                 r_iters++;
                 r_trials += qmax;
                 r_chi = currentChi;
-                if (qmax == 10 || rho == 0) break;
-                if ((iniChi - currentChi) * 1e3 < iniChi) nBadLM++;
-                else nBadLM = 0;
-                if (nBadLM >= 3) break;
+                if (lm_stop(lm, qmax, rho, iniChi, currentChi)) break;
             }
         }
         // outlier classification (src/Optimizer.cc:243-265)
@@ -915,7 +748,7 @@ __global__ __launch_bounds__(kPxThreads) void k_pose_exact_wide(const PoseHdr* _
     const PoseHdr& H = hdrs[prob];
     const long long e0 = H.e0;
     const int nE = H.nE;
-    const Cam cam{(double)H.cam[0], (double)H.cam[1], (double)H.cam[2], (double)H.cam[3]};
+    const CamD cam{(double)H.cam[0], (double)H.cam[1], (double)H.cam[2], (double)H.cam[3]};
     double pose[7], errpose[7];
     {
         double R[9];
@@ -1076,8 +909,7 @@ __global__ __launch_bounds__(kPxThreads) void k_pose_exact_wide(const PoseHdr* _
         double r_chi = 0;
         rounds = it + 1;
         if (n_active > 0) {
-            double lambda = 0, ni = 2;
-            int nBadLM = 0;
+            LmState lm{0, 2, 0};
             // the system at `pose` (chi2, H, b): built at the round's start; a
             // trial pass builds it at the trial pose too, which the next
             // iteration uses when the trial is accepted -- the same sums in
@@ -1102,13 +934,11 @@ __global__ __launch_bounds__(kPxThreads) void k_pose_exact_wide(const PoseHdr* _
                 }
                 have_sys = false;
                 const double iniChi = currentChi;
-                if (iter == 0) {   // computeLambdaInit (levenberg.cpp:166-180)
+                if (iter == 0) {
                     double mx = 0;
 #pragma unroll
-                    for (int j = 0; j < 6; j++) mx = fmax(fabs(h[LT(j, j)]), mx);
-                    lambda = 1e-5 * mx;
-                    ni = 2;
-                    nBadLM = 0;
+                    for (int j = 0; j < 6; j++) mx = fmax(fabs(h[lt_idx(j, j)]), mx);
+                    lm_init(lm, mx);
                 }
                 double rho = 0;
                 int qmax = 0;
@@ -1122,11 +952,11 @@ __global__ __launch_bounds__(kPxThreads) void k_pose_exact_wide(const PoseHdr* _
 #pragma unroll
                         for (int k = 0; k < 21; k++) m[k] = h[k];
 #pragma unroll
-                        for (int j = 0; j < 6; j++) m[LT(j, j)] += lambda;
+                        for (int j = 0; j < 6; j++) m[lt_idx(j, j)] += lm.lambda;
 #ifdef ORBX_POSE_PROFILE
                         const unsigned long long t_l0 = wall_clock64();
 #endif
-                        const bool ok = ldlt6_solve(m, bv, xs);
+                        const bool ok = ldlt_solve<6>(m, bv, xs);
 #pragma unroll
                         for (int i = 0; i < 7; i++) tp[i] = pose[i];
 #ifdef ORBX_POSE_PROFILE
@@ -1167,18 +997,9 @@ __global__ __launch_bounds__(kPxThreads) void k_pose_exact_wide(const PoseHdr* _
                     PX_ACC(2, _px_t0);
 #pragma unroll
                     for (int i = 0; i < 7; i++) errpose[i] = tp[i];
-                    if (!ok2) tempChi = 1.79769313486231570815e+308;
-                    double scale = 0;
-#pragma unroll
-                    for (int j = 0; j < 6; j++) scale += xs[j] * (lambda * xs[j] + bv[j]);
-                    scale += 1e-3;
-                    rho = (currentChi - tempChi) / scale;
-                    if (rho > 0 && isfinite(tempChi)) {
-                        double alpha = 1. - pow((2 * rho - 1), 3);
-                        alpha = fmin(alpha, 2. / 3.);
-                        lambda *= fmax(1. / 3., alpha);
-                        ni = 2;
-                        currentChi = tempChi;
+                    const LmTrial trial = lm_trial(lm, currentChi, tempChi, ok2, lm_scale(xs, lm.lambda, bv));
+                    rho = trial.rho;
+                    if (trial.accept) {
 #pragma unroll
                         for (int i = 0; i < 7; i++) pose[i] = tp[i];
                         // the trial pass's system (s_sum stays until the
@@ -1188,19 +1009,13 @@ __global__ __launch_bounds__(kPxThreads) void k_pose_exact_wide(const PoseHdr* _
 #pragma unroll
                         for (int k = 0; k < 6; k++) bv[k] = s_sum[22 + k];
                         have_sys = true;
-                    } else {
-                        lambda *= ni;
-                        ni *= 2;
                     }
                     qmax++;
-                } while (rho < 0 && qmax < 10);
+                } while (lm_retry(rho, qmax));
                 r_iters++;
                 r_trials += qmax;
                 r_chi = currentChi;
-                if (qmax == 10 || rho == 0) break;
-                if ((iniChi - currentChi) * 1e3 < iniChi) nBadLM++;
-                else nBadLM = 0;
-                if (nBadLM >= 3) break;
+                if (lm_stop(lm, qmax, rho, iniChi, currentChi)) break;
             }
         }
         // outlier classification (src/Optimizer.cc:243-265)

@@ -49,6 +49,7 @@
 
 #include "orbx_device.h"
 #include "orbx_internal.h"
+#include "orbx_lm.h"
 #include "orbx_match_common.h"
 #include "orbx_se3.h"
 #include "orbx_stage.h"
@@ -211,12 +212,8 @@ __device__ inline void sim3_inverse(const double a[8], double o[8])
     o[7] = 1. / a[7];
 }
 
-struct SoCam {
-    double fx, fy, cx, cy;
-};
-
 // obs - cam_map(project(S.map(X))) (types_seven_dof_expmap.h:138-167)
-__device__ inline void sim3_edge_error(const double* S, const double X[3], double o0, double o1, const SoCam& c,
+__device__ inline void sim3_edge_error(const double* S, const double X[3], double o0, double o1, const CamD& c,
                                        double& e0, double& e1)
 {
     const Q q{S[0], S[1], S[2], S[3]};
@@ -228,123 +225,11 @@ __device__ inline void sim3_edge_error(const double* S, const double X[3], doubl
     e1 = o1 - (y / z * c.fy + c.cy);
 }
 
-// RobustKernelHuber::robustify (robust_kernel_impl.cpp:78-91)
-__device__ inline void so_huber(double e2, double delta, double& rho0, double& rho1)
-{
-    const double dsqr = delta * delta;
-    if (e2 <= dsqr) {
-        rho0 = e2;
-        rho1 = 1.;
-    } else {
-        const double sq = sqrt(e2);
-        rho0 = 2 * sq * delta - dsqr;
-        rho1 = delta / sq;
-    }
-}
-
-// Packed lower triangle: entry (i, j), j <= i, at i (i + 1) / 2 + j.
-#define SO_LT(i, j) ((i) * ((i) + 1) / 2 + (j))
-
-// Eigen::LDLT<MatrixXd> of the lower triangle of m (packed, N x N) and the
-// solve of m x = b: the algorithm of orbx_pose.hip's ldlt6_solve for any N,
-// every index a compile-time constant (the runtime pivot selects among
-// unrolled swap variants), so the matrix stays in registers.
-template <int N>
-__device__ inline bool ldlt_solve(double (&m)[N * (N + 1) / 2], const double (&b)[N], double (&x)[N])
-{
-    int tr[N];
-    double temp[N];
-    int sign = 0;   // 0 zero, 1 positive semidefinite, 2 negative semidefinite, 3 indefinite
-    auto swap_d = [](double& a, double& c) {
-        const double t = a;
-        a = c;
-        c = t;
-    };
-#pragma unroll
-    for (int k = 0; k < N; k++) {
-        int big = k;
-        double bv = fabs(m[SO_LT(k, k)]);
-#pragma unroll
-        for (int i = k + 1; i < N; i++)
-            if (fabs(m[SO_LT(i, i)]) > bv) {
-                bv = fabs(m[SO_LT(i, i)]);
-                big = i;
-            }
-        tr[k] = big;
-#pragma unroll
-        for (int q = k + 1; q < N; q++) {
-            if (big == q) {
-#pragma unroll
-                for (int j = 0; j < k; j++) swap_d(m[SO_LT(k, j)], m[SO_LT(q, j)]);
-#pragma unroll
-                for (int i = q + 1; i < N; i++) swap_d(m[SO_LT(i, k)], m[SO_LT(i, q)]);
-                swap_d(m[SO_LT(k, k)], m[SO_LT(q, q)]);
-#pragma unroll
-                for (int i = k + 1; i < q; i++) swap_d(m[SO_LT(i, k)], m[SO_LT(q, i)]);
-            }
-        }
-        if (k > 0) {
-#pragma unroll
-            for (int j = 0; j < k; j++) temp[j] = m[SO_LT(j, j)] * m[SO_LT(k, j)];
-            double acc = m[SO_LT(k, 0)] * temp[0];
-#pragma unroll
-            for (int j = 1; j < k; j++) acc += m[SO_LT(k, j)] * temp[j];
-            m[SO_LT(k, k)] -= acc;
-#pragma unroll
-            for (int i = k + 1; i < N; i++)
-#pragma unroll
-                for (int j = 0; j < k; j++) m[SO_LT(i, k)] -= m[SO_LT(i, j)] * temp[j];
-        }
-        const double akk = m[SO_LT(k, k)];
-        if (k < N - 1 && fabs(akk) > 0.0) {
-#pragma unroll
-            for (int i = k + 1; i < N; i++) m[SO_LT(i, k)] /= akk;
-        }
-        if (sign == 1) {
-            if (akk < 0) sign = 3;
-        } else if (sign == 2) {
-            if (akk > 0) sign = 3;
-        } else if (sign == 0) {
-            if (akk > 0) sign = 1;
-            else if (akk < 0) sign = 2;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < N; i++) x[i] = b[i];
-#pragma unroll
-    for (int k = 0; k < N; k++)
-#pragma unroll
-        for (int q = k + 1; q < N; q++)
-            if (tr[k] == q) swap_d(x[k], x[q]);
-#pragma unroll
-    for (int i = 0; i < N; i++)
-#pragma unroll
-        for (int j = 0; j < i; j++) x[i] -= m[SO_LT(i, j)] * x[j];
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-        if (fabs(m[SO_LT(i, i)]) > 2.2250738585072014e-308) x[i] /= m[SO_LT(i, i)];
-        else x[i] = 0.0;
-    }
-#pragma unroll
-    for (int i = N - 2; i >= 0; i--) {
-        double s = m[SO_LT(i + 1, i)] * x[i + 1];
-#pragma unroll
-        for (int j = i + 2; j < N; j++) s += m[SO_LT(j, i)] * x[j];
-        x[i] -= s;
-    }
-#pragma unroll
-    for (int k = N - 1; k >= 0; k--)
-#pragma unroll
-        for (int q = k + 1; q < N; q++)
-            if (tr[k] == q) swap_d(x[k], x[q]);
-    return sign == 1 || sign == 0;
-}
-
 // One edge's 36 terms at the 15 estimates S[0..14] (LDS): computeError, the
 // central differences of BaseBinaryEdge::linearizeOplus, robustify and
 // constructQuadraticForm's products for the Sim3 vertex
 // (base_binary_edge.hpp:91-113), written to row[0, 36).
-__device__ inline void so_edge_terms(const double (*S)[8], const double X[3], double o0, double o1, const SoCam& cam,
+__device__ inline void so_edge_terms(const double (*S)[8], const double X[3], double o0, double o1, const CamD& cam,
                                      double info, double delta, double* row, bool tap, double* tap_err, double* tap_J)
 {
     constexpr double scalar = 1.0 / (2 * kSoDelta);
@@ -368,7 +253,7 @@ __device__ inline void so_edge_terms(const double (*S)[8], const double X[3], do
         }
     }
     double rho0, rho1;
-    so_huber(er0 * (info * er0) + er1 * (info * er1), delta, rho0, rho1);
+    huber(er0 * (info * er0) + er1 * (info * er1), delta, rho0, rho1);
     row[0] = rho0;
     const double w = rho1 * info;
     const double om0 = -(info * er0) * rho1, om1 = -(info * er1) * rho1;
@@ -405,8 +290,8 @@ __global__ __launch_bounds__(64 * kW) void k_sim3_opt(const Sim3OptProb* __restr
     double* tap_err = reinterpret_cast<double*>(blk + L.o_err);
     double* tap_J = reinterpret_cast<double*>(blk + L.o_J);
     double* tap_chi = reinterpret_cast<double*>(blk + L.o_chi);
-    const SoCam cam1{(double)P.cam1[0], (double)P.cam1[1], (double)P.cam1[2], (double)P.cam1[3]};
-    const SoCam cam2{(double)P.cam2[0], (double)P.cam2[1], (double)P.cam2[2], (double)P.cam2[3]};
+    const CamD cam1{(double)P.cam1[0], (double)P.cam1[1], (double)P.cam1[2], (double)P.cam1[3]};
+    const CamD cam2{(double)P.cam2[0], (double)P.cam2[1], (double)P.cam2[2], (double)P.cam2[3]};
     const double delta = P.delta;
     const double th2 = (double)P.th2;
 
@@ -521,8 +406,8 @@ __global__ __launch_bounds__(64 * kW) void k_sim3_opt(const Sim3OptProb* __restr
 #pragma unroll 1
     for (int round = 0; round < 2 && n > 0; round++) {
         const int its = round == 0 ? 5 : (n_bad > 0 ? 10 : 5);   // nMoreIterations (:951-955)
-        double lambda = 0, ni = 2;
-        int nBadLM = 0, iters = 0, trials = 0, npd = 0;
+        LmState lm{0, 2, 0};
+        int iters = 0, trials = 0, npd = 0;
 #pragma unroll 1
         for (int iter = 0; iter < its; iter++) {
             // the 15 estimates of the linearisation and their inverses, a lane each
@@ -566,13 +451,11 @@ __global__ __launch_bounds__(64 * kW) void k_sim3_opt(const Sim3OptProb* __restr
             for (int k = 0; k < 7; k++) bv[k] = s_sum[29 + k];
             __syncthreads();   // s_sum is written again by the trial pass
             const double iniChi = currentChi;
-            if (iter == 0) {   // computeLambdaInit (levenberg.cpp:166-180)
+            if (iter == 0) {
                 double mx = 0;
 #pragma unroll
-                for (int j = 0; j < 7; j++) mx = fmax(fabs(h[SO_LT(j, j)]), mx);
-                lambda = 1e-5 * mx;
-                ni = 2;
-                nBadLM = 0;
+                for (int j = 0; j < 7; j++) mx = fmax(fabs(h[lt_idx(j, j)]), mx);
+                lm_init(lm, mx);
             }
             Sim3OptIter* rec = tap_it + min(n_lm, kSoLm - 1);
             if (taps && tid == 0) {
@@ -591,7 +474,7 @@ __global__ __launch_bounds__(64 * kW) void k_sim3_opt(const Sim3OptProb* __restr
 #pragma unroll
                 for (int k = 0; k < 28; k++) m[k] = h[k];
 #pragma unroll
-                for (int j = 0; j < 7; j++) m[SO_LT(j, j)] += lambda;
+                for (int j = 0; j < 7; j++) m[lt_idx(j, j)] += lm.lambda;
                 const bool ok2 = ldlt_solve<7>(m, bv, xs);
                 if (ok2) {   // VertexSim3Expmap::oplusImpl: Sim3(update) * estimate
                     double ex[8];
@@ -623,45 +506,30 @@ __global__ __launch_bounds__(64 * kW) void k_sim3_opt(const Sim3OptProb* __restr
                     double X1[3], X2[3], o[4], w[2], e0, e1, rho1;
                     load_pair(c, X1, X2, o, w);
                     sim3_edge_error(s_est[0], X2, o[0], o[1], cam1, e0, e1);
-                    so_huber(e0 * (w[0] * e0) + e1 * (w[0] * e1), delta, row[0], rho1);
+                    huber(e0 * (w[0] * e0) + e1 * (w[0] * e1), delta, row[0], rho1);
                     sim3_edge_error(s_inv[0], X1, o[2], o[3], cam2, e0, e1);
-                    so_huber(e0 * (w[1] * e0) + e1 * (w[1] * e1), delta, row[kSoTerms], rho1);
+                    huber(e0 * (w[1] * e0) + e1 * (w[1] * e1), delta, row[kSoTerms], rho1);
                 });
                 double tempChi = s_sum[0];
                 __syncthreads();
 #pragma unroll
                 for (int i = 0; i < 8; i++) errest[i] = te[i];
-                if (!ok2) tempChi = 1.79769313486231570815e+308;
-                double scale = 0;
-#pragma unroll
-                for (int j = 0; j < 7; j++) scale += xs[j] * (lambda * xs[j] + bv[j]);
-                scale += 1e-3;
-                rho = (currentChi - tempChi) / scale;
-                if (rho > 0 && isfinite(tempChi)) {
-                    double alpha = 1. - pow((2 * rho - 1), 3);
-                    alpha = fmin(alpha, 2. / 3.);
-                    lambda *= fmax(1. / 3., alpha);
-                    ni = 2;
-                    currentChi = tempChi;
+                const LmTrial trial = lm_trial(lm, currentChi, tempChi, ok2, lm_scale(xs, lm.lambda, bv));
+                rho = trial.rho;
+                if (trial.accept) {
 #pragma unroll
                     for (int i = 0; i < 8; i++) est[i] = te[i];
-                } else {
-                    lambda *= ni;
-                    ni *= 2;
                 }
                 qmax++;
-            } while (rho < 0 && qmax < 10);
+            } while (lm_retry(rho, qmax));
             if (taps && tid == 0) {
-                rec->lambda = lambda;
+                rec->lambda = lm.lambda;
                 rec->trials = qmax;
             }
             iters++;
             n_lm++;
             trials += qmax;
-            if (qmax == 10 || rho == 0) break;
-            if ((iniChi - currentChi) * 1e3 < iniChi) nBadLM++;
-            else nBadLM = 0;
-            if (nBadLM >= 3) break;
+            if (lm_stop(lm, qmax, rho, iniChi, currentChi)) break;
         }
         if (tid == 0) {
             hdr->iters[round] = iters;

@@ -261,7 +261,7 @@ def stored_chi2(est, pb):
 def ldlt_solve(H, b):
     """Eigen::LDLT<MatrixXd> (lower, diagonal pivoting) of the symmetric H
     (n x n, the lower triangle is read) and the solve of H x = b: (isPositive,
-    x).  The algorithm of the device's ldlt6_solve / ldlt7_solve."""
+    x).  The algorithm of the device's ldlt_solve<N> (orbx_lm.h)."""
     n = len(b)
     m = [[float(H[i][j]) if j <= i else 0.0 for j in range(n)] for i in range(n)]
     tr, sign = [0] * n, 0
