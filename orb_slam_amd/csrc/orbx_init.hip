@@ -160,47 +160,10 @@ __global__ __launch_bounds__(256) void k_init_prepare(const orbx_keypoint* __res
 // (B V = U S), the column of the smallest norm dropped.
 __device__ inline void rank2_3x3(const float* fpre, float* fn)
 {
-    double b[3][3], v[3][3];   // [column][row]
-#pragma unroll
-    for (int j = 0; j < 3; j++)
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            b[j][i] = (double)fpre[3 * i + j];
-            v[j][i] = i == j ? 1.0 : 0.0;
-        }
-    double floor = 0.0;
-#pragma unroll
-    for (int j = 0; j < 3; j++) floor += b[j][0] * b[j][0] + b[j][1] * b[j][1] + b[j][2] * b[j][2];
-    floor *= kInitFloor;
-    for (int sweep = 0; sweep < kInitSweeps; sweep++) {
-        bool rot = false;
-#pragma unroll
-        for (int p = 0; p < 2; p++)
-#pragma unroll
-            for (int q = p + 1; q < 3; q++) {
-                const double al = b[p][0] * b[p][0] + b[p][1] * b[p][1] + b[p][2] * b[p][2];
-                const double be = b[q][0] * b[q][0] + b[q][1] * b[q][1] + b[q][2] * b[q][2];
-                const double ga = b[p][0] * b[q][0] + b[p][1] * b[q][1] + b[p][2] * b[q][2];
-                if (jacobi_wants(al, be, ga, floor)) {
-                    rot = true;
-                    double c, s;
-                    jacobi_cs(al, be, ga, c, s);
-#pragma unroll
-                    for (int i = 0; i < 3; i++) {
-                        const double bp = b[p][i], bq = b[q][i];
-                        b[p][i] = c * bp - s * bq;
-                        b[q][i] = s * bp + c * bq;
-                        const double vp = v[p][i], vq = v[q][i];
-                        v[p][i] = c * vp - s * vq;
-                        v[q][i] = s * vp + c * vq;
-                    }
-                }
-            }
-        if (!rot) break;
-    }
+    const JacobiCols<3> m = hestenes(load_cols<3>(fpre));
     double nrm[3];
 #pragma unroll
-    for (int j = 0; j < 3; j++) nrm[j] = b[j][0] * b[j][0] + b[j][1] * b[j][1] + b[j][2] * b[j][2];
+    for (int j = 0; j < 3; j++) nrm[j] = col_dot(m.a[j], m.a[j]);
     int kmin = 0;
     if (nrm[1] < nrm[kmin]) kmin = 1;
     if (nrm[2] < nrm[kmin]) kmin = 2;
@@ -211,7 +174,7 @@ __device__ inline void rank2_3x3(const float* fpre, float* fn)
             double acc = 0.0;
 #pragma unroll
             for (int k = 0; k < 3; k++)
-                if (k != kmin) acc += b[k][i] * v[k][j];
+                if (k != kmin) acc += m.a[k][i] * m.v[k][j];
             fn[3 * i + j] = (float)acc;
         }
 }
@@ -314,14 +277,13 @@ __global__ __launch_bounds__(256) void k_init_solve(const InitPair* __restrict__
                 const double ga = row_sum16(a[p] * a[q]);
                 if (jacobi_wants(al, be, ga, floor)) {
                     rot = true;
-                    double c, s;
-                    jacobi_cs(al, be, ga, c, s);
+                    const JacobiRot g = jacobi_cs(al, be, ga);
                     const double ap = a[p], aq = a[q];
-                    a[p] = c * ap - s * aq;
-                    a[q] = s * ap + c * aq;
+                    a[p] = g.c * ap - g.s * aq;
+                    a[q] = g.s * ap + g.c * aq;
                     const double vp = v[p], vq = v[q];
-                    v[p] = c * vp - s * vq;
-                    v[q] = s * vp + c * vq;
+                    v[p] = g.c * vp - g.s * vq;
+                    v[q] = g.s * vp + g.c * vq;
                 }
             }
         if (!__any(rot)) break;

@@ -52,49 +52,13 @@ struct TriJob {
 // translation is added to that double, the assignment rounds (:322, :332).
 __device__ inline float cam_coord(const TriGeom& g, int r, const float* x)
 {
-    double d = (double)g.Rcw[3 * r] * (double)x[0];
-    d = d + (double)g.Rcw[3 * r + 1] * (double)x[1];
-    d = d + (double)g.Rcw[3 * r + 2] * (double)x[2];
-    return (float)(d + (double)g.tcw[r]);
-}
-
-// ray = Rwc * xn (:294): OpenCV's float gemm accumulates each entry in double.
-__device__ inline void ray_of(const TriGeom& g, const float* xn, float* ray)
-{
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        double d = (double)g.Rcw[i] * (double)xn[0];
-        d = d + (double)g.Rcw[3 + i] * (double)xn[1];
-        d = d + (double)g.Rcw[6 + i] * (double)xn[2];
-        ray[i] = (float)d;
-    }
-}
-
-__device__ inline double norm3(const float* x)
-{
-    double s = (double)x[0] * (double)x[0];
-    s = s + (double)x[1] * (double)x[1];
-    s = s + (double)x[2] * (double)x[2];
-    return sqrt(s);
+    return affine3(g.Rcw + 3 * r, x, g.tcw[r]);
 }
 
 // The reprojection gate of one keyframe (:331-340, :343-352): true = rejected.
 __device__ inline bool reproj_rejects(const TriGeom& g, const orbx_keypoint& kp, const float* x3D, float z, int contract)
 {
-    const float x = cam_coord(g, 0, x3D);
-    const float y = cam_coord(g, 1, x3D);
-    const float invz = (float)(1.0 / (double)z);
-    float u, v;
-    if (contract) {
-        u = fmaf(g.cam[0] * x, invz, g.cam[2]);
-        v = fmaf(g.cam[1] * y, invz, g.cam[3]);
-    } else {
-        u = g.cam[0] * x * invz + g.cam[2];
-        v = g.cam[1] * y * invz + g.cam[3];
-    }
-    const float ex = u - kp.x;
-    const float ey = v - kp.y;
-    const float e2 = contract ? fmaf(ex, ex, ey * ey) : ex * ex + ey * ey;
+    const float e2 = reproj_e2(g.cam, cam_coord(g, 0, x3D), cam_coord(g, 1, x3D), z, kp.x, kp.y, contract);
     return (double)e2 > 5.991 * (double)g.sigma2[kp.octave];
 }
 
@@ -110,12 +74,10 @@ __device__ inline int triangulate_match(const TriGeom& g1, const TriGeom& g2, co
     const float xn1[3] = {(kp1.x - g1.cam[2]) * invfx1, (kp1.y - g1.cam[3]) * invfy1, 1.0f};
     const float xn2[3] = {(kp2.x - g2.cam[2]) * invfx2, (kp2.y - g2.cam[3]) * invfy2, 1.0f};
     float ray1[3], ray2[3];
-    ray_of(g1, xn1, ray1);
-    ray_of(g2, xn2, ray2);
-    double dot = (double)ray1[0] * (double)ray2[0];
-    dot = dot + (double)ray1[1] * (double)ray2[1];
-    dot = dot + (double)ray1[2] * (double)ray2[2];
-    const float cosv = (float)(dot / (norm3(ray1) * norm3(ray2)));
+    tmatvec3(g1.Rcw, xn1, ray1);   // ray = Rwc * xn (:294)
+    tmatvec3(g2.Rcw, xn2, ray2);
+    // the quotient by the double product of the norms (reconstruction divides by the float product)
+    const float cosv = (float)(dot3(ray1, ray2) / (norm3(ray1) * norm3(ray2)));
     if (cosv < 0.f || (double)cosv > 0.9998) return 2;
 
     // A.row(0) = xn1(0) * Tcw1.row(2) - Tcw1.row(0), ... (:303-307)

@@ -234,7 +234,7 @@ __device__ inline void svd_cols(double* A, int m, int n, double* V)
         bool rot = false;
         for (int p = 0; p < n - 1; p++)
             for (int q = p + 1; q < n; q++) {
-                double al = 0.0, be = 0.0, ga = 0.0;
+                double al = 0.0, be = 0.0, ga = 0.0;   // from 0.0 over a run-time m: not col_dot's sums
                 for (int i = 0; i < m; i++) {
                     const double ap = A[i * n + p], aq = A[i * n + q];
                     al += ap * ap;
@@ -243,8 +243,8 @@ __device__ inline void svd_cols(double* A, int m, int n, double* V)
                 }
                 if (jacobi_wants(al, be, ga, floor)) {
                     rot = true;
-                    double c, s;
-                    jacobi_cs(al, be, ga, c, s);
+                    const JacobiRot g = jacobi_cs(al, be, ga);
+                    const double c = g.c, s = g.s;
                     for (int i = 0; i < m; i++) {
                         const double ap = A[i * n + p], aq = A[i * n + q];
                         A[i * n + p] = c * ap - s * aq;
@@ -288,14 +288,11 @@ __device__ inline void sym_eig(double* A, double* V, int n, int lane, int nl, bo
                     app = A[p * n + p];
                     aqq = A[q * n + q];
                 }
-                if (act && apq != 0.0 && apq * apq > floor) {
+                // act last: apq is 0.0 in an inactive group, and this order keeps the kernels' control flow
+                if (sym_wants(apq, floor) && act) {
                     rot = true;
-                    double zeta = (aqq - app) * fast_rcp(2.0 * apq);
-                    zeta = fmin(fmax(zeta, -1e100), 1e100);
-                    const double w = 1.0 + zeta * zeta;
-                    const double t = copysign(fast_rcp(fabs(zeta) + w * fast_rsq(w)), zeta);
-                    const double c = fast_rsq(1.0 + t * t);
-                    const double s = c * t;
+                    const JacobiRot g = jacobi_cs(app, aqq, apq);
+                    const double c = g.c, s = g.s, t = g.t;
                     for (int k = lane; k < n; k += nl) {
                         const double vp = V[p * n + k], vq = V[q * n + k];
                         V[p * n + k] = c * vp - s * vq;

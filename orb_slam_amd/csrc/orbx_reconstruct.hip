@@ -89,7 +89,7 @@ static RecLayout rec_layout(int cap)
 // ---------------------------------------------------------------------------
 // defined arithmetic of the hypotheses
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void rec_swap_cols(double (&b)[3][3], double (&v)[3][3], double (&n)[3], int p, int q)
+__device__ __forceinline__ void rec_swap_cols(JacobiCols<3>& m, double (&n)[3], int p, int q)
 {
     if (n[q] > n[p]) {
         const double t = n[p];
@@ -97,73 +97,36 @@ __device__ __forceinline__ void rec_swap_cols(double (&b)[3][3], double (&v)[3][
         n[q] = t;
 #pragma unroll
         for (int i = 0; i < 3; i++) {
-            const double tb = b[p][i], tv = v[p][i];
-            b[p][i] = b[q][i];
-            b[q][i] = tb;
-            v[p][i] = v[q][i];
-            v[q][i] = tv;
+            const double tb = m.a[p][i], tv = m.v[p][i];
+            m.a[p][i] = m.a[q][i];
+            m.a[q][i] = tb;
+            m.v[p][i] = m.v[q][i];
+            m.v[q][i] = tv;
         }
     }
 }
 
 // U (9), w (3), Vt (9) of a row-major float 3x3: one-sided Jacobi on its
-// columns in FP64 (M V = U S), singular values descending (equal ones in
-// column order), rounded once.  Where sigma3 <= kRecRankCut sigma1 -- always,
-// for an essential matrix formed in float -- the third column of U is the
-// cross product of the first two instead of a column of round-off divided by
-// its norm.
-__device__ inline void svd3(const float* m, float* out)
+// columns in FP64 (M V = U S, orbx_jacobi.h), singular values descending
+// (equal ones in column order), rounded once.  Where sigma3 <= kRecRankCut
+// sigma1 -- always, for an essential matrix formed in float -- the third
+// column of U is the cross product of the first two instead of a column of
+// round-off divided by its norm.
+__device__ inline void svd3(const float* mf, float* out)
 {
-    double b[3][3], v[3][3];   // [column][row]
-#pragma unroll
-    for (int j = 0; j < 3; j++)
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            b[j][i] = (double)m[3 * i + j];
-            v[j][i] = i == j ? 1.0 : 0.0;
-        }
-    double floor = 0.0;
-#pragma unroll
-    for (int j = 0; j < 3; j++) floor += b[j][0] * b[j][0] + b[j][1] * b[j][1] + b[j][2] * b[j][2];
-    floor *= kInitFloor;
-    for (int sweep = 0; sweep < kInitSweeps; sweep++) {
-        bool rot = false;
-#pragma unroll
-        for (int p = 0; p < 2; p++)
-#pragma unroll
-            for (int q = p + 1; q < 3; q++) {
-                const double al = b[p][0] * b[p][0] + b[p][1] * b[p][1] + b[p][2] * b[p][2];
-                const double be = b[q][0] * b[q][0] + b[q][1] * b[q][1] + b[q][2] * b[q][2];
-                const double ga = b[p][0] * b[q][0] + b[p][1] * b[q][1] + b[p][2] * b[q][2];
-                if (jacobi_wants(al, be, ga, floor)) {
-                    rot = true;
-                    double c, s;
-                    jacobi_cs(al, be, ga, c, s);
-#pragma unroll
-                    for (int i = 0; i < 3; i++) {
-                        const double bp = b[p][i], bq = b[q][i];
-                        b[p][i] = c * bp - s * bq;
-                        b[q][i] = s * bp + c * bq;
-                        const double vp = v[p][i], vq = v[q][i];
-                        v[p][i] = c * vp - s * vq;
-                        v[q][i] = s * vp + c * vq;
-                    }
-                }
-            }
-        if (!rot) break;
-    }
+    JacobiCols<3> m = hestenes(load_cols<3>(mf));
     double nrm[3];
 #pragma unroll
-    for (int j = 0; j < 3; j++) nrm[j] = b[j][0] * b[j][0] + b[j][1] * b[j][1] + b[j][2] * b[j][2];
-    rec_swap_cols(b, v, nrm, 0, 1);
-    rec_swap_cols(b, v, nrm, 1, 2);
-    rec_swap_cols(b, v, nrm, 0, 1);
+    for (int j = 0; j < 3; j++) nrm[j] = col_dot(m.a[j], m.a[j]);
+    rec_swap_cols(m, nrm, 0, 1);
+    rec_swap_cols(m, nrm, 1, 2);
+    rec_swap_cols(m, nrm, 0, 1);
     double s[3], u[3][3];
 #pragma unroll
     for (int j = 0; j < 3; j++) {
         s[j] = sqrt(nrm[j]);
 #pragma unroll
-        for (int i = 0; i < 3; i++) u[j][i] = b[j][i] / s[j];
+        for (int i = 0; i < 3; i++) u[j][i] = m.a[j][i] / s[j];
     }
     if (s[2] <= kRecRankCut * s[0]) {
         u[2][0] = u[0][1] * u[1][2] - u[0][2] * u[1][1];
@@ -175,62 +138,16 @@ __device__ inline void svd3(const float* m, float* out)
         out[9 + j] = (float)s[j];
 #pragma unroll
         for (int i = 0; i < 3; i++) {
-            out[3 * i + j] = (float)u[j][i];        // U's column j
-            out[12 + 3 * j + i] = (float)v[j][i];   // Vt's row j
+            out[3 * i + j] = (float)u[j][i];          // U's column j
+            out[12 + 3 * j + i] = (float)m.v[j][i];   // Vt's row j
         }
     }
-}
-
-// cv::determinant of a 3x3 float matrix, defined: FP64 cofactor expansion
-// along the first row, in inv3's order.
-__device__ inline double det3(const float* mf)
-{
-    double m[9];
-#pragma unroll
-    for (int i = 0; i < 9; i++) m[i] = (double)mf[i];
-    const double c0 = m[4] * m[8] - m[5] * m[7];
-    const double c3 = m[5] * m[6] - m[3] * m[8];
-    const double c6 = m[3] * m[7] - m[4] * m[6];
-    return (m[0] * c0 + m[1] * c3) + m[2] * c6;
-}
-
-// (s*a)*b of the MatExpr s*U*Rp*Vt: alpha times the FP64 sum, rounded once.
-__device__ inline void scaled_mul3(float s, const float* a, const float* b, float* out)
-{
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            double acc = (double)a[3 * i] * (double)b[j];
-            acc = acc + (double)a[3 * i + 1] * (double)b[3 + j];
-            acc = acc + (double)a[3 * i + 2] * (double)b[6 + j];
-            out[3 * i + j] = (float)((double)s * acc);
-        }
-}
-
-__device__ inline void matvec3(const float* m, const float* v, float* out)
-{
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        double acc = (double)m[3 * i] * (double)v[0];
-        acc = acc + (double)m[3 * i + 1] * (double)v[1];
-        acc = acc + (double)m[3 * i + 2] * (double)v[2];
-        out[i] = (float)acc;
-    }
-}
-
-__device__ inline double rec_norm3(const float* x)
-{
-    double s = (double)x[0] * (double)x[0];
-    s = s + (double)x[1] * (double)x[1];
-    s = s + (double)x[2] * (double)x[2];
-    return sqrt(s);
 }
 
 // t / cv::norm(t): a scaled convert with the float scale 1 / norm
 __device__ inline void unit3(float* t)
 {
-    const float sc = (float)(1.0 / rec_norm3(t));
+    const float sc = (float)(1.0 / norm3(t));
 #pragma unroll
     for (int i = 0; i < 3; i++) t[i] = t[i] * sc;
 }
@@ -248,18 +165,10 @@ __device__ inline void store_hyp(RecHdr* h, int k, const float* cam, const float
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const float r0 = j < 3 ? R[j] : t[0], r1 = j < 3 ? R[3 + j] : t[1], r2 = j < 3 ? R[6 + j] : t[2];
-            double acc = (double)K[3 * i] * (double)r0;
-            acc = acc + (double)K[3 * i + 1] * (double)r1;
-            acc = acc + (double)K[3 * i + 2] * (double)r2;
-            h->P2[12 * k + 4 * i + j] = (float)acc;
+            h->P2[12 * k + 4 * i + j] = (float)dot3(K + 3 * i, r0, r1, r2);
         }
 #pragma unroll
-    for (int i = 0; i < 3; i++) {
-        double acc = (double)R[i] * (double)t[0];
-        acc = acc + (double)R[3 + i] * (double)t[1];
-        acc = acc + (double)R[6 + i] * (double)t[2];
-        h->O2[3 * k + i] = (float)(-acc);
-    }
+    for (int i = 0; i < 3; i++) h->O2[3 * k + i] = (float)(-dot3(t, R[i], R[3 + i], R[6 + i]));
 }
 
 // ---------------------------------------------------------------------------
@@ -415,18 +324,7 @@ __global__ __launch_bounds__(64) void k_rec_hyp(const RecPair* __restrict__ desc
 // The reprojection gate of one image (:865-884): true = rejected.
 __device__ inline bool rec_reproj_rejects(const float* cam, const float* pt, float u, float v, float th2, int contract)
 {
-    const float invZ = (float)(1.0 / (double)pt[2]);
-    float imx, imy;
-    if (contract) {
-        imx = fmaf(cam[0] * pt[0], invZ, cam[2]);
-        imy = fmaf(cam[1] * pt[1], invZ, cam[3]);
-    } else {
-        imx = cam[0] * pt[0] * invZ + cam[2];
-        imy = cam[1] * pt[1] * invZ + cam[3];
-    }
-    const float ex = imx - u, ey = imy - v;
-    const float e2 = contract ? fmaf(ex, ex, ey * ey) : ex * ex + ey * ey;
-    return e2 > th2;
+    return reproj_e2(cam, pt[0], pt[1], pt[2], u, v, contract) > th2;
 }
 
 __global__ __launch_bounds__(256) void k_rec_check(const RecPair* __restrict__ descs, uint8_t* __restrict__ res,
@@ -475,24 +373,17 @@ __global__ __launch_bounds__(256) void k_rec_check(const RecPair* __restrict__ d
         x[2] = v4[2] * inv;
         bool alive = isfinite(x[0]) && isfinite(x[1]) && isfinite(x[2]);   // :839
         // parallax (:846-852); O1 = 0
-        const float dist1 = (float)rec_norm3(x);
+        const float dist1 = (float)norm3(x);
         const float n2[3] = {x[0] - O2[0], x[1] - O2[1], x[2] - O2[2]};
-        const float dist2 = (float)rec_norm3(n2);
-        double dot = (double)x[0] * (double)n2[0];
-        dot = dot + (double)x[1] * (double)n2[1];
-        dot = dot + (double)x[2] * (double)n2[2];
-        const float c = (float)(dot / (double)(dist1 * dist2));
+        const float dist2 = (float)norm3(n2);
+        // the quotient by the float product of the rounded norms (new points divide by the double product)
+        const float c = (float)(dot3(x, n2) / (double)(dist1 * dist2));
         const bool low = (double)c < 0.99998;
         if (x[2] <= 0.f && low) alive = false;                              // :855
         // p3dC2 = R*p3dC1+t (:859)
         float x2[3];
 #pragma unroll
-        for (int r = 0; r < 3; r++) {
-            double acc = (double)R[3 * r] * (double)x[0];
-            acc = acc + (double)R[3 * r + 1] * (double)x[1];
-            acc = acc + (double)R[3 * r + 2] * (double)x[2];
-            x2[r] = (float)(acc + (double)t[r]);
-        }
+        for (int r = 0; r < 3; r++) x2[r] = affine3(R + 3 * r, x, t[r]);
         if (x2[2] <= 0.f && low) alive = false;                             // :861
         if (rec_reproj_rejects(cam, x, m.x, m.y, h->th2, contract)) alive = false;    // :872
         if (rec_reproj_rejects(cam, x2, m.z, m.w, h->th2, contract)) alive = false;   // :883

@@ -32,6 +32,7 @@
 #include "orbx_device.h"
 #include "orbx_internal.h"
 #include "orbx_jacobi.h"
+#include "orbx_linalg.h"
 #include "orbx_stage.h"
 
 namespace orbx {
@@ -104,20 +105,11 @@ inline Sim3Layout sim3_layout(int M, int cap)
     return L;
 }
 
-// The defined float gemm: FP64 accumulation over k in order (rounded by the
-// caller, after the addend or the scalar where there is one).
-__device__ inline double dot3(const float* r, float x0, float x1, float x2)
-{
-    double acc = (double)r[0] * (double)x0;
-    acc = acc + (double)r[1] * (double)x1;
-    acc = acc + (double)r[2] * (double)x2;
-    return acc;
-}
-
 // fx*x+cx (:396, :416), the reference's own source: follows orbx_set_fp_contract
 __device__ inline float to_pixel(float f, float x, float c, int contract) { return contract ? fmaf(f, x, c) : f * x + c; }
 
-// FromCameraToImage / Project's tail (:392-396, :412-416)
+// FromCameraToImage / Project's tail (:392-396, :412-416).  Not reproj_e2's
+// projection: the divide is in float, and x meets 1/z before f.
 __device__ inline void cam_to_image(const float* cam, float X, float Y, float Z, int contract, float& u, float& v)
 {
     const float invz = 1.f / Z;
@@ -180,8 +172,8 @@ __global__ __launch_bounds__(256) void k_sim3_prepare(const Sim3Pair* __restrict
                 float ca[3], cb[3];
 #pragma unroll
                 for (int r = 0; r < 3; r++) {
-                    ca[r] = (float)(dot3(d.T1w + 4 * r, a[0], a[1], a[2]) + (double)d.T1w[4 * r + 3]);
-                    cb[r] = (float)(dot3(d.T2w + 4 * r, b[0], b[1], b[2]) + (double)d.T2w[4 * r + 3]);
+                    ca[r] = affine3(d.T1w + 4 * r, a, d.T1w[4 * r + 3]);
+                    cb[r] = affine3(d.T2w + 4 * r, b, d.T2w[4 * r + 3]);
                     x1[3 * pos + r] = ca[r];
                     x2[3 * pos + r] = cb[r];
                 }
@@ -272,14 +264,10 @@ __device__ inline void top_eigenvector4(const float* n, float* q)
 #pragma unroll
             for (int r = p + 1; r < 4; r++) {
                 const double apq = a[p][r];
-                if (apq != 0.0 && apq * apq > floor) {
+                if (sym_wants(apq, floor)) {
                     rot = true;
-                    double zeta = (a[r][r] - a[p][p]) * fast_rcp(2.0 * apq);
-                    zeta = fmin(fmax(zeta, -1e100), 1e100);
-                    const double w = 1.0 + zeta * zeta;
-                    const double t = copysign(fast_rcp(fabs(zeta) + w * fast_rsq(w)), zeta);
-                    const double c = fast_rsq(1.0 + t * t);
-                    const double s = c * t;
+                    const JacobiRot g = jacobi_cs(a[p][p], a[r][r], apq);
+                    const double c = g.c, s = g.s, t = g.t;
                     a[p][p] = a[p][p] - t * apq;
                     a[r][r] = a[r][r] + t * apq;
                     a[p][r] = a[r][p] = 0.0;
@@ -369,7 +357,7 @@ __global__ __launch_bounds__(64) void k_sim3_solve(const Sim3Pair* __restrict__ 
 #pragma unroll
     for (int i = 0; i < 3; i++)
 #pragma unroll
-        for (int j = 0; j < 3; j++) Mm[i][j] = (float)dot3(Pr2[i], Pr1[j][0], Pr1[j][1], Pr1[j][2]);
+        for (int j = 0; j < 3; j++) Mm[i][j] = (float)dot3(Pr2[i], Pr1[j]);
     // N (:251-265): sums and differences of floats are float arithmetic
     float n[10];
     n[0] = Mm[0][0] + Mm[1][1] + Mm[2][2];
@@ -386,8 +374,7 @@ __global__ __launch_bounds__(64) void k_sim3_solve(const Sim3Pair* __restrict__ 
     top_eigenvector4(n, q);
     // ang (:278) and the angle-axis vector (:280): a scaled convert with the
     // float scale float((2*ang)*(1/norm))
-    double nrm = (double)q[1] * (double)q[1] + (double)q[2] * (double)q[2];
-    nrm = sqrt(nrm + (double)q[3] * (double)q[3]);
+    const double nrm = norm3(q + 1);
     const double ang = atan2(nrm, (double)q[0]);
     const float av = (float)((2.0 * ang) * (1.0 / nrm));
     const float vec[3] = {q[1] * av, q[2] * av, q[3] * av};
@@ -410,7 +397,8 @@ __global__ __launch_bounds__(64) void k_sim3_solve(const Sim3Pair* __restrict__ 
             for (int k = 0; k < 9; k++) R[k] = (float)((c * ((k % 4 == 0) ? 1.0 : 0.0) + c1 * rrt[k]) + s * rcr[k]);
         }
     }
-    // P3 = mR12i*Pr2 (:288), nom = Pr1.dot(P3) (:292), den (:295-304)
+    // P3 = mR12i*Pr2 (:288), nom = Pr1.dot(P3) (:292), den (:295-304): sums
+    // of nine terms in the walk's order, so no dot3
     double nom = 0.0, den = 0.0;
 #pragma unroll
     for (int i = 0; i < 3; i++)
@@ -424,7 +412,7 @@ __global__ __launch_bounds__(64) void k_sim3_solve(const Sim3Pair* __restrict__ 
     // mt12i = O1 - ms12i*mR12i*O2 (:311): the gemm with alpha = -s and addend O1
     float t[3];
 #pragma unroll
-    for (int i = 0; i < 3; i++) t[i] = (float)(-(double)s12 * dot3(R + 3 * i, O2[0], O2[1], O2[2]) + (double)O1[i]);
+    for (int i = 0; i < 3; i++) t[i] = (float)(-(double)s12 * dot3(R + 3 * i, O2) + (double)O1[i]);
     // T12 (:316-321), T21 (:325-331)
     const float sinv = (float)(1.0 / (double)s12);
     float T12[16], T21[16], sRinv[9];
@@ -439,7 +427,7 @@ __global__ __launch_bounds__(64) void k_sim3_solve(const Sim3Pair* __restrict__ 
 #pragma unroll
     for (int i = 0; i < 3; i++) {
         T12[4 * i + 3] = t[i];
-        T21[4 * i + 3] = (float)(-dot3(sRinv + 3 * i, t[0], t[1], t[2]));
+        T21[4 * i + 3] = (float)(-dot3(sRinv + 3 * i, t));
         T12[12 + i] = T21[12 + i] = 0.f;
     }
     T12[15] = T21[15] = 1.f;
@@ -471,12 +459,13 @@ __device__ inline bool sim3_inlier(const float* c, const float* T12, const float
 {
     float X[3], u, v;
 #pragma unroll
-    for (int r = 0; r < 3; r++) X[r] = (float)(dot3(T12 + 4 * r, c[3], c[4], c[5]) + (double)T12[4 * r + 3]);
+    for (int r = 0; r < 3; r++) X[r] = affine3(T12 + 4 * r, c + 3, T12[4 * r + 3]);
     cam_to_image(cam1, X[0], X[1], X[2], contract, u, v);   // vP2im1
     const float d1x = c[6] - u, d1y = c[7] - v;
+    // dist.dot(dist) of two entries: no dot3
     const float err1 = (float)((double)d1x * (double)d1x + (double)d1y * (double)d1y);
 #pragma unroll
-    for (int r = 0; r < 3; r++) X[r] = (float)(dot3(T21 + 4 * r, c[0], c[1], c[2]) + (double)T21[4 * r + 3]);
+    for (int r = 0; r < 3; r++) X[r] = affine3(T21 + 4 * r, c, T21[4 * r + 3]);
     cam_to_image(cam2, X[0], X[1], X[2], contract, u, v);   // vP1im2
     const float d2x = u - c[8], d2y = v - c[9];
     const float err2 = (float)((double)d2x * (double)d2x + (double)d2y * (double)d2y);
