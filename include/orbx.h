@@ -65,8 +65,11 @@ extern "C" {
  *  12: the keyframe database in HBM (orbx_kfdb_create / destroy / clear /
  *      size, orbx_kfdb_add, orbx_kfdb_add_slot, orbx_kfdb_erase,
  *      orbx_kfdb_set_neighbours, orbx_kfdb_query, orbx_kfdb_score);
- *      additions only. */
-#define ORBX_ABI_VERSION 12
+ *      additions only.
+ *  13: the essential-graph optimisation of CorrectLoop (orbx_essgraph_kf,
+ *      orbx_essgraph_edge, orbx_essgraph_query, orbx_essgraph_plan,
+ *      orbx_optimize_essential_graph); additions only. */
+#define ORBX_ABI_VERSION 13
 int orbx_abi_version(void);
 
 #define ORBX_OK               0
@@ -1173,6 +1176,94 @@ int orbx_optimize_sim3_batch(orbx_ctx* ctx, int B, orbx_sim3_opt_query* qs);
  * nlevels is the extractor's (ORBX_ERR_ARG otherwise). */
 int orbx_dev_optimize_sim3(orbx_ctx* ctx, int slot1, const orbx_sim3_kf* kf1, const float* inv_sigma2_1, int n,
                            const int* slots2, const orbx_sim3_kf* kf2s, orbx_sim3_opt_query* out);
+
+/* Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:540-789), the call of
+ * LoopClosing::CorrectLoop (src/LoopClosing.cc:553) after SearchAndFuse: a
+ * 7-DoF pose graph over every keyframe of the map, then the Sim3 -> SE3
+ * recovery of every keyframe pose and the correction of every map point.
+ * g2o as the reference configures it: one VertexSim3Expmap per keyframe (the
+ * loop keyframe fixed), EdgeSim3 with information I7 and error
+ * (C * v0 * v1.inverse()).log(), no robust kernel, BaseBinaryEdge's central
+ * differences with delta 1e-9, BlockSolver_7_3 without a Schur step over a
+ * sparse Cholesky of H + lambda I, Levenberg with setUserLambdaInit(1e-16),
+ * optimize(20), at most 10 trials per iteration and ORB-SLAM's stop rule.
+ * The free vertices are ordered by id; a keyframe without an edge is not part
+ * of the system and keeps its estimate.  A failed factorisation (a pivot that
+ * is not positive and finite) rejects the trial with a zero step.
+ * The factorisation is a block Cholesky in envelope storage by block row
+ * (orbx_essgraph_plan): row r keeps the 7 x 7 blocks first[r]..r.
+ * All arithmetic is FP64 without contraction, every sum in an order fixed by
+ * the problem; two calls on the same input give the same bytes, with or
+ * without taps or timing.
+ * Arguments are checked before any device work and a refused call leaves every
+ * caller array untouched.  ORBX_ERR_ARG: a null context, query or required
+ * pointer, a negative count, n_kf < 1, an index outside its array, duplicate
+ * ids, i == j on an edge, a kind other than 0 / 1, a non-finite pose or Sim3
+ * or one with s <= 0.  ORBX_ERR_UNSUPPORTED: n_kf above ORBX_ESSGRAPH_MAX_KF
+ * or a factor above ORBX_ESSGRAPH_MAX_FACTOR_BYTES (4096 keyframes with 16
+ * edges each pass).  n_edges == 0, or no free vertex with an edge: ORBX_OK,
+ * zero iterations; the recovery and the point correction still run. */
+#define ORBX_ESSGRAPH_MAX_LM 20                 /* optimize(20) */
+#define ORBX_ESSGRAPH_MAX_KF 16384
+#define ORBX_ESSGRAPH_MAX_FACTOR_BYTES (1ll << 30)   /* n_blocks x 49 x 8 */
+typedef struct {
+    int64_t id;                 /* mnId: unique; orders the free vertices                */
+    float Tcw[12];              /* R row-major, then t                                    */
+    int32_t has_corrected;      /* CorrectedSim3.count(pKF)                               */
+    int32_t has_noncorrected;   /* NonCorrectedSim3.count(pKF)                            */
+    double corrected[8];        /* (x, y, z, w, tx, ty, tz, s), as q12 / t12d / s12d      */
+    double noncorrected[8];
+} orbx_essgraph_kf;
+typedef struct {
+    int32_t i, j;               /* vertex 0 = keyframe i, vertex 1 = keyframe j (indices) */
+    uint8_t kind;               /* 0: loop connection, the measurement vScw[j] * vScw[i]^-1;
+                                   1: normal edge, each side from noncorrected where present,
+                                   else vScw                                              */
+} orbx_essgraph_edge;
+typedef struct {
+    /* in */
+    const orbx_essgraph_kf* kfs; int n_kf;   /* the caller's vpKFs order, bad keyframes left out */
+    int loop_kf, cur_kf;                     /* indices; the loop keyframe is fixed              */
+    const orbx_essgraph_edge* edges; int n_edges;   /* g2o insertion order                      */
+    const float* pos; const int32_t* ref_kf; int n_points;   /* n x 3; the index of the keyframe
+                                                of src/Optimizer.cc:765-774, -1: skipped (isBad),
+                                                its output bytes left alone                     */
+    /* out */
+    float* Tcw_out;                          /* n_kf x 12                                        */
+    float* pos_out;                          /* n_points x 3 (may be NULL when n_points == 0)    */
+    double* est_out;                         /* optional, n_kf x 8: the optimised Sim3           */
+    int iterations, trials, not_posdef;
+    double chi2_first, chi2_last, lambda_last;
+    int n_free;                              /* vertices of the system                           */
+    long long n_blocks;                      /* 7 x 7 blocks the factorisation stores            */
+    int max_row_blocks;
+    /* optional taps (may be NULL) per edge at the first iteration */
+    double* edge_meas;                       /* x 8                                              */
+    double* edge_err;                        /* x 7                                              */
+    double* edge_J;                          /* x 98: Ji then Jj, 7 x 7 row-major, zeros for a fixed side */
+    /* optional taps per LM iteration, ORBX_ESSGRAPH_MAX_LM entries each */
+    double* it_chi2;
+    double* it_lambda;                       /* lambda after the iteration                       */
+    int32_t* it_trials;
+    double* it_est;                          /* x n_kf x 8: every estimate at the iteration's start */
+    double* it_b;                            /* x 7 n_free                                       */
+    double* it_dx;                           /* x 7 n_free: the last trial's step                */
+    double* it_Hdiag;                        /* x n_free x 28: the packed lower triangle of each
+                                                diagonal block, before lambda                   */
+} orbx_essgraph_query;
+
+int orbx_optimize_essential_graph(orbx_ctx* ctx, orbx_essgraph_query* q);   /* one upload, one read-back */
+
+/* The symbolic part of that factorisation, on the host (no device is touched):
+ * the free vertices are the keyframes other than `fixed` (an index, or -1)
+ * that have an edge, in id order; free_index[k] (n_kf) is keyframe k's place
+ * in it or -1; first[r] (n_kf entries, n_free written) is the smallest free
+ * index row r is connected to, or r; row r stores the blocks first[r]..r at
+ * row_off[r] (n_kf + 1 entries, n_free + 1 written).  Output pointers may be
+ * NULL.  ORBX_ERR_ARG as orbx_optimize_essential_graph checks ids and edges. */
+int orbx_essgraph_plan(int n_kf, const int64_t* ids, int fixed, int n_edges, const orbx_essgraph_edge* edges,
+                       int32_t* free_index, int32_t* first, int64_t* row_off, int* n_free, long long* n_blocks,
+                       int* max_row_blocks);
 
 /* PnPsolver (src/PnPsolver.cc): EPnP inside a RANSAC over the map-point
  * matches of a frame, the step of Tracking::Relocalisation

@@ -383,6 +383,123 @@ def sim3_opt_result(q, keep, taps=False):
     return r
 
 
+class EssGraphQuery(ctypes.Structure):
+    """orbx_essgraph_query (include/orbx.h)."""
+    _fields_ = [("kfs", ctypes.c_void_p), ("n_kf", ctypes.c_int), ("loop_kf", ctypes.c_int), ("cur_kf", ctypes.c_int),
+                ("edges", ctypes.c_void_p), ("n_edges", ctypes.c_int),
+                ("pos", ctypes.c_void_p), ("ref_kf", ctypes.c_void_p), ("n_points", ctypes.c_int),
+                ("Tcw_out", ctypes.c_void_p), ("pos_out", ctypes.c_void_p), ("est_out", ctypes.c_void_p),
+                ("iterations", ctypes.c_int), ("trials", ctypes.c_int), ("not_posdef", ctypes.c_int),
+                ("chi2_first", ctypes.c_double), ("chi2_last", ctypes.c_double), ("lambda_last", ctypes.c_double),
+                ("n_free", ctypes.c_int), ("n_blocks", ctypes.c_longlong), ("max_row_blocks", ctypes.c_int),
+                ("edge_meas", ctypes.c_void_p), ("edge_err", ctypes.c_void_p), ("edge_J", ctypes.c_void_p),
+                ("it_chi2", ctypes.c_void_p), ("it_lambda", ctypes.c_void_p), ("it_trials", ctypes.c_void_p),
+                ("it_est", ctypes.c_void_p), ("it_b", ctypes.c_void_p), ("it_dx", ctypes.c_void_p),
+                ("it_Hdiag", ctypes.c_void_p)]
+
+
+# orbx_essgraph_kf (192 bytes) and orbx_essgraph_edge (12 bytes)
+ESSGRAPH_KF = np.dtype([("id", "<i8"), ("Tcw", "<f4", 12), ("has_corrected", "<i4"), ("has_noncorrected", "<i4"),
+                        ("corrected", "<f8", 8), ("noncorrected", "<f8", 8)])
+ESSGRAPH_EDGE = np.dtype({"names": ["i", "j", "kind"], "formats": ["<i4", "<i4", "u1"], "offsets": [0, 4, 8],
+                          "itemsize": 12})
+assert ESSGRAPH_KF.itemsize == 192
+ESSGRAPH_MAX_LM = 20
+
+
+def essgraph_arrays(ids, Tcw, edges, corrected=None, noncorrected=None):
+    """The keyframe and edge arrays of an essential graph: ids (n), Tcw (n x 12,
+    R row-major then t, or n x 4 x 4 / n x 3 x 4), edges (m x 3: i, j, kind),
+    corrected / noncorrected: {keyframe index: Sim3 (x, y, z, w, tx, ty, tz, s)}."""
+    ids = np.asarray(ids, np.int64).reshape(-1)
+    n = len(ids)
+    T = np.asarray(Tcw, np.float32)
+    if T.ndim == 3:
+        T = np.concatenate([T[:, :3, :3].reshape(n, 9), T[:, :3, 3]], 1)
+    kfs = np.zeros(n, ESSGRAPH_KF)
+    kfs["id"], kfs["Tcw"] = ids, T.reshape(n, 12)
+    for name, table in (("corrected", corrected), ("noncorrected", noncorrected)):
+        for k, v in (table or {}).items():
+            kfs["has_" + name][k] = 1
+            kfs[name][k] = np.asarray(v, np.float64)
+    e = np.asarray(edges, np.int64).reshape(-1, 3)
+    ed = np.zeros(len(e), ESSGRAPH_EDGE)
+    ed["i"], ed["j"], ed["kind"] = e[:, 0], e[:, 1], e[:, 2]
+    return kfs, ed
+
+
+def essgraph_query(kfs, edges, loop_kf, cur_kf, pos=None, ref_kf=None, taps=False):
+    """An EssGraphQuery over numpy arrays and the arrays it points to (keep both
+    alive while the query is used): (query, keep).  kfs / edges: ESSGRAPH_KF and
+    ESSGRAPH_EDGE arrays (essgraph_arrays); pos (n x 3) / ref_kf (n): the map
+    points and the index of each one's reference keyframe (-1: skipped).  The
+    outputs start as NaN (pos_out as a copy of pos), so what a call does not
+    write is visible."""
+    keep = dict(kfs=np.ascontiguousarray(kfs, ESSGRAPH_KF), edges=np.ascontiguousarray(edges, ESSGRAPH_EDGE))
+    q = EssGraphQuery()
+    n, m = len(keep["kfs"]), len(keep["edges"])
+    q.kfs, q.n_kf, q.loop_kf, q.cur_kf = keep["kfs"].ctypes.data, n, int(loop_kf), int(cur_kf)
+    q.edges, q.n_edges = keep["edges"].ctypes.data, m
+    keep["pos"] = np.ascontiguousarray(pos if pos is not None else np.zeros((0, 3)), np.float32).reshape(-1, 3)
+    keep["ref_kf"] = np.ascontiguousarray(ref_kf if ref_kf is not None else np.zeros(0), np.int32).reshape(-1)
+    npts = len(keep["pos"])
+    q.pos, q.ref_kf, q.n_points = keep["pos"].ctypes.data, keep["ref_kf"].ctypes.data, npts
+    keep["Tcw_out"] = np.full((n, 12), np.nan, np.float32)
+    keep["pos_out"] = keep["pos"].copy()
+    keep["est_out"] = np.full((n, 8), np.nan)
+    q.Tcw_out, q.pos_out, q.est_out = keep["Tcw_out"].ctypes.data, keep["pos_out"].ctypes.data, keep["est_out"].ctypes.data
+    if taps:
+        L = ESSGRAPH_MAX_LM
+        shapes = dict(edge_meas=(m, 8), edge_err=(m, 7), edge_J=(m, 98), it_chi2=(L,), it_lambda=(L,),
+                      it_est=(L, n, 8), it_b=(L, 7 * n), it_dx=(L, 7 * n), it_Hdiag=(L, n * 28))
+        for name, shape in shapes.items():
+            keep[name] = np.full(shape, np.nan)
+            setattr(q, name, keep[name].ctypes.data)
+        keep["it_trials"] = np.zeros(L, np.int32)
+        q.it_trials = keep["it_trials"].ctypes.data
+    return q, keep
+
+
+def essgraph_result(q, keep, taps=False):
+    """The out fields (and taps) of a filled EssGraphQuery as a dict.  The
+    per-iteration taps are cut to the iterations run and to n_free."""
+    r = dict(Tcw=keep["Tcw_out"], pos=keep["pos_out"], est=keep["est_out"], iterations=q.iterations, trials=q.trials,
+             not_posdef=q.not_posdef, chi2_first=q.chi2_first, chi2_last=q.chi2_last, lambda_last=q.lambda_last,
+             n_free=q.n_free, n_blocks=q.n_blocks, max_row_blocks=q.max_row_blocks)
+    if taps:
+        it, nf, n = q.iterations, q.n_free, q.n_kf
+        for name in ("edge_meas", "edge_err", "edge_J"):
+            r[name] = keep[name]
+        for name in ("it_chi2", "it_lambda", "it_trials"):
+            r[name] = keep[name][:it]
+        r["it_est"] = keep["it_est"].reshape(-1)[:it * n * 8].reshape(it, n, 8)
+        r["it_b"] = keep["it_b"].reshape(-1)[:it * nf * 7].reshape(it, nf * 7)
+        r["it_dx"] = keep["it_dx"].reshape(-1)[:it * nf * 7].reshape(it, nf * 7)
+        r["it_Hdiag"] = keep["it_Hdiag"].reshape(-1)[:it * nf * 28].reshape(it, nf, 28)
+    return r
+
+
+def essgraph_plan(ids, fixed, edges):
+    """orbx_essgraph_plan (host only, no GPU): the envelope of the block
+    Cholesky over the free vertices in id order.  edges: an ESSGRAPH_EDGE
+    array or m x 3 integers.  A dict of free_index (n_kf), first (n_free),
+    row_off (n_free + 1), n_free, n_blocks, max_row_blocks."""
+    ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+    if not (isinstance(edges, np.ndarray) and edges.dtype == ESSGRAPH_EDGE):
+        e = np.asarray(edges, np.int64).reshape(-1, 3)
+        edges = np.zeros(len(e), ESSGRAPH_EDGE)
+        edges["i"], edges["j"], edges["kind"] = e[:, 0], e[:, 1], e[:, 2]
+    edges = np.ascontiguousarray(edges)
+    n = len(ids)
+    free_index, first, row_off = np.full(n, -1, np.int32), np.zeros(n, np.int32), np.zeros(n + 1, np.int64)
+    nf, nb, mx = ctypes.c_int(), ctypes.c_longlong(), ctypes.c_int()
+    _check(lib().orbx_essgraph_plan(n, _ptr(ids), int(fixed), len(edges), _ptr(edges), _ptr(free_index), _ptr(first),
+                                    _ptr(row_off), ctypes.byref(nf), ctypes.byref(nb), ctypes.byref(mx)),
+           "orbx_essgraph_plan")
+    return dict(free_index=free_index, first=first[:nf.value], row_off=row_off[:nf.value + 1], n_free=nf.value,
+                n_blocks=nb.value, max_row_blocks=mx.value)
+
+
 class PnpQuery(ctypes.Structure):
     """orbx_pnp_query (include/orbx.h)."""
     _fields_ = [("keys", ctypes.c_void_p), ("n", ctypes.c_int), ("pos", ctypes.c_void_p), ("valid", ctypes.c_void_p),
@@ -655,6 +772,8 @@ def _declare(L):
         "orbx_optimize_sim3": ([vp, vp], i),
         "orbx_optimize_sim3_batch": ([vp, i, vp], i),
         "orbx_dev_optimize_sim3": ([vp, i, vp, vp, i, vp, vp, vp], i),
+        "orbx_optimize_essential_graph": ([vp, vp], i),
+        "orbx_essgraph_plan": ([i, vp, i, i, vp, vp, vp, vp, vp, vp, vp], i),
         "orbx_kfdb_create": ([vp, i, i, ctypes.POINTER(vp)], i),
         "orbx_kfdb_destroy": ([vp], None),
         "orbx_kfdb_clear": ([vp, vp], i),
@@ -1317,6 +1436,15 @@ class Context:
         q, keep = sim3_opt_query(kf1, kf2, matches12, R12, t12, s12, th2=th2, taps=taps)
         _check(lib().orbx_optimize_sim3(self._h, ctypes.byref(q)), "orbx_optimize_sim3")
         return sim3_opt_result(q, keep, taps)
+
+    def optimize_essential_graph(self, kfs, edges, loop_kf, cur_kf, pos=None, ref_kf=None, taps=False):
+        """Optimizer::OptimizeEssentialGraph on the device
+        (orbx_optimize_essential_graph): arguments as essgraph_query, a dict as
+        essgraph_result (Tcw n_kf x 12, pos, est n_kf x 8, the solver's counts
+        and structure, the taps)."""
+        q, keep = essgraph_query(kfs, edges, loop_kf, cur_kf, pos=pos, ref_kf=ref_kf, taps=taps)
+        _check(lib().orbx_optimize_essential_graph(self._h, ctypes.byref(q)), "orbx_optimize_essential_graph")
+        return essgraph_result(q, keep, taps)
 
     def optimize_sim3_batch(self, queries, th2=10.0, taps=False):
         """orbx_optimize_sim3_batch over (kf1, kf2, matches12, R12, t12, s12)

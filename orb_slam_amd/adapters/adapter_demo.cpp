@@ -473,6 +473,103 @@ int main()
         const int n_pose_inliers = Optimizer::PoseOptimization(ex.context(), PF);
         int n_mp = 0;
         for (uint8_t m : PF.has_mp) n_mp += m;
+        // Optimizer::OptimizeEssentialGraph on a small loop: eight keyframes on an arc whose map grew by 3 % per
+        // keyframe (pure scale drift), the last one closing onto the first.  CorrectLoop has given the current
+        // keyframe its corrected Sim3 (the true pose at the drifted scale) and its pose the corrected SE3.  Through
+        // the adapter (which builds the edge list) and through the plain C call on the adapter's edges
+        EssentialGraph EG;
+        const int eg_n = 8;
+        double eg_scale7 = 1.0;
+        for (int k = 0; k < eg_n; k++) {
+            EssentialGraph::KeyFrame kf;
+            kf.mnId = 10 + 2 * k;
+            const double a = 0.4 * k, f = 1.0 + 0.03 * k;
+            const double R[9] = {std::cos(a), 0, std::sin(a), 0, 1, 0, -std::sin(a), 0, std::cos(a)};
+            const double c[3] = {3 * std::cos(a), 0.1 * k, 3 * std::sin(a)};
+            float Rf[9], tf[3], tdrift[3];
+            for (int i = 0; i < 3; i++) {
+                const double t = -(R[3 * i] * c[0] + R[3 * i + 1] * c[1] + R[3 * i + 2] * c[2]);
+                tf[i] = (float)t;
+                tdrift[i] = (float)(f * t);
+            }
+            for (int i = 0; i < 9; i++) Rf[i] = (float)R[i];
+            std::memcpy(kf.Tcw, Rf, sizeof(Rf));
+            std::memcpy(kf.Tcw + 9, tdrift, sizeof(tdrift));
+            if (k > 0) kf.parent = 10 + 2 * (k - 1);
+            if (k > 1) kf.covisibles = {kf.mnId - 2, kf.mnId - 4};        // the parent is skipped, k - 2 makes an edge
+            if (k + 1 < eg_n) kf.children = {kf.mnId + 2};
+            if (k == eg_n - 1) {
+                kf.hasCorrected = kf.hasNonCorrected = true;
+                kf.nonCorrected = Sim3(Rf, tdrift, 1.f);
+                kf.corrected = Sim3(Rf, tf, 1.f);
+                for (int i = 0; i < 3; i++) kf.corrected.t[i] *= f;
+                kf.corrected.s = eg_scale7 = f;
+                std::memcpy(kf.Tcw + 9, tf, sizeof(tf));
+            }
+            EG.keyframes.push_back(kf);
+        }
+        EG.loopKF = 10;
+        EG.curKF = 10 + 2 * (eg_n - 1);
+        EG.loopConnections = {{EG.curKF, {{EG.loopKF, 30}, {12, 20}, {14, 150}}}};   // the first is exempt from minFeat
+        for (int k = 0; k < 40; k++)
+            EG.points.push_back({{0.1f * k, 0.5f, 4.f + 0.05f * k}, k % 7 == 3 ? -1 : (long long)(10 + 2 * (k % eg_n))});
+        EssentialGraph EGc = EG;
+        Optimizer::OptimizeEssentialGraph(ex.context(), EG);
+        const std::vector<orbx_essgraph_edge> eg_edges = EGc.BuildEdges();
+        std::vector<orbx_essgraph_kf> eg_kfs(eg_n);
+        std::vector<float> eg_pos, eg_pos_out(3 * EGc.points.size()), eg_Tcw(12 * eg_n);
+        std::vector<int32_t> eg_ref;
+        for (int k = 0; k < eg_n; k++) {
+            const EssentialGraph::KeyFrame& kf = EGc.keyframes[k];
+            std::memset(&eg_kfs[k], 0, sizeof(eg_kfs[k]));
+            eg_kfs[k].id = (int64_t)kf.mnId;
+            std::memcpy(eg_kfs[k].Tcw, kf.Tcw, sizeof(kf.Tcw));
+            eg_kfs[k].has_corrected = kf.hasCorrected;
+            eg_kfs[k].has_noncorrected = kf.hasNonCorrected;
+            for (int i = 0; i < 8; i++) {
+                eg_kfs[k].corrected[i] = i < 4 ? kf.corrected.q[i] : i < 7 ? kf.corrected.t[i - 4] : kf.corrected.s;
+                eg_kfs[k].noncorrected[i] =
+                    i < 4 ? kf.nonCorrected.q[i] : i < 7 ? kf.nonCorrected.t[i - 4] : kf.nonCorrected.s;
+            }
+        }
+        for (const EssentialGraph::MapPoint& mp : EGc.points) {
+            eg_pos.insert(eg_pos.end(), mp.pos, mp.pos + 3);
+            eg_ref.push_back(mp.refKF < 0 ? -1 : EGc.IndexOf((unsigned long)mp.refKF));
+        }
+        eg_pos_out = eg_pos;
+        orbx_essgraph_query eq;
+        std::memset(&eq, 0, sizeof(eq));
+        eq.kfs = eg_kfs.data();
+        eq.n_kf = eg_n;
+        eq.loop_kf = 0;
+        eq.cur_kf = eg_n - 1;
+        eq.edges = eg_edges.data();
+        eq.n_edges = (int)eg_edges.size();
+        eq.pos = eg_pos.data();
+        eq.ref_kf = eg_ref.data();
+        eq.n_points = (int)eg_ref.size();
+        eq.Tcw_out = eg_Tcw.data();
+        eq.pos_out = eg_pos_out.data();
+        check(orbx_optimize_essential_graph(ex.context(), &eq), "orbx_optimize_essential_graph");
+        bool essgraph_same = eq.iterations == EG.iterations && eq.trials == EG.trials && eq.chi2_last == EG.chi2Last;
+        for (int k = 0; k < eg_n && essgraph_same; k++)
+            essgraph_same = std::memcmp(EG.keyframes[k].Tcw, &eg_Tcw[12 * k], 48) == 0;
+        for (size_t k = 0; k < EG.points.size() && essgraph_same; k++)
+            essgraph_same = std::memcmp(EG.points[k].pos, &eg_pos_out[3 * k], 12) == 0;
+        // the loop closes: the recovered camera centre of the current keyframe against the true one (where the
+        // corrected pose has it) and, for scale, the distance of the drifted centre from the true one
+        auto centre = [](const float* T, double c[3]) {   // -R^T t
+            for (int i = 0; i < 3; i++) c[i] = -((double)T[i] * T[9] + (double)T[3 + i] * T[10] + (double)T[6 + i] * T[11]);
+        };
+        double eg_c_true[3], eg_c_opt[3], essgraph_centre_err = 0, essgraph_centre_gap = 0;
+        centre(EGc.keyframes[eg_n - 1].Tcw, eg_c_true);
+        centre(EG.keyframes[eg_n - 1].Tcw, eg_c_opt);
+        for (int i = 0; i < 3; i++) {
+            essgraph_centre_err += (eg_c_opt[i] - eg_c_true[i]) * (eg_c_opt[i] - eg_c_true[i]);
+            essgraph_centre_gap += (eg_scale7 - 1) * eg_c_true[i] * (eg_scale7 - 1) * eg_c_true[i];
+        }
+        essgraph_centre_err = std::sqrt(essgraph_centre_err);
+        essgraph_centre_gap = std::sqrt(essgraph_centre_gap);
         std::printf("{\"n1\": %zu, \"n2\": %zu, \"levels\": %d, \"scale\": %.3f, \"init_matches\": %d, "
                     "\"bf_matches\": %d, \"ba_iterations\": [%d, %d], \"ba_chi2\": [%.6g, %.6g], "
                     "\"pose_inliers\": %d, \"pose_edges\": %d, \"pose_tx\": %.6g, \"init_same\": %d, "
@@ -492,6 +589,11 @@ int main()
         std::printf("\"sim3opt_same\": %d, \"sim3opt_n_in\": %d, \"sim3opt_n_corr\": %d, \"sim3opt_n_bad\": %d, "
                     "\"sim3opt_scale\": %.9f, ",
                     sim3opt_same ? 1 : 0, opt_n_in, oq.n_corr, oq.n_bad, gS12.s);
+        std::printf("\"essgraph_same\": %d, \"essgraph_edges\": %d, \"essgraph_iterations\": %d, "
+                    "\"essgraph_chi2\": [%.6g, %.6g], \"essgraph_centre_err\": %.4g, \"essgraph_centre_gap\": %.4g, "
+                    "\"essgraph_scale\": [%.6f, %.6f], ",
+                    essgraph_same ? 1 : 0, (int)eg_edges.size(), EG.iterations, EG.chi2First, EG.chi2Last,
+                    essgraph_centre_err, essgraph_centre_gap, EG.optimised[eg_n - 1].s, eg_scale7);
         std::printf("\"pnp_same\": %d, \"pnp_n\": %d, \"pnp_found\": %d, \"pnp_refined\": %d, \"pnp_inliers\": %d, "
                     "\"pnp_iterations\": %d, \"pnp_calls\": %d, \"pnp_pose_error\": %.3g, \"pnp_max_its\": %d, "
                     "\"pnp_find_found\": %d, \"pnp_find_iterations\": %d, \"pnp_find_max_its\": %d, "

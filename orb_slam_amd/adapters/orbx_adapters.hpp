@@ -6,7 +6,8 @@
 //
 //   ORB_SLAM_AMD::ORBextractor   <- ORB_SLAM::ORBextractor   include/ORBextractor.h:32-77
 //   ORB_SLAM_AMD::ORBmatcher     <- ORB_SLAM::ORBmatcher     include/ORBmatcher.h:37-107
-//   ORB_SLAM_AMD::Optimizer      <- ORB_SLAM::Optimizer::LocalBundleAdjustment, PoseOptimization, OptimizeSim3
+//   ORB_SLAM_AMD::Optimizer      <- ORB_SLAM::Optimizer::LocalBundleAdjustment, PoseOptimization, OptimizeSim3,
+//                                   OptimizeEssentialGraph
 //                                                           include/Optimizer.h:42
 //   ORB_SLAM_AMD::Initializer    <- ORB_SLAM::Initializer    include/Initializer.h:33-96
 //                                   (FindHomography + FindFundamental)
@@ -25,6 +26,7 @@
 #include <cmath>
 #include <cstring>
 #include <memory>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -358,6 +360,7 @@ struct PoseFrame {
 
 struct Sim3KeyFrame;   // below, with Sim3Solver
 struct Sim3;
+struct EssentialGraph;   // below, after Sim3
 
 class Optimizer {
 public:
@@ -365,6 +368,12 @@ public:
     // (src/Optimizer.cc:791-987); defined below Sim3.
     static int OptimizeSim3(orbx_ctx* ctx, const Sim3KeyFrame& kf1, const Sim3KeyFrame& kf2, std::vector<int>& vMatches1,
                             Sim3& S12, float th2);
+
+    // void OptimizeEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, g2o::Sim3& Scurw,
+    //                             KeyFrameAndPose& NonCorrectedSim3, KeyFrameAndPose& CorrectedSim3,
+    //                             map<KeyFrame*, set<KeyFrame*>>& LoopConnections)
+    // (src/Optimizer.cc:540-789); defined below EssentialGraph.
+    static void OptimizeEssentialGraph(orbx_ctx* ctx, EssentialGraph& G);
 
     // Returns nInitialCorrespondences - nBad, updates F.Tcw and F.outlier.
     static int PoseOptimization(orbx_ctx* ctx, PoseFrame& F)
@@ -905,6 +914,159 @@ inline int Optimizer::OptimizeSim3(orbx_ctx* ctx, const Sim3KeyFrame& kf1, const
         S12.from_float = false;
     }
     return q.n_in;
+}
+
+// ---------------------------------------------------------------------------
+// Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:540-789), the call of
+// LoopClosing::CorrectLoop after SearchAndFuse.  EssentialGraph holds what
+// the reference reads from the map, as plain arrays; BuildEdges() is the edge
+// list by the rules of :604-729, free of the device.  The reference iterates
+// LoopConnections (a std::map keyed by KeyFrame*) and its std::set<KeyFrame*>
+// values in pointer order, which no caller can reproduce; this iterates both
+// in the caller's order, so the edges' insertion order -- and with it the last
+// bits of the sums -- is the caller's.
+// ---------------------------------------------------------------------------
+struct EssentialGraph {
+    struct KeyFrame {
+        unsigned long mnId = 0;
+        float Tcw[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};   // GetRotation() row-major, GetTranslation(); out: SetPose
+        long long parent = -1;                  // GetParent()->mnId, -1: none
+        std::vector<unsigned long> loopEdges;   // GetLoopEdges()
+        std::vector<unsigned long> covisibles;  // GetCovisiblesByWeight(100), in its order (bad keyframes are skipped)
+        std::vector<unsigned long> children;    // mspChildrens (hasChild)
+        bool hasCorrected = false, hasNonCorrected = false;   // CorrectedSim3.count / NonCorrectedSim3.count
+        Sim3 corrected, nonCorrected;
+    };
+    struct Connection {
+        unsigned long id;   // the connected keyframe
+        int weight;         // pKF->GetWeight(it)
+    };
+    struct LoopConnection {
+        unsigned long id;   // the key of LoopConnections
+        std::vector<Connection> to;
+    };
+    struct MapPoint {
+        float pos[3];       // GetWorldPos(); out: SetWorldPos
+        long long refKF;    // mnCorrectedReference where mnCorrectedByKF == pCurKF->mnId, else the reference
+                            // keyframe's mnId (:765-774); -1: isBad(), left alone
+    };
+    std::vector<KeyFrame> keyframes;   // pMap->GetAllKeyFrames() without the bad ones
+    unsigned long loopKF = 0, curKF = 0;
+    std::vector<LoopConnection> loopConnections;
+    std::vector<MapPoint> points;
+    // out
+    std::vector<Sim3> optimised;       // per keyframe: the vertex's estimate
+    int iterations = 0, trials = 0, notPosDef = 0;
+    double chi2First = 0, chi2Last = 0;
+
+    // index of a keyframe id, -1 when the map holds no such (good) keyframe
+    int IndexOf(unsigned long id) const
+    {
+        for (size_t k = 0; k < keyframes.size(); k++)
+            if (keyframes[k].mnId == id) return (int)k;
+        return -1;
+    }
+
+    // The edges in g2o's insertion order (:604-729).  Throws for a parent, a loop edge or a loop connection that
+    // names a keyframe the map does not hold (the reference would dereference a null vertex).
+    std::vector<orbx_essgraph_edge> BuildEdges() const
+    {
+        const int minFeat = 100;
+        std::vector<orbx_essgraph_edge> edges;
+        std::set<std::pair<unsigned long, unsigned long>> sInsertedEdges;
+        auto need = [&](unsigned long id) {
+            const int k = IndexOf(id);
+            if (k < 0) throw orbx_error(ORBX_ERR_ARG, "EssentialGraph::BuildEdges");
+            return k;
+        };
+        auto has = [](const std::vector<unsigned long>& v, unsigned long id) {
+            return std::find(v.begin(), v.end(), id) != v.end();
+        };
+        // SET LOOP EDGES (:609-637)
+        for (const LoopConnection& lc : loopConnections) {
+            const int i = need(lc.id);
+            for (const Connection& c : lc.to) {
+                if ((lc.id != curKF || c.id != loopKF) && c.weight < minFeat) continue;
+                edges.push_back({i, need(c.id), 0});
+                sInsertedEdges.insert({std::min(lc.id, c.id), std::max(lc.id, c.id)});
+            }
+        }
+        // SET NORMAL EDGES (:640-729)
+        for (size_t k = 0; k < keyframes.size(); k++) {
+            const KeyFrame& kf = keyframes[k];
+            if (kf.parent >= 0) edges.push_back({(int)k, need((unsigned long)kf.parent), 1});   // the spanning tree
+            for (unsigned long l : kf.loopEdges)
+                if (l < kf.mnId) edges.push_back({(int)k, need(l), 1});
+            for (unsigned long n : kf.covisibles) {
+                if ((kf.parent >= 0 && n == (unsigned long)kf.parent) || has(kf.children, n) || has(kf.loopEdges, n)) continue;
+                const int j = IndexOf(n);
+                if (j < 0 || !(n < kf.mnId)) continue;   // isBad(), or the other end adds it
+                if (sInsertedEdges.count({std::min(kf.mnId, n), std::max(kf.mnId, n)})) continue;
+                edges.push_back({(int)k, j, 1});
+            }
+        }
+        return edges;
+    }
+};
+
+// Runs the optimisation, then writes the keyframe poses (SetPose) and the map points (SetWorldPos) back into G.
+inline void Optimizer::OptimizeEssentialGraph(orbx_ctx* ctx, EssentialGraph& G)
+{
+    const std::vector<orbx_essgraph_edge> edges = G.BuildEdges();
+    const int n = (int)G.keyframes.size(), np = (int)G.points.size();
+    std::vector<orbx_essgraph_kf> kfs(n);
+    auto put = [](const Sim3& S, double* o) {
+        for (int i = 0; i < 4; i++) o[i] = S.q[i];
+        for (int i = 0; i < 3; i++) o[4 + i] = S.t[i];
+        o[7] = S.s;
+    };
+    for (int k = 0; k < n; k++) {
+        const EssentialGraph::KeyFrame& kf = G.keyframes[k];
+        std::memset(&kfs[k], 0, sizeof(kfs[k]));
+        kfs[k].id = (int64_t)kf.mnId;
+        std::memcpy(kfs[k].Tcw, kf.Tcw, sizeof(kf.Tcw));
+        kfs[k].has_corrected = kf.hasCorrected;
+        kfs[k].has_noncorrected = kf.hasNonCorrected;
+        if (kf.hasCorrected) put(kf.corrected, kfs[k].corrected);
+        if (kf.hasNonCorrected) put(kf.nonCorrected, kfs[k].noncorrected);
+    }
+    std::vector<float> pos(3 * (size_t)np), pos_out(3 * (size_t)np), Tcw(12 * (size_t)n);
+    std::vector<int32_t> ref(np);
+    std::vector<double> est(8 * (size_t)n);
+    for (int k = 0; k < np; k++) {
+        std::memcpy(&pos[3 * (size_t)k], G.points[k].pos, 12);
+        ref[k] = G.points[k].refKF < 0 ? -1 : G.IndexOf((unsigned long)G.points[k].refKF);
+        if (G.points[k].refKF >= 0 && ref[k] < 0) throw orbx_error(ORBX_ERR_ARG, "Optimizer::OptimizeEssentialGraph");
+    }
+    orbx_essgraph_query q;
+    std::memset(&q, 0, sizeof(q));
+    q.kfs = kfs.data();
+    q.n_kf = n;
+    q.loop_kf = G.IndexOf(G.loopKF);
+    q.cur_kf = G.IndexOf(G.curKF);
+    q.edges = edges.data();
+    q.n_edges = (int)edges.size();
+    q.pos = pos.data();
+    q.ref_kf = ref.data();
+    q.n_points = np;
+    q.Tcw_out = Tcw.data();
+    q.pos_out = pos_out.data();
+    q.est_out = est.data();
+    check(orbx_optimize_essential_graph(ctx, &q), "Optimizer::OptimizeEssentialGraph");
+    G.optimised.assign(n, Sim3());
+    for (int k = 0; k < n; k++) {
+        std::memcpy(G.keyframes[k].Tcw, &Tcw[12 * (size_t)k], 48);
+        for (int i = 0; i < 4; i++) G.optimised[k].q[i] = est[8 * (size_t)k + i];
+        for (int i = 0; i < 3; i++) G.optimised[k].t[i] = est[8 * (size_t)k + 4 + i];
+        G.optimised[k].s = est[8 * (size_t)k + 7];
+    }
+    for (int k = 0; k < np; k++)
+        if (ref[k] >= 0) std::memcpy(G.points[k].pos, &pos_out[3 * (size_t)k], 12);
+    G.iterations = q.iterations;
+    G.trials = q.trials;
+    G.notPosDef = q.not_posdef;
+    G.chi2First = q.chi2_first;
+    G.chi2Last = q.chi2_last;
 }
 
 // ---------------------------------------------------------------------------

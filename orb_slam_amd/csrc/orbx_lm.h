@@ -1,5 +1,5 @@
 // The g2o pieces the FP64 optimisers share (orbx_pose.hip, orbx_sim3opt.hip,
-// orbx_lba.hip): the Huber kernel, Eigen's pivoted LDLT behind
+// orbx_lba.hip, orbx_essgraph.hip): the Huber kernel, Eigen's pivoted LDLT behind
 // LinearSolverDense, and OptimizationAlgorithmLevenberg's control with
 // ORB-SLAM's stop rule.  Every kernel has to follow the oracle's trajectory
 // bit for bit, so this is the one text of each expression: operand order,
@@ -158,6 +158,15 @@ constexpr int kLmMaxTrials = 10;   // _maxTrialsAfterFailure
 ORBX_LM_FN void lm_init(LmState& s, double max_diag)
 {
     s.lambda = 1e-5 * max_diag;   // _tau
+    s.ni = 2;
+    s.nBad = 0;
+}
+
+// computeLambdaInit with setUserLambdaInit(lambda) (levenberg.cpp:166-169): the
+// caller's value instead of _tau times the largest diagonal entry.
+ORBX_LM_FN void lm_init_user(LmState& s, double lambda)
+{
+    s.lambda = lambda;
     s.ni = 2;
     s.nBad = 0;
 }

@@ -52,6 +52,7 @@
 #include "orbx_lm.h"
 #include "orbx_match_common.h"
 #include "orbx_se3.h"
+#include "orbx_sim3_dev.h"
 #include "orbx_stage.h"
 
 namespace orbx {
@@ -61,9 +62,6 @@ constexpr int kSoTrials = ORBX_SIM3_OPT_MAX_TRIALS;
 constexpr int kSoWide = 4;          // wavefronts of a lone call's workgroup
 constexpr int kSoTerms = 36;        // per edge: chi2, 28 of H, 7 of b
 constexpr int kSoStride = 73;       // doubles per LDS row (72 terms + 1: odd, so rows spread over the banks)
-constexpr double kSoDelta = 1e-9;   // base_binary_edge.hpp:133
-constexpr double kSoExpP = 0x1.000000044b830p+0;   // exp(+1e-9), correctly rounded
-constexpr double kSoExpM = 0x1.fffffff768fa1p-1;   // exp(-1e-9)
 static_assert(64 * kSoWide * kSoStride * sizeof(double) <= 150 * 1024, "the term rows of a lone call fit gfx950's LDS");
 
 // One candidate: device pointers to its inputs.
@@ -119,97 +117,6 @@ inline Sim3OptLayout sim3opt_layout(int cap, bool taps)
     L.stride = o.end;
     L.cap = cap;
     return L;
-}
-
-// g2o::Sim3 as (x, y, z, w, tx, ty, tz, s).
-// Sim3(const Vector7d& update) (sim3.h:70-142); es = exp(update[6]).
-__device__ inline void sim3_exp(const double u[7], double es, double out[8])
-{
-    const double om[3] = {u[0], u[1], u[2]}, up[3] = {u[3], u[4], u[5]};
-    const double sigma = u[6];
-    const double theta = sqrt(om[0] * om[0] + om[1] * om[1] + om[2] * om[2]);
-    const double O[9] = {0, -om[2], om[1], om[2], 0, -om[0], -om[1], om[0], 0};
-    double O2[9], R[9], W[9];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) O2[i * 3 + j] = O[i * 3] * O[j] + O[i * 3 + 1] * O[3 + j] + O[i * 3 + 2] * O[6 + j];
-    const double s = es;
-    const double eps = 0.00001;
-    double A, B, C;
-    bool rodrigues;
-    if (fabs(sigma) < eps) {
-        C = 1;
-        if (theta < eps) {
-            A = 1. / 2.;
-            B = 1. / 6.;
-            rodrigues = false;
-        } else {
-            const double theta2 = theta * theta;
-            A = (1 - cos(theta)) / (theta2);
-            B = (theta - sin(theta)) / (theta2 * theta);
-            rodrigues = true;
-        }
-    } else {
-        C = (s - 1) / sigma;
-        if (theta < eps) {
-            const double sigma2 = sigma * sigma;
-            A = ((sigma - 1) * s + 1) / sigma2;
-            B = ((0.5 * sigma2 - sigma + 1) * s) / (sigma2 * sigma);
-            rodrigues = false;
-        } else {
-            const double a = s * sin(theta);
-            const double b = s * cos(theta);
-            const double theta2 = theta * theta;
-            const double sigma2 = sigma * sigma;
-            const double c = theta2 + sigma2;
-            A = (a * sigma + (1 - b) * theta) / (theta * c);
-            B = (C - ((b - 1) * sigma + a * theta) / (c)) * 1. / (theta2);
-            rodrigues = true;
-        }
-    }
-    if (rodrigues) {
-        const double ra = sin(theta) / theta, rb = (1 - cos(theta)) / (theta * theta);
-#pragma unroll
-        for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0 ? 1.0 : 0.0) + ra * O[i] + rb * O2[i];
-    } else {
-#pragma unroll
-        for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0 ? 1.0 : 0.0) + O[i] + O2[i];
-    }
-    const Q q = qfrom(R);
-#pragma unroll
-    for (int i = 0; i < 9; i++) W[i] = A * O[i] + B * O2[i] + C * (i % 4 == 0 ? 1.0 : 0.0);
-    out[0] = q.x; out[1] = q.y; out[2] = q.z; out[3] = q.w;
-#pragma unroll
-    for (int i = 0; i < 3; i++) out[4 + i] = W[i * 3] * up[0] + W[i * 3 + 1] * up[1] + W[i * 3 + 2] * up[2];
-    out[7] = s;
-}
-
-// Sim3::operator* (sim3.h:266-272): the quaternion is never renormalised
-__device__ inline void sim3_mul(const double a[8], const double b[8], double o[8])
-{
-    const Q qa{a[0], a[1], a[2], a[3]};
-    const Q r = qmul(qa, Q{b[0], b[1], b[2], b[3]});
-    const double bt[3] = {b[4], b[5], b[6]};
-    double rt[3];
-    qrot(qa, bt, rt);
-    o[0] = r.x; o[1] = r.y; o[2] = r.z; o[3] = r.w;
-#pragma unroll
-    for (int i = 0; i < 3; i++) o[4 + i] = a[7] * rt[i] + a[4 + i];
-    o[7] = a[7] * b[7];
-}
-
-// Sim3::inverse (sim3.h:233-236)
-__device__ inline void sim3_inverse(const double a[8], double o[8])
-{
-    const Q rc{-a[0], -a[1], -a[2], a[3]};
-    const double f = -1. / a[7];
-    const double st[3] = {f * a[4], f * a[5], f * a[6]};
-    double rt[3];
-    qrot(rc, st, rt);
-    o[0] = rc.x; o[1] = rc.y; o[2] = rc.z; o[3] = rc.w;
-    o[4] = rt[0]; o[5] = rt[1]; o[6] = rt[2];
-    o[7] = 1. / a[7];
 }
 
 // obs - cam_map(project(S.map(X))) (types_seven_dof_expmap.h:138-167)
