@@ -440,8 +440,9 @@ def essgraph_query(kfs, edges, loop_kf, cur_kf, pos=None, ref_kf=None, taps=Fals
     n, m = len(keep["kfs"]), len(keep["edges"])
     q.kfs, q.n_kf, q.loop_kf, q.cur_kf = keep["kfs"].ctypes.data, n, int(loop_kf), int(cur_kf)
     q.edges, q.n_edges = keep["edges"].ctypes.data, m
-    keep["pos"] = np.ascontiguousarray(pos if pos is not None else np.zeros((0, 3)), np.float32).reshape(-1, 3)
-    keep["ref_kf"] = np.ascontiguousarray(ref_kf if ref_kf is not None else np.zeros(0), np.int32).reshape(-1)
+    # copies: `keep` owns what the query points to, so writing into it never reaches the caller's arrays
+    keep["pos"] = np.array(pos if pos is not None else np.zeros((0, 3)), np.float32, order="C").reshape(-1, 3)
+    keep["ref_kf"] = np.array(ref_kf if ref_kf is not None else np.zeros(0), np.int32, order="C").reshape(-1)
     npts = len(keep["pos"])
     q.pos, q.ref_kf, q.n_points = keep["pos"].ctypes.data, keep["ref_kf"].ctypes.data, npts
     keep["Tcw_out"] = np.full((n, 12), np.nan, np.float32)
