@@ -68,8 +68,13 @@ extern "C" {
  *      additions only.
  *  13: the essential-graph optimisation of CorrectLoop (orbx_essgraph_kf,
  *      orbx_essgraph_edge, orbx_essgraph_query, orbx_essgraph_plan,
- *      orbx_optimize_essential_graph); additions only. */
-#define ORBX_ABI_VERSION 13
+ *      orbx_optimize_essential_graph); additions only.
+ *  14: the covisibility graph in HBM (orbx_covis_create / destroy / clear /
+ *      size, orbx_covis_add_keyframe, orbx_covis_set_matches,
+ *      orbx_covis_erase_points, orbx_covis_erase_keyframe,
+ *      orbx_covis_update_connections, orbx_covis_connections,
+ *      orbx_covis_update_reference); additions only. */
+#define ORBX_ABI_VERSION 14
 int orbx_abi_version(void);
 
 #define ORBX_OK               0
@@ -585,7 +590,9 @@ int orbx_search_local_map(orbx_ctx* ctx, orbx_local_map_query* q);
  * searches; a caller passes the one it holds (the previous frame's), which
  * is the reference's whenever those keyframes are unchanged, or runs the two
  * halves with the host-array calls (orbx_search_by_projection_motion,
- * orbx_pose_optimization, orbx_search_local_map).  The camera centre for the frustum
+ * orbx_pose_optimization, orbx_search_local_map) around
+ * orbx_covis_update_reference, which rebuilds the local map on the device
+ * (its lists are not yet read by this call in HBM).  The camera centre for the frustum
  * test is Frame::UpdatePoseMatrices' mOw = -Rcw^T tcw evaluated in float
  * left to right (the adapter's host glue does the same).  The undistorted
  * keypoints of the slot are its extracted keypoints (k1 = 0) or those
@@ -1473,6 +1480,133 @@ int orbx_kfdb_query(orbx_ctx* ctx, orbx_kfdb* db, orbx_kfdb_query_args* q);
  * ORBX_ERR_ARG: an id that is not a member. */
 int orbx_kfdb_score(orbx_ctx* ctx, orbx_kfdb* db, int slot, int n_words, const uint32_t* words, const double* values,
                     int n, const int32_t* ids, float* scores);
+
+/* The covisibility graph in HBM: the keyframe -> map-point table
+ * (KeyFrame::mvpMapPoints of every keyframe) and the connection weights
+ * (mConnectedKeyFrameWeights), with KeyFrame::UpdateConnections
+ * (src/KeyFrame.cc:332-421), the covisibility reads (:162-211) and
+ * Tracking::UpdateReferenceKeyFrames + UpdateReferencePoints
+ * (src/Tracking.cc:764-865) on top of them.  Integer work throughout: every
+ * list comes back as the reference builds it, entry for entry.
+ *
+ * Ids.  Keyframes are named by mnId in [0, kf_capacity), kf_capacity <=
+ * ORBX_COVIS_MAX_KEYFRAMES; map points by mnId in [0, mp_capacity),
+ * mp_capacity <= ORBX_COVIS_MAX_POINTS; a row holds at most max_keypoints <=
+ * ORBX_COVIS_MAX_KEYPOINTS entries.  Above a limit orbx_covis_create returns
+ * ORBX_ERR_UNSUPPORTED.  An id is never reused: adding a keyframe id that was
+ * erased is ORBX_ERR_ARG (until orbx_covis_clear).
+ *
+ * Order keys.  The reference iterates std::map<KeyFrame*, ...> and sorts
+ * pair<int, KeyFrame*>, so pointer values decide the order of its lists.
+ * Every keyframe is added with a 64-bit key that stands for that value (the
+ * adapter passes (uint64_t)(uintptr_t)pKF), distinct among all keyframes ever
+ * added.
+ *
+ * Observations.  The observation set of point p is, by definition, the
+ * members whose row holds p.  That equals MapPoint::mObservations wherever
+ * KeyFrame::AddMapPoint / MapPoint::AddObservation and EraseMapPointMatch /
+ * EraseObservation have been applied in pairs, which is the case at every
+ * call site of the three operations.  A keyframe is therefore added where
+ * LocalMapping::ProcessNewKeyFrame has added its observations
+ * (src/LocalMapping.cc:130-160), not where Tracking constructs it.  A point
+ * stands at most once in a row (mObservations holds one index per keyframe).
+ * MapPoint::EraseObservation turns a point bad when two observations or
+ * fewer remain; that is a SetBadFlag, mirrored with orbx_covis_erase_points.
+ *
+ * Erased points (MapPoint::isBad()).  An erased id in an input row or in a
+ * frame is no error: it is skipped as the reference skips a bad point.
+ *
+ * Connection state of member i: the weights W[i][j] > 0, a flag filtered_i and
+ * a threshold th_i.  The ordered list (mvpOrderedConnectedKeyFrames /
+ * mvOrderedWeights) is a function of these: the entries of row i when not
+ * filtered; when filtered those with weight >= th_i, or, if none passes, the
+ * single entry of largest weight (the smallest key among equals); sorted
+ * descending by (weight, key): among equal weights the larger key first.
+ *
+ * Every edit is applied to a host shadow (where it is checked) and mirrored
+ * to HBM on the context's stream.  An object belongs to the device of the
+ * context it was created with; one thread at a time. */
+#define ORBX_COVIS_MAX_KEYFRAMES 8192
+#define ORBX_COVIS_MAX_KEYPOINTS 65535
+#define ORBX_COVIS_MAX_POINTS    (1 << 27)
+#define ORBX_COVIS_ORDERED 0
+#define ORBX_COVIS_ALL     1
+typedef struct orbx_covis orbx_covis;
+int orbx_covis_create(orbx_ctx* ctx, int kf_capacity, int mp_capacity, int max_keypoints, orbx_covis** out);
+void orbx_covis_destroy(orbx_covis* m);
+/* No keyframes, no erased points, every id and key free again. */
+int orbx_covis_clear(orbx_ctx* ctx, orbx_covis* m);
+int orbx_covis_size(const orbx_covis* m);   /* member keyframes; ORBX_ERR_ARG for NULL */
+/* A keyframe with its row mvpMapPoints: n <= max_keypoints entries, a point id
+ * or -1 each.  ORBX_ERR_ARG: id out of range, in use or erased; a key used
+ * before; n or an entry out of range; a point twice in the row. */
+int orbx_covis_add_keyframe(orbx_ctx* ctx, orbx_covis* m, int id, uint64_t key, int n, const int32_t* mp);
+/* Scattered writes to member id's row, in order: row[idx[k]] = mp[k]; -1 is
+ * EraseMapPointMatch, a point id AddMapPoint / ReplaceMapPointMatch.  All or
+ * none: ORBX_ERR_ARG (and no change) for an index outside the row, a point out
+ * of range or a point that would stand twice in the row. */
+int orbx_covis_set_matches(orbx_ctx* ctx, orbx_covis* m, int id, int n_edits, const int32_t* idx, const int32_t* mp);
+/* MapPoint::SetBadFlag, and Replace's old point: marks the points erased and
+ * clears them from every row.  ORBX_ERR_ARG: an id out of range. */
+int orbx_covis_erase_points(orbx_ctx* ctx, orbx_covis* m, int n, const int32_t* ids);
+/* The connection part of KeyFrame::SetBadFlag (src/KeyFrame.cc:510-521): for
+ * every j in row id of W, an existing W[j][id] is erased and filtered_j
+ * cleared (EraseConnection -> UpdateBestCovisibles); then row id of W and the
+ * keyframe's table row go.  A W[j][id] without a W[id][j] stays, as the
+ * reference's dangling KeyFrame* does; the reads report it as it stands.  The
+ * spanning tree stays with the caller, which reads what it needs through
+ * orbx_covis_connections before this call.  ORBX_ERR_ARG: not a member. */
+int orbx_covis_erase_keyframe(orbx_ctx* ctx, orbx_covis* m, int id);
+/* KeyFrame::UpdateConnections for members ids[0, n), in that order, with the
+ * reference's threshold th (15).  For i = ids[k]: counter[j] = the entries of
+ * row i that are not -1, not erased and in row j (j != i a member).  All zero:
+ * nothing changes, updated[k] = 0, front[k] = -1.  Otherwise row i of W
+ * becomes the non-zero counts (those below th included), filtered_i = 1, th_i
+ * = th; AddConnection(j <- i) runs for every j with counter[j] >= th, or for
+ * the single fallback keyframe: an unchanged W[j][i] leaves j as it is, a
+ * changed or new one is written and clears filtered_j.  updated[k] = 1 and
+ * front[k] = the head of i's ordered list (mpParent under mbFirstConnection).
+ * updated / front hold n entries.  ORBX_ERR_ARG: an id that is not a member,
+ * th < 1. */
+int orbx_covis_update_connections(orbx_ctx* ctx, orbx_covis* m, int n, const int32_t* ids, int th, int32_t* updated,
+                                  int32_t* front);
+/* which = ORBX_COVIS_ORDERED: the ordered list of member id and its weights
+ * (GetVectorCovisibleKeyFrames; its first N entries are
+ * GetBestCovisibilityKeyFrames(N)); ORBX_COVIS_ALL: every entry of row id in
+ * ascending key order (GetConnectedKeyFrames with GetWeight).  Entries that
+ * name an erased keyframe are reported (the reference's callers test
+ * isBad()).  *n = the list's length; ORBX_ERR_CAPACITY when it exceeds cap
+ * (cap entries are written then). */
+int orbx_covis_connections(orbx_ctx* ctx, orbx_covis* m, int id, int which, int32_t* kfs, int32_t* weights, int cap,
+                           int* n);
+
+typedef struct {
+    /* in */
+    int n; const int32_t* frame_mp;       /* mCurrentFrame.mvpMapPoints: ids or -1, n <= max_keypoints;
+                                             a point may stand twice and then votes twice           */
+    /* out */
+    uint8_t* frame_erased;                /* [n] 1 where the point is erased: the caller NULLs it
+                                             (src/Tracking.cc:805-808); NULL: not wanted            */
+    int32_t* local_kf; int kf_cap;        /* mvpLocalKeyFrames                                      */
+    int n_local_kf;                       /* its size                                               */
+    int n_voters;                         /* its size before the neighbour pass                     */
+    int ref_kf;                           /* mpReferenceKF (pKFmax), or -1                          */
+    int32_t* local_mp; int mp_cap;        /* mvpLocalMapPoints                                      */
+    int n_local_mp;                       /* its size                                               */
+} orbx_covis_reference_args;
+/* Tracking::UpdateReferenceKeyFrames + UpdateReferencePoints for one frame.
+ * Votes: every frame entry that is a point and not erased votes for the
+ * members whose row holds it.  The voters in ascending key order open
+ * local_kf; ref_kf is the first strict maximum in that order.  The neighbour
+ * pass visits the voters in that order, stops before a voter once the list
+ * holds more than 80 keyframes, and appends the first of the voter's best 10
+ * (erased keyframes take places among the 10) that is a member and not yet
+ * listed.  local_mp: the rows of the local keyframes in list and index
+ * order, every point that is not erased once, at its first place.  Both lists
+ * also stay in buffers of the object in HBM.  ORBX_ERR_ARG: n or an entry out
+ * of range, cap < 0; ORBX_ERR_CAPACITY with the three counts set when a list
+ * exceeds its capacity (the capacity's worth of entries is written). */
+int orbx_covis_update_reference(orbx_ctx* ctx, orbx_covis* m, orbx_covis_reference_args* q);
 
 /* ------------------------------------------------------------------------ */
 /* C. Local bundle adjustment                                                */

@@ -785,6 +785,17 @@ def _declare(L):
         "orbx_kfdb_set_neighbours": ([vp, vp, i, vp, vp], i),
         "orbx_kfdb_query": ([vp, vp, vp], i),
         "orbx_kfdb_score": ([vp, vp, i, i, vp, vp, i, vp, vp], i),
+        "orbx_covis_create": ([vp, i, i, i, ctypes.POINTER(vp)], i),
+        "orbx_covis_destroy": ([vp], None),
+        "orbx_covis_clear": ([vp, vp], i),
+        "orbx_covis_size": ([vp], i),
+        "orbx_covis_add_keyframe": ([vp, vp, i, ctypes.c_uint64, i, vp], i),
+        "orbx_covis_set_matches": ([vp, vp, i, i, vp, vp], i),
+        "orbx_covis_erase_points": ([vp, vp, i, vp], i),
+        "orbx_covis_erase_keyframe": ([vp, vp, i], i),
+        "orbx_covis_update_connections": ([vp, vp, i, vp, i, vp, vp], i),
+        "orbx_covis_connections": ([vp, vp, i, i, vp, vp, i, ctypes.POINTER(i)], i),
+        "orbx_covis_update_reference": ([vp, vp, vp], i),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(L, name)
@@ -1680,6 +1691,122 @@ class KeyFrameDatabase:
         (GetConnectedKeyFrames)."""
         c, i = self._detect(KFDB_LOOP, query, min_score, ref, exclude, taps, cap)
         return (c, i) if (taps or info) else c
+
+
+class CovisReference(ctypes.Structure):
+    """orbx_covis_reference_args (include/orbx.h)."""
+    _fields_ = [("n", ctypes.c_int), ("frame_mp", ctypes.c_void_p), ("frame_erased", ctypes.c_void_p),
+                ("local_kf", ctypes.c_void_p), ("kf_cap", ctypes.c_int), ("n_local_kf", ctypes.c_int),
+                ("n_voters", ctypes.c_int), ("ref_kf", ctypes.c_int), ("local_mp", ctypes.c_void_p),
+                ("mp_cap", ctypes.c_int), ("n_local_mp", ctypes.c_int)]
+
+
+COVIS_ORDERED, COVIS_ALL = 0, 1
+COVIS_MAX_KEYFRAMES, COVIS_MAX_KEYPOINTS, COVIS_MAX_POINTS = 8192, 65535, 1 << 27
+
+
+class CovisibilityMap:
+    """The covisibility graph in HBM (orbx_covis_*): the keyframes' map-point
+    rows and the connection weights, KeyFrame::UpdateConnections, the
+    covisibility reads and Tracking::UpdateReference.  Keyframes and points
+    are named by mnId; every keyframe carries a 64-bit order key that stands
+    for its KeyFrame* value."""
+
+    def __init__(self, ctx, kf_capacity, mp_capacity, max_keypoints):
+        self._ctx = ctx
+        self.kf_capacity, self.mp_capacity, self.max_keypoints = int(kf_capacity), int(mp_capacity), int(max_keypoints)
+        self._h = ctypes.c_void_p()
+        _check(lib().orbx_covis_create(ctx.handle, self.kf_capacity, self.mp_capacity, self.max_keypoints,
+                                       ctypes.byref(self._h)), "orbx_covis_create")
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if self._h:
+            lib().orbx_covis_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return lib().orbx_covis_size(self._h)
+
+    def clear(self):
+        _check(lib().orbx_covis_clear(self._ctx.handle, self._h), "orbx_covis_clear")
+
+    def add_keyframe(self, kf_id, key, mp):
+        """A keyframe with its row mvpMapPoints (point ids or -1)."""
+        mp = np.ascontiguousarray(mp, np.int32).reshape(-1)
+        _check(lib().orbx_covis_add_keyframe(self._ctx.handle, self._h, int(kf_id), int(key), len(mp),
+                                             _ptr(mp) if len(mp) else None), "orbx_covis_add_keyframe")
+
+    def set_matches(self, kf_id, idx, mp):
+        """row[idx[k]] = mp[k] in order; -1 erases the match."""
+        idx = np.ascontiguousarray(idx, np.int32).reshape(-1)
+        mp = np.ascontiguousarray(mp, np.int32).reshape(-1)
+        if len(idx) != len(mp):
+            raise ValueError("as many points as indices")
+        _check(lib().orbx_covis_set_matches(self._ctx.handle, self._h, int(kf_id), len(idx), _ptr(idx) if len(idx) else None,
+                                            _ptr(mp) if len(mp) else None), "orbx_covis_set_matches")
+
+    def erase_points(self, ids):
+        """MapPoint::SetBadFlag for every id."""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        _check(lib().orbx_covis_erase_points(self._ctx.handle, self._h, len(ids), _ptr(ids) if len(ids) else None),
+               "orbx_covis_erase_points")
+
+    def erase_keyframe(self, kf_id):
+        """The connection part of KeyFrame::SetBadFlag."""
+        _check(lib().orbx_covis_erase_keyframe(self._ctx.handle, self._h, int(kf_id)), "orbx_covis_erase_keyframe")
+
+    def update_connections(self, ids, th=15):
+        """KeyFrame::UpdateConnections for `ids`, in order: (updated, front)."""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        updated = np.zeros(max(len(ids), 1), np.int32)
+        front = np.full(max(len(ids), 1), -1, np.int32)
+        _check(lib().orbx_covis_update_connections(self._ctx.handle, self._h, len(ids), _ptr(ids) if len(ids) else None,
+                                                   int(th), _ptr(updated), _ptr(front)), "orbx_covis_update_connections")
+        return updated[:len(ids)], front[:len(ids)]
+
+    def connections(self, kf_id, which=COVIS_ORDERED, cap=None):
+        """(keyframes, weights): the ordered list (COVIS_ORDERED) or the whole
+        row in ascending key order (COVIS_ALL)."""
+        cap = self.kf_capacity if cap is None else int(cap)
+        kfs, ws = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32)
+        n = ctypes.c_int()
+        _check(lib().orbx_covis_connections(self._ctx.handle, self._h, int(kf_id), int(which), _ptr(kfs), _ptr(ws), cap,
+                                            ctypes.byref(n)), "orbx_covis_connections")
+        return kfs[:n.value].copy(), ws[:n.value].copy()
+
+    def best_covisibility_keyframes(self, kf_id, n):
+        """GetBestCovisibilityKeyFrames(n)."""
+        return self.connections(kf_id)[0][:n]
+
+    def update_reference(self, frame_mp, kf_cap=None, mp_cap=None):
+        """Tracking::UpdateReferenceKeyFrames + UpdateReferencePoints: a dict
+        of frame_erased, local_kf, n_voters, ref_kf and local_mp."""
+        f = np.ascontiguousarray(frame_mp, np.int32).reshape(-1)
+        q = CovisReference()
+        q.n = len(f)
+        er = np.zeros(max(len(f), 1), np.uint8)
+        q.kf_cap = self.kf_capacity if kf_cap is None else int(kf_cap)
+        q.mp_cap = min(self.mp_capacity, self.kf_capacity * self.max_keypoints) if mp_cap is None else int(mp_cap)
+        lk, lm = np.zeros(max(q.kf_cap, 1), np.int32), np.zeros(max(q.mp_cap, 1), np.int32)
+        q.frame_mp = f.ctypes.data if len(f) else None
+        q.frame_erased, q.local_kf, q.local_mp = er.ctypes.data, lk.ctypes.data, lm.ctypes.data
+        r = lib().orbx_covis_update_reference(self._ctx.handle, self._h, ctypes.byref(q))
+        out = dict(frame_erased=er[:len(f)].copy(), n_local_kf=q.n_local_kf, n_voters=q.n_voters, ref_kf=q.ref_kf,
+                   n_local_mp=q.n_local_mp, local_kf=lk[:min(q.n_local_kf, q.kf_cap)].copy(),
+                   local_mp=lm[:min(q.n_local_mp, q.mp_cap)].copy(), code=r)
+        if r != -3 or (kf_cap is None and mp_cap is None):   # with caps of the caller's, ORBX_ERR_CAPACITY is an answer
+            _check(r, "orbx_covis_update_reference")
+        return out
 
 
 def describe_levels(w, h, nfeatures=1000, scale_factor=1.2, nlevels=8, fast_th=20):

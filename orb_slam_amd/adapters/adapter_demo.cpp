@@ -627,9 +627,57 @@ int main()
             return d;
         };
         std::printf("\"kfdb_reloc\": %d, \"kfdb_reloc_readded\": %d, \"kfdb_loop\": %d, \"kfdb_min_score\": %.6f, "
-                    "\"kfdb_loop_above\": %zu, \"kfdb_score\": [%.6f, %.6f], \"kfdb_size_after_clear\": %d}\n",
+                    "\"kfdb_loop_above\": %zu, \"kfdb_score\": [%.6f, %.6f], \"kfdb_size_after_clear\": %d, ",
                     digits(kf_reloc), digits(kf_reloc2), digits(kf_loop), (double)kf_min, kf_loop_hi.size(),
                     (double)kf_scores[0], (double)kf_scores[1], kfdb.size());
+        // CovisibilityGraph: four keyframes whose keys (the KeyFrame* stand-ins) run 2 < 4 < 3 < 1, updated in
+        // the order 1, 2, 3, 4 with th = 2.  1 counts 2 three times, 3 twice and 4 once: its list is 2 3, its
+        // set in key order 2 4 3.  4 counts 1 and 3 once each: the fallback is 3, the smaller key.  Then 4 gains
+        // point 14 and counts 1 and 3 twice: new weights, so the lists of 1 and 3 are rebuilt in full, with the
+        // larger key first among equal weights.
+        CovisibilityGraph covis(ex.context(), 8, 64, 8);
+        covis.AddKeyFrame(1, 400, {10, 11, 12, 13, 14, 15});
+        covis.AddKeyFrame(2, 100, {10, 11, 12, 20, 21});
+        covis.AddKeyFrame(3, 300, {13, 14, 20, 30});
+        covis.AddKeyFrame(4, 200, {15, 30, 31});
+        const std::vector<int> cv_fronts = covis.UpdateConnections(std::vector<int>{1, 2, 3}, 2);
+        const bool cv_updated4 = covis.UpdateConnections(4, 2);
+        const int cv_front4 = covis.mFront;
+        const int cv_ordered1 = digits(covis.GetVectorCovisibleKeyFrames(1));
+        const int cv_connected1 = digits(covis.GetConnectedKeyFrames(1));
+        const int cv_weight14 = covis.GetWeight(1, 4), cv_weight24 = covis.GetWeight(2, 4);
+        const int cv_best1 = digits(covis.GetBestCovisibilityKeyFrames(1, 1));
+        const int cv_by_weight3 = digits(covis.GetCovisiblesByWeight(1, 3));       // weights 3 2: the first below 3
+        const size_t cv_by_weight2 = covis.GetCovisiblesByWeight(1, 2).size();     // every weight >= 2: end(), empty
+        covis.EraseMapPointMatch(4, 2);
+        covis.AddMapPoint(4, 14, 2);
+        covis.UpdateConnections(4, 2);
+        const int cv_front4b = covis.mFront;
+        const int cv_ordered1b = digits(covis.GetVectorCovisibleKeyFrames(1));
+        const int cv_ordered3b = digits(covis.GetVectorCovisibleKeyFrames(3));
+        const int cv_ordered4b = digits(covis.GetVectorCovisibleKeyFrames(4));
+        // a frame that sees 10, 20 twice and 30: 2 and 3 get three votes, 2 comes first in key order
+        const CovisibilityGraph::Reference cv_ref = covis.UpdateReference({10, 20, 20, 30});
+        covis.EraseMapPoints({20});
+        const CovisibilityGraph::Reference cv_ref2 = covis.UpdateReference({10, 20, 20, 30});
+        covis.EraseKeyFrame(2);   // EraseConnection on 1 and 3
+        const int cv_ordered1c = digits(covis.GetVectorCovisibleKeyFrames(1));
+        kfdb.add(1, BowVector({10, 40}, {.5, .5}));
+        covis.PushBestCovisibles(kfdb, 1);
+        std::printf("\"covis_fronts\": %d, \"covis_updated4\": %d, \"covis_front4\": %d, \"covis_ordered1\": %d, "
+                    "\"covis_connected1\": %d, \"covis_weights\": [%d, %d], \"covis_best1\": %d, "
+                    "\"covis_by_weight3\": %d, \"covis_by_weight2_size\": %zu, \"covis_front4_new\": %d, "
+                    "\"covis_ordered1_new\": %d, \"covis_ordered3_new\": %d, \"covis_ordered4_new\": %d, "
+                    "\"covis_local_kf\": %d, \"covis_ref_kf\": %d, \"covis_voters\": %d, \"covis_local_mp\": %d, "
+                    "\"covis_local_mp_n\": %zu, \"covis_frame_erased\": %d, \"covis_ref_kf_after\": %d, "
+                    "\"covis_ordered1_after_erase\": %d, \"covis_size\": %d}\n",
+                    digits(cv_fronts), cv_updated4 ? 1 : 0, cv_front4, cv_ordered1, cv_connected1, cv_weight14,
+                    cv_weight24, cv_best1, cv_by_weight3, cv_by_weight2, cv_front4b, cv_ordered1b, cv_ordered3b,
+                    cv_ordered4b, digits(cv_ref.mvpLocalKeyFrames), cv_ref.mpReferenceKF, cv_ref.nVoters,
+                    cv_ref.mvpLocalMapPoints.empty() ? -1 : cv_ref.mvpLocalMapPoints.back(),
+                    cv_ref.mvpLocalMapPoints.size(),
+                    digits(std::vector<int>(cv_ref2.vbErased.begin(), cv_ref2.vbErased.end())), cv_ref2.mpReferenceKF,
+                    cv_ordered1c, covis.size());
         return 0;
     } catch (const orbx_error& e) {
         std::fprintf(stderr, "%s\n", e.what());

@@ -1318,4 +1318,168 @@ private:
     int capacity_;
 };
 
+// ---------------------------------------------------------------------------
+// The covisibility graph (KeyFrame::mvpMapPoints, mConnectedKeyFrameWeights,
+// mvpOrderedConnectedKeyFrames of every keyframe) in HBM, with the reference's
+// method names.  Keyframes and map points are named by mnId; where the
+// reference's order depends on KeyFrame* values, the keyframe's `key` stands
+// for the pointer: pass (uint64_t)(uintptr_t)pKF to AddKeyFrame.
+// ---------------------------------------------------------------------------
+class CovisibilityGraph {
+public:
+    CovisibilityGraph(orbx_ctx* ctx, int kfCapacity, int mpCapacity, int maxKeypoints)
+        : ctx_(ctx), kf_capacity_(kfCapacity)
+    {
+        if (orbx_abi_version() != ORBX_ABI_VERSION) throw orbx_error(ORBX_ERR_UNSUPPORTED, "orbx_abi_version");
+        check(orbx_covis_create(ctx, kfCapacity, mpCapacity, maxKeypoints, &m_), "CovisibilityGraph");
+    }
+    ~CovisibilityGraph() { orbx_covis_destroy(m_); }
+    CovisibilityGraph(const CovisibilityGraph&) = delete;
+    CovisibilityGraph& operator=(const CovisibilityGraph&) = delete;
+
+    // Where LocalMapping::ProcessNewKeyFrame has added the keyframe's
+    // observations (src/LocalMapping.cc:130-160): vpMapPoints is
+    // GetMapPointMatches() as mnIds, -1 for NULL.
+    void AddKeyFrame(int mnId, uint64_t key, const std::vector<int>& vpMapPoints)
+    {
+        const std::vector<int32_t> mp(vpMapPoints.begin(), vpMapPoints.end());
+        check(orbx_covis_add_keyframe(ctx_, m_, mnId, key, (int)mp.size(), mp.data()), "CovisibilityGraph::AddKeyFrame");
+    }
+    // pKF->AddMapPoint(pMP, idx) with pMP->AddObservation(pKF, idx)
+    void AddMapPoint(int kfId, int mpId, size_t idx)
+    {
+        const int32_t i = (int32_t)idx, p = mpId;
+        check(orbx_covis_set_matches(ctx_, m_, kfId, 1, &i, &p), "CovisibilityGraph::AddMapPoint");
+    }
+    // pKF->EraseMapPointMatch(idx) with pMP->EraseObservation(pKF)
+    void EraseMapPointMatch(int kfId, size_t idx) { AddMapPoint(kfId, -1, idx); }
+    // MapPoint::SetBadFlag of every id (and the old point of MapPoint::Replace)
+    void EraseMapPoints(const std::vector<int>& ids)
+    {
+        const std::vector<int32_t> p(ids.begin(), ids.end());
+        check(orbx_covis_erase_points(ctx_, m_, (int)p.size(), p.data()), "CovisibilityGraph::EraseMapPoints");
+    }
+    // the connection part of KeyFrame::SetBadFlag (src/KeyFrame.cc:510-521)
+    void EraseKeyFrame(int mnId) { check(orbx_covis_erase_keyframe(ctx_, m_, mnId), "CovisibilityGraph::EraseKeyFrame"); }
+    int size() const { return orbx_covis_size(m_); }
+
+    // void KeyFrame::UpdateConnections() (:332-421).  Returns false where the
+    // reference returns at `if(KFcounter.empty())`; mFront is then -1, else
+    // mvpOrderedConnectedKeyFrames.front() (mpParent under mbFirstConnection).
+    bool UpdateConnections(int mnId, int th = 15)
+    {
+        const int32_t id = mnId;
+        int32_t updated = 0, front = -1;
+        check(orbx_covis_update_connections(ctx_, m_, 1, &id, th, &updated, &front), "CovisibilityGraph::UpdateConnections");
+        mFront = front;
+        return updated != 0;
+    }
+    // CorrectLoop's loop over the connected keyframes (src/LoopClosing.cc:
+    // 411-412), in the given order; fronts as above.
+    std::vector<int> UpdateConnections(const std::vector<int>& ids, int th = 15)
+    {
+        const std::vector<int32_t> i32(ids.begin(), ids.end());
+        std::vector<int32_t> updated(ids.size() + 1), front(ids.size() + 1);
+        check(orbx_covis_update_connections(ctx_, m_, (int)i32.size(), i32.data(), th, updated.data(), front.data()),
+              "CovisibilityGraph::UpdateConnections");
+        return std::vector<int>(front.begin(), front.begin() + ids.size());
+    }
+
+    // vector<KeyFrame*> GetVectorCovisibleKeyFrames() (:171-175); mvOrderedWeights of the call in mWeights
+    std::vector<int> GetVectorCovisibleKeyFrames(int mnId) { return read(mnId, ORBX_COVIS_ORDERED); }
+    // vector<KeyFrame*> GetBestCovisibilityKeyFrames(const int &N) (:177-185)
+    std::vector<int> GetBestCovisibilityKeyFrames(int mnId, int N)
+    {
+        std::vector<int> v = read(mnId, ORBX_COVIS_ORDERED);
+        if ((int)v.size() > N) v.resize((size_t)N);
+        return v;
+    }
+    // set<KeyFrame*> GetConnectedKeyFrames() (:162-169), in the set's order
+    std::vector<int> GetConnectedKeyFrames(int mnId) { return read(mnId, ORBX_COVIS_ALL); }
+    // int GetWeight(KeyFrame* pKF) (:204-211)
+    int GetWeight(int mnId, int pKF)
+    {
+        const std::vector<int> all = read(mnId, ORBX_COVIS_ALL);
+        for (size_t k = 0; k < all.size(); k++)
+            if (all[k] == pKF) return mWeights[k];
+        return 0;
+    }
+    // vector<KeyFrame*> GetCovisiblesByWeight(const int &w) (:187-202), the
+    // reference's upper_bound as it stands: with weightComp(a, b) = a > b it
+    // finds the first weight below w, and when every weight is >= w it
+    // returns end() and the function an empty vector.
+    std::vector<int> GetCovisiblesByWeight(int mnId, int w)
+    {
+        const std::vector<int> ordered = read(mnId, ORBX_COVIS_ORDERED);
+        if (ordered.empty()) return std::vector<int>();
+        const std::vector<int>::iterator it =
+            std::upper_bound(mWeights.begin(), mWeights.end(), w, [](int a, int b) { return a > b; });
+        if (it == mWeights.end()) return std::vector<int>();
+        return std::vector<int>(ordered.begin(), ordered.begin() + (it - mWeights.begin()));
+    }
+
+    // Tracking::UpdateReference's two functions (src/Tracking.cc:764-865) for
+    // mCurrentFrame.mvpMapPoints as mnIds (-1 for NULL).
+    struct Reference {
+        std::vector<int> mvpLocalKeyFrames, mvpLocalMapPoints;
+        int mpReferenceKF = -1;            // pKFmax, -1 for NULL
+        int nVoters = 0;                   // keyframes that observe a point of the frame
+        std::vector<uint8_t> vbErased;     // 1: the frame's point is bad, NULL it (:805-808)
+    };
+    Reference UpdateReference(const std::vector<int>& vpMapPoints)
+    {
+        const std::vector<int32_t> f(vpMapPoints.begin(), vpMapPoints.end());
+        Reference r;
+        r.vbErased.assign(f.size() + 1, 0);
+        std::vector<int32_t> lk((size_t)kf_capacity_), lm(1024);
+        orbx_covis_reference_args q{};
+        q.n = (int)f.size();
+        q.frame_mp = f.data();
+        q.frame_erased = r.vbErased.data();
+        q.local_kf = lk.data();
+        q.kf_cap = kf_capacity_;
+        for (;;) {   // the list of points grows with the map: once more with the size the call reported
+            q.local_mp = lm.data();
+            q.mp_cap = (int)lm.size();
+            const int code = orbx_covis_update_reference(ctx_, m_, &q);
+            if (code == ORBX_ERR_CAPACITY && q.n_local_mp > q.mp_cap) {
+                lm.resize((size_t)q.n_local_mp);
+                continue;
+            }
+            check(code, "CovisibilityGraph::UpdateReference");
+            break;
+        }
+        r.vbErased.resize(f.size());
+        r.mvpLocalKeyFrames.assign(lk.begin(), lk.begin() + q.n_local_kf);
+        r.mvpLocalMapPoints.assign(lm.begin(), lm.begin() + q.n_local_mp);
+        r.mpReferenceKF = q.ref_kf;
+        r.nVoters = q.n_voters;
+        return r;
+    }
+
+    // Where KeyFrame::UpdateBestCovisibles runs: the keyframe's first 10 go to
+    // the device KeyFrameDatabase, which accumulates scores over them.
+    void PushBestCovisibles(KeyFrameDatabase& db, int mnId)
+    {
+        db.SetBestCovisibles(mnId, GetBestCovisibilityKeyFrames(mnId, ORBX_KFDB_NEIGHBOURS));
+    }
+
+    int mFront = -1;              // the last single UpdateConnections' front
+    std::vector<int> mWeights;    // the weights of the last read, entry for entry
+
+private:
+    std::vector<int> read(int mnId, int which)
+    {
+        std::vector<int32_t> kfs((size_t)kf_capacity_), ws((size_t)kf_capacity_);
+        int n = 0;
+        check(orbx_covis_connections(ctx_, m_, mnId, which, kfs.data(), ws.data(), kf_capacity_, &n),
+              "CovisibilityGraph::read");
+        mWeights.assign(ws.begin(), ws.begin() + n);
+        return std::vector<int>(kfs.begin(), kfs.begin() + n);
+    }
+    orbx_ctx* ctx_;
+    orbx_covis* m_ = nullptr;
+    int kf_capacity_;
+};
+
 }  // namespace ORB_SLAM_AMD
