@@ -73,8 +73,11 @@ extern "C" {
  *      size, orbx_covis_add_keyframe, orbx_covis_set_matches,
  *      orbx_covis_erase_points, orbx_covis_erase_keyframe,
  *      orbx_covis_update_connections, orbx_covis_connections,
- *      orbx_covis_update_reference); additions only. */
-#define ORBX_ABI_VERSION 14
+ *      orbx_covis_update_reference); additions only.
+ *  15: LocalMapping's culling on the covisibility graph
+ *      (orbx_covis_set_octaves, orbx_covis_cull_keyframes,
+ *      orbx_covis_cull_points); additions only. */
+#define ORBX_ABI_VERSION 15
 int orbx_abi_version(void);
 
 #define ORBX_OK               0
@@ -1511,7 +1514,9 @@ int orbx_kfdb_score(orbx_ctx* ctx, orbx_kfdb* db, int slot, int n_words, const u
  * (src/LocalMapping.cc:130-160), not where Tracking constructs it.  A point
  * stands at most once in a row (mObservations holds one index per keyframe).
  * MapPoint::EraseObservation turns a point bad when two observations or
- * fewer remain; that is a SetBadFlag, mirrored with orbx_covis_erase_points.
+ * fewer remain; that is a SetBadFlag, mirrored with orbx_covis_erase_points
+ * (orbx_covis_cull_keyframes applies the rule itself for the keyframes it
+ * culls).
  *
  * Erased points (MapPoint::isBad()).  An erased id in an input row or in a
  * frame is no error: it is skipped as the reference skips a bad point.
@@ -1607,6 +1612,71 @@ typedef struct {
  * of range, cap < 0; ORBX_ERR_CAPACITY with the three counts set when a list
  * exceeds its capacity (the capacity's worth of entries is written). */
 int orbx_covis_update_reference(orbx_ctx* ctx, orbx_covis* m, orbx_covis_reference_args* q);
+
+/* LocalMapping's two culling walks on the table (src/LocalMapping.cc:190-218,
+ * :539-593).
+ *
+ * mvKeysUn[i].octave of member id, n = the row length given at
+ * orbx_covis_add_keyframe.  orbx_covis_cull_keyframes needs them of every
+ * member.  ORBX_ERR_ARG: not a member, another n, a null pointer with n > 0. */
+int orbx_covis_set_octaves(orbx_ctx* ctx, orbx_covis* m, int id, int n, const uint8_t* octave);
+
+typedef struct {
+    /* in */
+    int cur;                              /* mpCurrentKeyFrame, a member: the candidates are its ordered
+                                             list (GetVectorCovisibleKeyFrames) as the call finds it, taken
+                                             on the device; -1: the caller's list cand[0, n_cand)          */
+    int n_keep; const int32_t* keep;      /* the keyframes with mbNotErase set; may be empty               */
+    int max_culls;                        /* 0: no limit; else the call stops right after that many culls  */
+    int cand_cap;                         /* entries of cand, n_mps, n_redundant and decision              */
+    /* in (cur == -1) / out */
+    int32_t* cand; int n_cand;            /* vpLocalKeyFrames                                              */
+    /* out */
+    int n_done;                           /* candidates processed                                          */
+    int32_t* n_mps;                       /* [n_done] nMPs                                                 */
+    int32_t* n_redundant;                 /* [n_done] nRedundantObservations                               */
+    int32_t* decision;                    /* [n_done] -1: keyframe 0 or no member, skipped; 0: stays;
+                                             1: culled; 2: redundant but kept (mbToBeErased)               */
+    int32_t* bad_points; int bad_cap;     /* the points that a cull left with two observers or fewer, by
+                                             culled keyframe in candidate order, ascending row index within */
+    int n_bad;                            /* its size                                                      */
+} orbx_covis_cull_args;
+/* LocalMapping::KeyFrameCulling.  Candidate c at place k is judged against the
+ * state (members, rows, erased points, connections) as the candidates before
+ * it left it.  c == 0 or no member: decision -1, nothing changes.  Otherwise
+ * nMPs = the entries of row c that are a point and not erased; such an entry
+ * (idx, p) with o = octave_c[idx] is redundant when at least three members
+ * j != c hold p at an index idx_j with octave_j[idx_j] <= o + 1.  With
+ * (double)nRedundant > 0.9 * (double)nMPs false the decision is 0; true with c
+ * in keep it is 2 and nothing changes; true otherwise it is 1 and the graph
+ * part of KeyFrame::SetBadFlag runs: the connection part exactly as
+ * orbx_covis_erase_keyframe, row c goes, and MapPoint::EraseObservation for
+ * every point of the row: a point, not erased, that two members or fewer still
+ * hold becomes erased and is cleared from every row, as orbx_covis_erase_points
+ * does it, and is appended to bad_points.  The spanning tree stays with the
+ * caller, which reads the children's lists right after one cull: call with
+ * max_culls = 1, repair the tree, resume with cur = -1 and cand + n_done.  A
+ * resumed sequence leaves the state and the decisions of one unlimited call.
+ * ORBX_ERR_ARG (no change): cur no member (or below -1), a listed or kept id
+ * outside [0, kf_capacity), n_cand above kf_capacity, a member whose octaves
+ * were never set, max_culls or a count or capacity below 0, a null pointer.
+ * ORBX_ERR_CAPACITY (no change to the graph, n_cand, n_done and n_bad set, the
+ * capacities' worth of entries written): n_cand > cand_cap or n_bad > bad_cap;
+ * n_cand <= kf_capacity, n_bad <= the sum of the culled rows' lengths. */
+int orbx_covis_cull_keyframes(orbx_ctx* ctx, orbx_covis* m, orbx_covis_cull_args* q);
+/* LocalMapping::MapPointCulling over mlpRecentAddedMapPoints = ids[0, n), each
+ * id once, with mnFound, mnVisible and mnFirstKFid of each and cur_kf =
+ * mpCurrentKeyFrame->mnId.  action[k], by the reference's if-chain: 1 the point
+ * is erased already (drop it from the list); 2 (float)found / (float)visible <
+ * 0.25f in FP32 (visible == 0 gives inf or NaN: false): SetBadFlag and drop; 3
+ * cur_kf - first_kf >= 2 and two observers (members whose row holds the point)
+ * or fewer: SetBadFlag and drop; 4 cur_kf - first_kf >= 3: drop; 0 keep.  The
+ * points of actions 2 and 3 are erased as orbx_covis_erase_points erases them.
+ * ORBX_ERR_ARG (no change): an id out of range or listed twice, found or
+ * visible below 0, first_kf > cur_kf or below 0, n < 0, a null pointer with
+ * n > 0. */
+int orbx_covis_cull_points(orbx_ctx* ctx, orbx_covis* m, int cur_kf, int n, const int32_t* ids, const int32_t* found,
+                           const int32_t* visible, const int32_t* first_kf, int32_t* action);
 
 /* ------------------------------------------------------------------------ */
 /* C. Local bundle adjustment                                                */

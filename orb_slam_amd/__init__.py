@@ -796,6 +796,9 @@ def _declare(L):
         "orbx_covis_update_connections": ([vp, vp, i, vp, i, vp, vp], i),
         "orbx_covis_connections": ([vp, vp, i, i, vp, vp, i, ctypes.POINTER(i)], i),
         "orbx_covis_update_reference": ([vp, vp, vp], i),
+        "orbx_covis_set_octaves": ([vp, vp, i, i, vp], i),
+        "orbx_covis_cull_keyframes": ([vp, vp, vp], i),
+        "orbx_covis_cull_points": ([vp, vp, i, i, vp, vp, vp, vp, vp], i),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(L, name)
@@ -1701,6 +1704,15 @@ class CovisReference(ctypes.Structure):
                 ("mp_cap", ctypes.c_int), ("n_local_mp", ctypes.c_int)]
 
 
+class CovisCull(ctypes.Structure):
+    """orbx_covis_cull_args (include/orbx.h)."""
+    _fields_ = [("cur", ctypes.c_int), ("n_keep", ctypes.c_int), ("keep", ctypes.c_void_p),
+                ("max_culls", ctypes.c_int), ("cand_cap", ctypes.c_int), ("cand", ctypes.c_void_p),
+                ("n_cand", ctypes.c_int), ("n_done", ctypes.c_int), ("n_mps", ctypes.c_void_p),
+                ("n_redundant", ctypes.c_void_p), ("decision", ctypes.c_void_p), ("bad_points", ctypes.c_void_p),
+                ("bad_cap", ctypes.c_int), ("n_bad", ctypes.c_int)]
+
+
 COVIS_ORDERED, COVIS_ALL = 0, 1
 COVIS_MAX_KEYFRAMES, COVIS_MAX_KEYPOINTS, COVIS_MAX_POINTS = 8192, 65535, 1 << 27
 
@@ -1807,6 +1819,54 @@ class CovisibilityMap:
         if r != -3 or (kf_cap is None and mp_cap is None):   # with caps of the caller's, ORBX_ERR_CAPACITY is an answer
             _check(r, "orbx_covis_update_reference")
         return out
+
+    def set_octaves(self, kf_id, octave):
+        """mvKeysUn[i].octave of a member, as many as its row has entries."""
+        o = np.ascontiguousarray(octave, np.uint8).reshape(-1)
+        _check(lib().orbx_covis_set_octaves(self._ctx.handle, self._h, int(kf_id), len(o), _ptr(o) if len(o) else None),
+               "orbx_covis_set_octaves")
+
+    def cull_keyframes(self, cur=-1, keep=(), max_culls=0, cand=None, cand_cap=None, bad_cap=None):
+        """LocalMapping::KeyFrameCulling over the ordered list of member `cur`,
+        or over `cand` with cur = -1 (the form that resumes after max_culls):
+        a dict of cand, n_done, n_mps, n_redundant, decision (-1 skipped, 0
+        stays, 1 culled, 2 kept by `keep`) and bad_points."""
+        keep = np.ascontiguousarray(keep, np.int32).reshape(-1)
+        q = CovisCull()
+        q.cur, q.max_culls = int(cur), int(max_culls)
+        q.n_keep, q.keep = len(keep), (keep.ctypes.data if len(keep) else None)
+        given = np.ascontiguousarray(cand if cand is not None else [], np.int32).reshape(-1)
+        room = max(self.kf_capacity, len(given))
+        q.cand_cap = room if cand_cap is None else int(cand_cap)
+        q.bad_cap = min(self.mp_capacity, self.kf_capacity * self.max_keypoints) if bad_cap is None else int(bad_cap)
+        size = max(q.cand_cap, len(given), 1)
+        c, nm, nr, de = (np.zeros(size, np.int32) for _ in range(4))
+        c[:len(given)] = given
+        q.n_cand = len(given)
+        bad = np.zeros(max(q.bad_cap, 1), np.int32)
+        q.cand, q.n_mps, q.n_redundant, q.decision = c.ctypes.data, nm.ctypes.data, nr.ctypes.data, de.ctypes.data
+        q.bad_points = bad.ctypes.data
+        r = lib().orbx_covis_cull_keyframes(self._ctx.handle, self._h, ctypes.byref(q))
+        if r != -3 or (cand_cap is None and bad_cap is None):   # with caps of the caller's, ORBX_ERR_CAPACITY is an answer
+            _check(r, "orbx_covis_cull_keyframes")
+        nd = min(q.n_done, q.cand_cap)
+        return dict(code=r, n_cand=q.n_cand, n_done=q.n_done, n_bad=q.n_bad, cand=c[:min(q.n_cand, max(q.cand_cap, len(given)))].copy(),
+                    n_mps=nm[:nd].copy(), n_redundant=nr[:nd].copy(), decision=de[:nd].copy(),
+                    bad_points=bad[:min(q.n_bad, q.bad_cap)].copy())
+
+    def cull_points(self, cur_kf, ids, found, visible, first_kf):
+        """LocalMapping::MapPointCulling over mlpRecentAddedMapPoints = ids:
+        the action per point (0 keep, 1 erased already, 2 found ratio, 3 two
+        observers or fewer, 4 old enough to leave the list)."""
+        a = [np.ascontiguousarray(x, np.int32).reshape(-1) for x in (ids, found, visible, first_kf)]
+        n = len(a[0])
+        if any(len(x) != n for x in a):
+            raise ValueError("one entry per point in every array")
+        action = np.zeros(max(n, 1), np.int32)
+        ptrs = [x.ctypes.data if n else None for x in a]
+        _check(lib().orbx_covis_cull_points(self._ctx.handle, self._h, int(cur_kf), n, *ptrs, action.ctypes.data),
+               "orbx_covis_cull_points")
+        return action[:n]
 
 
 def describe_levels(w, h, nfeatures=1000, scale_factor=1.2, nlevels=8, fast_th=20):

@@ -670,7 +670,7 @@ int main()
                     "\"covis_ordered1_new\": %d, \"covis_ordered3_new\": %d, \"covis_ordered4_new\": %d, "
                     "\"covis_local_kf\": %d, \"covis_ref_kf\": %d, \"covis_voters\": %d, \"covis_local_mp\": %d, "
                     "\"covis_local_mp_n\": %zu, \"covis_frame_erased\": %d, \"covis_ref_kf_after\": %d, "
-                    "\"covis_ordered1_after_erase\": %d, \"covis_size\": %d}\n",
+                    "\"covis_ordered1_after_erase\": %d, \"covis_size\": %d, ",
                     digits(cv_fronts), cv_updated4 ? 1 : 0, cv_front4, cv_ordered1, cv_connected1, cv_weight14,
                     cv_weight24, cv_best1, cv_by_weight3, cv_by_weight2, cv_front4b, cv_ordered1b, cv_ordered3b,
                     cv_ordered4b, digits(cv_ref.mvpLocalKeyFrames), cv_ref.mpReferenceKF, cv_ref.nVoters,
@@ -678,6 +678,36 @@ int main()
                     cv_ref.mvpLocalMapPoints.size(),
                     digits(std::vector<int>(cv_ref2.vbErased.begin(), cv_ref2.vbErased.end())), cv_ref2.mpReferenceKF,
                     cv_ordered1c, covis.size());
+        // LocalMapping's culling.  Keyframes 0, 2, 3, 4 and 5 hold points 10..19; 2, 4 and 5 hold 50 as well, 5
+        // also 60.  The tree is 0 <- 2 <- {3, 4}, 4 <- 5.  KeyFrameCulling(5) walks 4, 2, 3, 0 (weights 11, 11,
+        // 10, 10, the larger key first).  4: ten of eleven points have three other observers, 10 > 9.9, but
+        // LoopClosing holds it.  2: the same, culled; 50 is left with 4 and 5 and goes bad; 3 takes the parent 0
+        // (weight 10, the first in key order), then 4 takes 3.  3: 0, 4 and 5 still see its ten points, culled;
+        // 4 takes 0.  0 is skipped.  MapPointCulling(5): 10 stays, 60 was found once in five frames, 50 is bad.
+        CovisibilityGraph lm(ex.context(), 8, 64, 16);
+        const std::vector<int> shared = {10, 11, 12, 13, 14, 15, 16, 17, 18, 19};
+        for (int id : {0, 2, 3, 4, 5}) {
+            std::vector<int> row = shared;
+            if (id == 2 || id == 4 || id == 5) row.push_back(50);
+            if (id == 5) row.push_back(60);
+            lm.AddKeyFrame(id, 100 * (uint64_t)id + 7, row);
+            lm.SetOctaves(id, std::vector<int>(row.size(), 0));
+            lm.UpdateConnections(id, 1);
+        }
+        lm.ChangeParent(2, 0);
+        lm.ChangeParent(3, 2);
+        lm.ChangeParent(4, 2);
+        lm.ChangeParent(5, 4);
+        const int lm_list5 = digits(lm.GetVectorCovisibleKeyFrames(5));
+        const CovisibilityGraph::Culling lm_cull = lm.KeyFrameCulling(5, {4});
+        std::list<CovisibilityGraph::RecentMapPoint> lm_recent = {{10, 5, 5, 3}, {60, 1, 5, 5}, {50, 4, 4, 4}};
+        const std::vector<int> lm_bad = lm.MapPointCulling(5, lm_recent);
+        std::printf("\"cull_list5\": %d, \"cull_culled\": %d, \"cull_to_be_erased\": %d, \"cull_bad_points\": %d, "
+                    "\"cull_parents\": [%d, %d, %d], \"cull_childs0\": %d, \"cull_size\": %d, \"cull_mp_bad\": %d, "
+                    "\"cull_mp_left\": %d, \"cull_mp_left_n\": %zu}\n",
+                    lm_list5, digits(lm_cull.vpCulled), digits(lm_cull.vpToBeErased), digits(lm_cull.vpBadMapPoints),
+                    lm.GetParent(3), lm.GetParent(4), lm.GetParent(5), digits(lm.GetChilds(0)), lm.size(),
+                    digits(lm_bad), lm_recent.empty() ? -1 : lm_recent.front().mnId, lm_recent.size());
         return 0;
     } catch (const orbx_error& e) {
         std::fprintf(stderr, "%s\n", e.what());

@@ -25,6 +25,8 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <list>
+#include <map>
 #include <memory>
 #include <set>
 #include <stdexcept>
@@ -1344,6 +1346,7 @@ public:
     {
         const std::vector<int32_t> mp(vpMapPoints.begin(), vpMapPoints.end());
         check(orbx_covis_add_keyframe(ctx_, m_, mnId, key, (int)mp.size(), mp.data()), "CovisibilityGraph::AddKeyFrame");
+        keys_[mnId] = key;
     }
     // pKF->AddMapPoint(pMP, idx) with pMP->AddObservation(pKF, idx)
     void AddMapPoint(int kfId, int mpId, size_t idx)
@@ -1464,10 +1467,169 @@ public:
         db.SetBestCovisibles(mnId, GetBestCovisibilityKeyFrames(mnId, ORBX_KFDB_NEIGHBOURS));
     }
 
+    // mvKeysUn[i].octave of keyframe mnId, one per entry of its row: what
+    // KeyFrameCulling reads through GetKeyPointUn(i).octave
+    void SetOctaves(int mnId, const std::vector<int>& vOctaves)
+    {
+        const std::vector<uint8_t> o(vOctaves.begin(), vOctaves.end());
+        check(orbx_covis_set_octaves(ctx_, m_, mnId, (int)o.size(), o.data()), "CovisibilityGraph::SetOctaves");
+    }
+
+    // The spanning tree (KeyFrame::mpParent, mspChildrens) stays on the host;
+    // the children of a keyframe are iterated in key order (a set<KeyFrame*>).
+    void ChangeParent(int mnId, int pKF)
+    {
+        EraseChild(GetParent(mnId), mnId);
+        mpParent_[mnId] = pKF;
+        if (pKF >= 0) mspChildrens_[pKF].push_back(mnId);
+    }
+    int GetParent(int mnId) const
+    {
+        const std::map<int, int>::const_iterator it = mpParent_.find(mnId);
+        return it == mpParent_.end() ? -1 : it->second;
+    }
+    std::vector<int> GetChilds(int mnId) const
+    {
+        const std::map<int, std::vector<int>>::const_iterator it = mspChildrens_.find(mnId);
+        std::vector<int> c = it == mspChildrens_.end() ? std::vector<int>() : it->second;
+        std::sort(c.begin(), c.end(), [this](int a, int b) { return keys_.at(a) < keys_.at(b); });
+        return c;
+    }
+
+    // void LocalMapping::KeyFrameCulling() (src/LocalMapping.cc:539-593) for
+    // mpCurrentKeyFrame; vpNotErase: the keyframes whose mbNotErase is set
+    // (LoopClosing holds them).  The walk, the connection part of every
+    // SetBadFlag and its EraseObservations run on the device, one cull per
+    // call: after each, the tree part of SetBadFlag (src/KeyFrame.cc:523-581)
+    // runs here on the children's lists as that cull left them, and the call
+    // resumes with the rest of the list.
+    struct Culling {
+        std::vector<int> vpCulled;        // SetBadFlag ran: mpMap->EraseKeyFrame, mpKeyFrameDB->erase are the caller's
+        std::vector<int> vpToBeErased;    // redundant, but mbNotErase: mbToBeErased = true
+        std::vector<int> vpBadMapPoints;  // MapPoint::SetBadFlag ran through EraseObservation
+    };
+    Culling KeyFrameCulling(int mpCurrentKeyFrame, const std::vector<int>& vpNotErase = std::vector<int>())
+    {
+        Culling out;
+        const std::vector<int32_t> keep(vpNotErase.begin(), vpNotErase.end());
+        std::vector<int32_t> cand((size_t)kf_capacity_), mps((size_t)kf_capacity_), red((size_t)kf_capacity_),
+            dec((size_t)kf_capacity_), bad(256);
+        int cur = mpCurrentKeyFrame, first = 0, n_rest = 0;   // the list is cand[first, first + n_rest) once it is known
+        for (;;) {
+            orbx_covis_cull_args q{};
+            q.cur = cur;
+            q.n_keep = (int)keep.size();
+            q.keep = keep.data();
+            q.max_culls = 1;
+            q.cand = cand.data() + first;
+            q.n_cand = n_rest;
+            q.cand_cap = kf_capacity_ - first;
+            q.n_mps = mps.data();
+            q.n_redundant = red.data();
+            q.decision = dec.data();
+            q.bad_points = bad.data();
+            q.bad_cap = (int)bad.size();
+            const int code = orbx_covis_cull_keyframes(ctx_, m_, &q);
+            if (code == ORBX_ERR_CAPACITY && q.n_bad > q.bad_cap) {   // nothing changed: once more with room
+                bad.resize((size_t)q.n_bad);
+                continue;
+            }
+            check(code, "CovisibilityGraph::KeyFrameCulling");
+            out.vpBadMapPoints.insert(out.vpBadMapPoints.end(), bad.begin(), bad.begin() + q.n_bad);
+            for (int k = 0; k < q.n_done; k++) {
+                const int pKF = cand[(size_t)(first + k)];
+                if (dec[(size_t)k] == 2) out.vpToBeErased.push_back(pKF);
+                if (dec[(size_t)k] != 1) continue;
+                out.vpCulled.push_back(pKF);
+                UpdateSpanningTree(pKF);
+            }
+            if (q.n_done >= q.n_cand) break;
+            cur = -1;
+            first += q.n_done;
+            n_rest = q.n_cand - q.n_done;
+        }
+        return out;
+    }
+
+    // void LocalMapping::MapPointCulling() (src/LocalMapping.cc:190-218): the
+    // list loses what the reference erases from it; returns the points whose
+    // SetBadFlag ran.
+    struct RecentMapPoint {
+        int mnId, mnFound, mnVisible, mnFirstKFid;
+    };
+    std::vector<int> MapPointCulling(int nCurrentKFid, std::list<RecentMapPoint>& mlpRecentAddedMapPoints)
+    {
+        std::vector<int32_t> ids, found, visible, first;
+        for (const RecentMapPoint& p : mlpRecentAddedMapPoints) {
+            ids.push_back(p.mnId);
+            found.push_back(p.mnFound);
+            visible.push_back(p.mnVisible);
+            first.push_back(p.mnFirstKFid);
+        }
+        std::vector<int32_t> action(ids.size() + 1);
+        check(orbx_covis_cull_points(ctx_, m_, nCurrentKFid, (int)ids.size(), ids.data(), found.data(), visible.data(),
+                                     first.data(), action.data()),
+              "CovisibilityGraph::MapPointCulling");
+        std::vector<int> vpBad;
+        size_t k = 0;
+        for (std::list<RecentMapPoint>::iterator lit = mlpRecentAddedMapPoints.begin();
+             lit != mlpRecentAddedMapPoints.end(); k++) {
+            if (action[k] == 2 || action[k] == 3) vpBad.push_back(lit->mnId);
+            if (action[k] != 0) lit = mlpRecentAddedMapPoints.erase(lit);
+            else lit++;
+        }
+        return vpBad;
+    }
+
     int mFront = -1;              // the last single UpdateConnections' front
     std::vector<int> mWeights;    // the weights of the last read, entry for entry
 
 private:
+    void EraseChild(int pKF, int child)
+    {
+        if (pKF < 0) return;
+        std::vector<int>& c = mspChildrens_[pKF];
+        c.erase(std::remove(c.begin(), c.end(), child), c.end());
+    }
+    // "Update Spanning Tree" of KeyFrame::SetBadFlag (src/KeyFrame.cc:523-581)
+    // for a keyframe the device has just culled: its children are erased
+    // members' entries no more, and the lists are read as they stand now.
+    void UpdateSpanningTree(int mnId)
+    {
+        const int mpParent = GetParent(mnId);
+        if (mpParent < 0) return;   // the caller keeps no tree here
+        std::vector<int> sParentCandidates(1, mpParent);
+        std::vector<int> mspChildrens = GetChilds(mnId);
+        while (!mspChildrens.empty()) {
+            bool bContinue = false;
+            int max = -1, pC = -1, pP = -1;
+            for (int pKF : mspChildrens) {
+                const std::vector<int> vpConnected = GetVectorCovisibleKeyFrames(pKF);
+                for (size_t i = 0; i < vpConnected.size(); i++)
+                    for (int cand : sParentCandidates)
+                        if (vpConnected[i] == cand) {
+                            const int w = mWeights[i];   // GetWeight(vpConnected[i])
+                            if (w > max) {
+                                pC = pKF;
+                                pP = vpConnected[i];
+                                max = w;
+                                bContinue = true;
+                            }
+                        }
+            }
+            if (!bContinue) break;
+            ChangeParent(pC, pP);
+            sParentCandidates.push_back(pC);
+            mspChildrens.erase(std::remove(mspChildrens.begin(), mspChildrens.end(), pC), mspChildrens.end());
+        }
+        for (int pKF : mspChildrens) ChangeParent(pKF, mpParent);
+        EraseChild(mpParent, mnId);
+        mpParent_.erase(mnId);
+        mspChildrens_.erase(mnId);
+    }
+    std::map<int, uint64_t> keys_;                   // the KeyFrame* stand-ins, for the order of a set<KeyFrame*>
+    std::map<int, int> mpParent_;
+    std::map<int, std::vector<int>> mspChildrens_;
     std::vector<int> read(int mnId, int which)
     {
         std::vector<int32_t> kfs((size_t)kf_capacity_), ws((size_t)kf_capacity_);

@@ -27,6 +27,10 @@
 //                    the launches of one call follow each other on the stream.
 //   k_covis_list     one workgroup: an ordered list (or a row in key order),
 //                    sorted in LDS.
+//   k_cull_* / k_cullp_*
+//                    LocalMapping's KeyFrameCulling and MapPointCulling, with
+//                    the keypoint octaves beside the rows: described where
+//                    they stand, below.
 //
 // Order.  The host keeps every key ever added sorted and uploads each
 // keyframe's rank (orbx_covis_host.h), so (weight, key) compares as the word
@@ -74,6 +78,7 @@ struct CovisDev {
     int32_t* res;       // update_connections: 2 per id; connections: 1 + 2 cap
     int32_t* edit;      // an uploaded frame, or erase_points' cells and ids
     uint8_t* ferased;   // per frame entry
+    uint8_t* oct;       // kf_capacity x max_keypoints: mvKeysUn[i].octave, beside rows
 };
 
 __device__ inline bool covis_point(int p, int M) { return p >= 0 && p < M; }
@@ -329,10 +334,10 @@ __global__ __launch_bounds__(kCovisBlock) void k_covis_connect(CovisDev d, int h
     }
 }
 
-// The connection part of KeyFrame::SetBadFlag.
-__global__ __launch_bounds__(kCovisThreads) void k_covis_erase_kf(CovisDev d, int hi, int Ws, int id)
+// The connection part of KeyFrame::SetBadFlag, entry j of row id (thread 0 of
+// the call takes the keyframe's own words as well).
+__device__ inline void covis_erase_kf_entry(const CovisDev& d, int hi, int Ws, int id, int j)
 {
-    const int j = blockIdx.x * kCovisThreads + threadIdx.x;
     if (j == 0) {
         d.row_n[id] = -1;
         d.filt[id] = 0;
@@ -347,6 +352,11 @@ __global__ __launch_bounds__(kCovisThreads) void k_covis_erase_kf(CovisDev d, in
         d.filt[j] = 0;
     }
     *wij = 0;
+}
+
+__global__ __launch_bounds__(kCovisThreads) void k_covis_erase_kf(CovisDev d, int hi, int Ws, int id)
+{
+    covis_erase_kf_entry(d, hi, Ws, id, blockIdx.x * kCovisThreads + threadIdx.x);
 }
 
 __global__ void k_covis_add_kf(CovisDev d, int id, int n)
@@ -435,6 +445,347 @@ __global__ __launch_bounds__(kCovisBlock) void k_covis_list(CovisDev d, int hi, 
     if (tid == 0) res[0] = n;
 }
 
+// ---------------------------------------------------------------------------
+// LocalMapping::KeyFrameCulling (src/LocalMapping.cc:539-593) and
+// MapPointCulling (:190-218).
+//
+// KeyFrameCulling asks, for every point of a candidate's row, who else observes
+// it and at which octave: MapPoint::mObservations.  Here those observer lists
+// are gathered for one call, for the points of the candidate rows only:
+//
+//   k_cull_stamp     mark[p] = 1 for the points of all candidate rows.
+//   k_cull_count     one wavefront per member row: mark[p] += 1 per observer.
+//   k_cull_offsets   per stamped point one owner (a compare-and-swap on
+//                    first[p]) draws a bucket of cells from an atomic cursor,
+//                    first[p] = its place, and lists the point.
+//   k_cull_fill      the member rows again: every observer's cell (keyframe,
+//                    index, octave) into the point's bucket; the slot is what
+//                    the atomic decrement of mark[p] returns, so the order in
+//                    a bucket is arbitrary, and only counts are taken of it.
+//                    mark[p] is back at 1.
+//   k_cull_pre       a workgroup per candidate: nMPs and nRedundant against
+//                    the state the call found.  They hold until the first cull.
+//   k_cull_walk      one workgroup, the candidates in order.  It changes no
+//                    lasting state: a culled keyframe is a bit in LDS, a point
+//                    that went bad is mark[p] = 2, and the buckets are read
+//                    through both, which is the state as the candidates before
+//                    left it.  After a cull the counts are taken anew.
+//   k_cull_commit    one workgroup: unless a list overflowed its capacity, the
+//                    connection part of SetBadFlag for every culled keyframe.
+//   k_cull_finish    the listed points: a bad one is marked erased and its
+//                    cells cleared from the rows (unless overflowed); mark and
+//                    first go back to 0 and ~0.
+//
+// The launches are the same whatever is culled, and nothing is read back
+// before the end.
+//
+// The predicate.  The reference counts an observation as redundant when, with
+// Observations() > 3, its loop over the other observers finds three at an
+// octave <= o + 1, and leaves the loop at the third.  Both are shortcuts that
+// do not change "at least three such observers": three others and the keyframe
+// itself are four observations, so the gate holds whenever the count can reach
+// three, and where it fails there are at most two others; the break only stops
+// counting once the answer is known.
+constexpr int kCullHeader = 8;   // ints: n_cand, n_done, n_bad, commit, cell cursor, n_listed, culls
+constexpr int kCullGone = 2;     // mark[p] of a point that a cull of this call erased
+constexpr uint32_t kCullClaimed = 0xFFFFFFFEu;
+
+struct CullDev {
+    uint64_t* cells;      // per listed point: the number of its cells, then the cells
+    int32_t* listed;      // the stamped points, in no order
+    int32_t* bad;         // the points the culls erased, in order
+    int bad_room;
+    int32_t* pre;         // per candidate: nMPs, nRedundant of the state the call found
+    int32_t* out;         // kCullHeader ints, then cand, n_mps, n_redundant, decision: stride each
+    int stride;
+    const int32_t* lst;   // lst[0] candidates lst[1 ...]
+    const int32_t* keep;
+    int n_keep;
+};
+
+__device__ inline uint64_t cull_cell(int kf, int idx, int octave)
+{
+    return (uint64_t)octave << 32 | (uint32_t)kf << 16 | (uint32_t)idx;
+}
+__device__ inline int cull_cell_kf(uint64_t c) { return (int)((uint32_t)c >> 16); }
+__device__ inline int cull_cell_idx(uint64_t c) { return (int)(c & 0xFFFFu); }
+__device__ inline int cull_cell_octave(uint64_t c) { return (int)(c >> 32); }
+
+// candidate k of the list, or -1 where the reference changes nothing: keyframe
+// 0, an entry that names no member
+__device__ inline int cull_candidate(const CovisDev& d, const CullDev& u, int hi, int k)
+{
+    const int c = u.lst[1 + k];
+    return (c <= 0 || c >= hi || d.row_n[c] < 0) ? -1 : c;
+}
+
+__global__ __launch_bounds__(kCovisThreads) void k_cull_stamp(CovisDev d, CullDev u, int hi, int P, int M)
+{
+    if ((int)blockIdx.x >= u.lst[0]) return;
+    const int c = cull_candidate(d, u, hi, blockIdx.x);
+    if (c < 0) return;
+    const int n = min(d.row_n[c], P);
+    const int32_t* row = d.rows + (size_t)c * P;
+    for (int i = threadIdx.x; i < n; i += kCovisThreads) {
+        const int p = row[i];
+        if (covis_point(p, M) && !d.erased[p]) d.mark[p] = 1;
+    }
+}
+
+// Rows [0, hi), a wavefront each: every entry whose point is stamped adds one
+// to the point's mark.
+__global__ __launch_bounds__(kCovisThreads) void k_cull_count(CovisDev d, int hi, int P, int M)
+{
+    const int lane = threadIdx.x & 63;
+    const int j = blockIdx.x * kCovisWaves + (threadIdx.x >> 6);
+    if (j >= hi) return;
+    const int n = min(d.row_n[j], P);
+    const int32_t* row = d.rows + (size_t)j * P;
+    for (int i = lane; i < n; i += 64) {
+        const int p = row[i];
+        if (covis_point(p, M) && d.mark[p] != 0) atomicAdd(&d.mark[p], 1);   // a mark in flight is not 0 either
+    }
+}
+
+__global__ __launch_bounds__(kCovisThreads) void k_cull_offsets(CovisDev d, CullDev u, int hi, int P, int M)
+{
+    if ((int)blockIdx.x >= u.lst[0]) return;
+    const int c = cull_candidate(d, u, hi, blockIdx.x);
+    if (c < 0) return;
+    const int n = min(d.row_n[c], P);
+    const int32_t* row = d.rows + (size_t)c * P;
+    for (int i = threadIdx.x; i < n; i += kCovisThreads) {
+        const int p = row[i];
+        if (!covis_point(p, M) || d.erased[p]) continue;
+        if (atomicCAS(&d.first[p], 0xFFFFFFFFu, kCullClaimed) != 0xFFFFFFFFu) continue;   // another row's thread owns p
+        const int cnt = d.mark[p] - 1;
+        const uint32_t off = (uint32_t)atomicAdd(&u.out[4], cnt + 1);
+        u.cells[off] = (uint64_t)cnt;
+        __hip_atomic_store(&d.first[p], off, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        u.listed[atomicAdd(&u.out[5], 1)] = p;
+    }
+}
+
+__global__ __launch_bounds__(kCovisThreads) void k_cull_fill(CovisDev d, CullDev u, int hi, int P, int M)
+{
+    const int lane = threadIdx.x & 63;
+    const int j = blockIdx.x * kCovisWaves + (threadIdx.x >> 6);
+    if (j >= hi) return;
+    const int n = min(d.row_n[j], P);
+    const int32_t* row = d.rows + (size_t)j * P;
+    const uint8_t* oct = d.oct + (size_t)j * P;
+    for (int i = lane; i < n; i += 64) {
+        const int p = row[i];
+        if (!covis_point(p, M) || d.mark[p] == 0) continue;   // it never falls below 1 here
+        const int v = atomicSub(&d.mark[p], 1);               // 1 + count ... 2
+        const uint32_t off = __hip_atomic_load(&d.first[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        u.cells[(size_t)off + (size_t)(v - 1)] = cull_cell(j, i, oct[i]);
+    }
+}
+
+__device__ inline bool cull_bit(const uint32_t* bits, int j) { return bits && (bits[j >> 5] >> (j & 31) & 1u); }
+
+// nMPs and nRedundantObservations of candidate c; culled: the keyframes that
+// went in this call (a bitmap in LDS), or nullptr.
+template <int kT>
+__device__ inline void cull_tally(const CovisDev& d, const CullDev& u, int c, int P, int M, const uint32_t* culled,
+                                  BlockScratchN<kT / 64>& bs, int* n_mps, int* n_redundant)
+{
+    const int n = min(d.row_n[c], P);
+    const int32_t* row = d.rows + (size_t)c * P;
+    const uint8_t* oct = d.oct + (size_t)c * P;
+    int mps = 0, red = 0;
+    for (int i = threadIdx.x; i < n; i += kT) {
+        const int p = row[i];
+        if (!covis_point(p, M) || d.erased[p] || d.mark[p] == kCullGone) continue;
+        mps++;
+        const int o = oct[i];
+        const uint64_t* cell = u.cells + d.first[p];
+        const int cnt = (int)cell[0];
+        int obs = 0;
+        for (int t = 1; t <= cnt && obs < 3; t++) {
+            const uint64_t x = cell[t];
+            const int kf = cull_cell_kf(x);
+            if (kf != c && !cull_bit(culled, kf) && cull_cell_octave(x) <= o + 1) obs++;
+        }
+        red += obs >= 3;
+    }
+    *n_mps = block_sum(mps, bs, 0);
+    *n_redundant = block_sum(red, bs, 1);
+}
+
+__global__ __launch_bounds__(kCovisThreads) void k_cull_pre(CovisDev d, CullDev u, int hi, int P, int M)
+{
+    __shared__ BlockScratchN<kCovisWaves> bs;
+    const int k = blockIdx.x;
+    if (k >= u.lst[0]) return;
+    const int c = cull_candidate(d, u, hi, k);
+    int mps = 0, red = 0;
+    if (c >= 0) cull_tally<kCovisThreads>(d, u, c, P, M, nullptr, bs, &mps, &red);
+    if (threadIdx.x == 0) {
+        u.pre[2 * k] = mps;
+        u.pre[2 * k + 1] = red;
+    }
+}
+
+__global__ __launch_bounds__(kCovisBlock) void k_cull_walk(CovisDev d, CullDev u, int hi, int P, int M, int max_culls,
+                                                           int cand_cap, int bad_cap)
+{
+    constexpr int kWords = kCovisMaxKeyframes / 32;
+    __shared__ uint32_t s_culled[kWords], s_keep[kWords];
+    __shared__ BlockScratchN<kCovisBlock / 64> bs;
+    const int tid = threadIdx.x;
+    for (int w = tid; w < kWords; w += kCovisBlock) s_culled[w] = s_keep[w] = 0;
+    __syncthreads();
+    for (int t = tid; t < u.n_keep; t += kCovisBlock) atomicOr(&s_keep[u.keep[t] >> 5], 1u << (u.keep[t] & 31));
+    const int n_cand = u.lst[0];
+    int32_t* o_cand = u.out + kCullHeader;
+    int32_t *o_mps = o_cand + u.stride, *o_red = o_mps + u.stride, *o_dec = o_red + u.stride;
+    for (int k = tid; k < n_cand; k += kCovisBlock) o_cand[k] = u.lst[1 + k];
+    __syncthreads();
+    int n_done = n_cand, n_bad = 0, culls = 0;
+    for (int k = 0; k < n_cand; k++) {
+        int c = cull_candidate(d, u, hi, k);
+        if (c >= 0 && cull_bit(s_culled, c)) c = -1;   // listed twice and gone at its first place
+        int mps = 0, red = 0, dec = -1;
+        if (c >= 0) {
+            if (culls == 0) {
+                mps = u.pre[2 * k];
+                red = u.pre[2 * k + 1];
+            } else {
+                cull_tally<kCovisBlock>(d, u, c, P, M, s_culled, bs, &mps, &red);
+            }
+            // nRedundantObservations > 0.9 * nMPs: one FP64 product, rounded once, and the comparison
+            const bool redundant = (double)red > __dmul_rn(0.9, (double)mps);
+            dec = !redundant ? 0 : cull_bit(s_keep, c) ? 2 : 1;
+        }
+        if (tid == 0) {
+            o_mps[k] = mps;
+            o_red[k] = red;
+            o_dec[k] = dec;
+        }
+        if (dec != 1) continue;
+        // MapPoint::EraseObservation for every point of the row: the ones that two keyframes or fewer still
+        // hold go bad, in index order
+        __syncthreads();   // the tally's reads of the bitmap are done
+        if (tid == 0) s_culled[c >> 5] |= 1u << (c & 31);
+        __syncthreads();
+        const int n = min(d.row_n[c], P);
+        const int32_t* row = d.rows + (size_t)c * P;
+        int buf = 0;
+        for (int i0 = 0; i0 < n; i0 += kCovisBlock, buf ^= 1) {
+            const int i = i0 + tid;
+            const int p = i < n ? row[i] : -1;
+            bool bad = false;
+            if (covis_point(p, M) && !d.erased[p] && d.mark[p] != kCullGone) {
+                const uint64_t* cell = u.cells + d.first[p];
+                const int cnt = (int)cell[0];
+                int left = 0;
+                for (int t = 1; t <= cnt && left < 3; t++) left += !cull_bit(s_culled, cull_cell_kf(cell[t]));
+                bad = left <= 2;
+            }
+            int total = 0;
+            const int o = block_exclusive_scan(bad ? 1 : 0, &total, bs, buf);
+            if (bad) {
+                d.mark[p] = kCullGone;   // a point stands once in a row: no other thread of this loop reads it
+                if (n_bad + o < u.bad_room) u.bad[n_bad + o] = p;
+            }
+            n_bad += total;
+        }
+        __syncthreads();   // the marks, before the next candidate's tally
+        if (++culls == max_culls) {
+            n_done = k + 1;
+            break;
+        }
+    }
+    if (tid == 0) {
+        u.out[0] = n_cand;
+        u.out[1] = n_done;
+        u.out[2] = n_bad;
+        u.out[3] = (n_cand <= cand_cap && n_bad <= bad_cap) ? 1 : 0;
+        u.out[6] = culls;
+    }
+}
+
+// After k_cull_walk; the culled keyframes one after the other, as
+// k_covis_erase_kf takes each.
+__global__ __launch_bounds__(kCovisBlock) void k_cull_commit(CovisDev d, CullDev u, int hi, int Ws)
+{
+    if (!u.out[3]) return;
+    const int n_done = u.out[1];
+    const int32_t* o_cand = u.out + kCullHeader;
+    const int32_t* o_dec = o_cand + 3 * (size_t)u.stride;
+    for (int k = 0; k < n_done; k++) {
+        if (o_dec[k] != 1) continue;
+        for (int j = threadIdx.x; j < max(hi, 1); j += kCovisBlock) covis_erase_kf_entry(d, hi, Ws, o_cand[k], j);
+        __syncthreads();   // the next keyframe reads the weights this one wrote
+    }
+}
+
+__global__ __launch_bounds__(kCovisThreads) void k_cull_finish(CovisDev d, CullDev u, int P)
+{
+    const int n = u.out[5];
+    const bool commit = u.out[3] != 0;
+    for (int t = blockIdx.x * kCovisThreads + threadIdx.x; t < n; t += gridDim.x * kCovisThreads) {
+        const int p = u.listed[t];
+        if (commit && d.mark[p] == kCullGone) {   // MapPoint::SetBadFlag
+            d.erased[p] = 1;
+            const uint64_t* cell = u.cells + d.first[p];
+            const int cnt = (int)cell[0];
+            for (int k = 1; k <= cnt; k++) d.rows[(size_t)cull_cell_kf(cell[k]) * P + cull_cell_idx(cell[k])] = -1;
+        }
+        d.mark[p] = 0;
+        d.first[p] = 0xFFFFFFFFu;
+    }
+}
+
+// MapPointCulling.  in: ids, found, visible, first_kf, n each.  After
+// k_cullp_stamp (mark 1) and k_cull_count, mark[p] - 1 is Observations().
+__global__ __launch_bounds__(kCovisThreads) void k_cullp_stamp(CovisDev d, const int32_t* in, int n)
+{
+    const int k = blockIdx.x * kCovisThreads + threadIdx.x;
+    if (k < n) d.mark[in[k]] = 1;
+}
+
+// The reference's if-chain; mark[p] = -1 for a point that goes, else 0.
+__global__ __launch_bounds__(kCovisThreads) void k_cullp_decide(CovisDev d, const int32_t* in, int n, int cur_kf,
+                                                                int32_t* action)
+{
+    const int k = blockIdx.x * kCovisThreads + threadIdx.x;
+    if (k >= n) return;
+    const int p = in[k], found = in[n + k], visible = in[2 * n + k], age = cur_kf - in[3 * n + k];
+    const int observers = d.mark[p] - 1;
+    int a = 0;
+    if (d.erased[p]) a = 1;
+    else if (__fdiv_rn((float)found, (float)visible) < 0.25f) a = 2;   // GetFoundRatio(): FP32, inf and NaN compare false
+    else if (age >= 2 && observers <= 2) a = 3;
+    else if (age >= 3) a = 4;
+    action[k] = a;
+    d.mark[p] = (a == 2 || a == 3) ? -1 : 0;
+}
+
+// Rows [0, hi), a wavefront each: the cells of the points that go are cleared.
+__global__ __launch_bounds__(kCovisThreads) void k_cullp_clear(CovisDev d, int hi, int P, int M)
+{
+    const int lane = threadIdx.x & 63;
+    const int j = blockIdx.x * kCovisWaves + (threadIdx.x >> 6);
+    if (j >= hi) return;
+    const int n = min(d.row_n[j], P);
+    int32_t* row = d.rows + (size_t)j * P;
+    for (int i = lane; i < n; i += 64) {
+        const int p = row[i];
+        if (covis_point(p, M) && d.mark[p] == -1) row[i] = -1;
+    }
+}
+
+__global__ __launch_bounds__(kCovisThreads) void k_cullp_finish(CovisDev d, const int32_t* in, int n, const int32_t* action)
+{
+    const int k = blockIdx.x * kCovisThreads + threadIdx.x;
+    if (k >= n || (action[k] != 2 && action[k] != 3)) return;
+    d.erased[in[k]] = 1;
+    d.mark[in[k]] = 0;
+}
+
 }  // namespace orbx
 
 using namespace orbx;
@@ -497,7 +848,7 @@ extern "C" int orbx_covis_create(orbx_ctx* ctx, int kf_capacity, int mp_capacity
     const Region<int32_t> o_top = l.take<int32_t>((size_t)kCovisLocalLimit * kCovisBest), o_cnt = l.take<int32_t>(K),
                           o_lkf = l.take<int32_t>(K), o_lmp = l.take<int32_t>(M), o_hdr = l.take<int32_t>(kCovisHeader),
                           o_res = l.take<int32_t>(2 * K + 8), o_edit = l.take<int32_t>(m->edit_cap);
-    const Region<uint8_t> o_fe = l.take<uint8_t>(P);
+    const Region<uint8_t> o_fe = l.take<uint8_t>(P), o_oct = l.take<uint8_t>(K * P);
     if (hipMalloc(&m->mem, l.total) != hipSuccess) {
         delete m;
         return ORBX_ERR_NOMEM;
@@ -507,7 +858,8 @@ extern "C" int orbx_covis_create(orbx_ctx* ctx, int kf_capacity, int mp_capacity
                     region_ptr(b, o_er),   region_ptr(b, o_w),    region_ptr(b, o_f),     region_ptr(b, o_th),
                     region_ptr(b, o_mark), region_ptr(b, o_first), region_ptr(b, o_votes), region_ptr(b, o_incl),
                     region_ptr(b, o_top),  region_ptr(b, o_cnt),  region_ptr(b, o_lkf),   region_ptr(b, o_lmp),
-                    region_ptr(b, o_hdr),  region_ptr(b, o_res),  region_ptr(b, o_edit),  region_ptr(b, o_fe)};
+                    region_ptr(b, o_hdr),  region_ptr(b, o_res),  region_ptr(b, o_edit),  region_ptr(b, o_fe),
+                    region_ptr(b, o_oct)};
     r = orbx_covis_clear(ctx, m);
     if (r != ORBX_OK) {
         orbx_covis_destroy(m);
@@ -741,4 +1093,157 @@ extern "C" int orbx_covis_update_reference(orbx_ctx* ctx, orbx_covis* m, orbx_co
         ORBX_HIP_CHECK(hipMemcpyAsync(q->frame_erased, m->d.ferased, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return (q->n_local_kf > q->kf_cap || q->n_local_mp > q->mp_cap) ? ORBX_ERR_CAPACITY : ORBX_OK;
+}
+
+extern "C" int orbx_covis_set_octaves(orbx_ctx* ctx, orbx_covis* m, int id, int n, const uint8_t* octave)
+{
+    if (!usable(ctx, m)) return ORBX_ERR_ARG;
+    const int r = m->tab.check_octaves(id, n, octave);
+    if (r != ORBX_OK) return r;
+    ctx_enter(ctx);
+    if (n > 0) {
+        ORBX_HIP_CHECK(hipMemcpyAsync(m->d.oct + (size_t)id * m->tab.max_keypoints, octave, (size_t)n, hipMemcpyHostToDevice,
+                                      ctx->stream));
+        ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // the caller's array is free at return
+    }
+    m->tab.commit_octaves(id);
+    return ORBX_OK;
+}
+
+extern "C" int orbx_covis_cull_keyframes(orbx_ctx* ctx, orbx_covis* m, orbx_covis_cull_args* q)
+{
+    if (!usable(ctx, m)) return ORBX_ERR_ARG;
+    CovisTable& t = m->tab;
+    int r = t.check_cull(q);
+    if (r == ORBX_ERR_CAPACITY) {   // the caller's own list does not fit its capacity
+        q->n_done = q->n_bad = 0;
+        return r;
+    }
+    if (r != ORBX_OK) return r;
+    const bool own = q->cur >= 0;   // the list is cur's, taken on the device
+    if (own) q->n_cand = 0;
+    q->n_done = q->n_bad = 0;
+    if (!own && (q->n_cand == 0 || t.hi == 0)) {   // nothing listed, or no keyframe was ever added: no member to judge
+        for (int k = 0; k < q->n_cand; k++) {
+            q->n_mps[k] = q->n_redundant[k] = 0;
+            q->decision[k] = -1;
+        }
+        q->n_done = q->n_cand;
+        return ORBX_OK;
+    }
+    ctx_enter(ctx);
+    const int hi = t.hi, P = t.max_keypoints, M = t.mp_capacity;
+    const int stride = own ? hi : q->n_cand;   // an ordered list names ids below hi, each once
+    const size_t cells = t.member_cells();     // every observer cell, every listed point and every bad point is one
+    Layout l;
+    const Region<uint64_t> o_cells = l.take<uint64_t>(2 * cells + 1);
+    const Region<int32_t> o_listed = l.take<int32_t>(cells), o_bad = l.take<int32_t>(cells),
+                          o_pre = l.take<int32_t>(2 * (size_t)stride),
+                          o_out = l.take<int32_t>(kCullHeader + 4 * (size_t)stride),
+                          o_up = l.take<int32_t>(1 + (size_t)(own ? 0 : q->n_cand) + (size_t)q->n_keep);
+    if ((r = ensure_scratch(ctx, l.total)) != ORBX_OK) return r;
+    void* b = ctx->scratch;
+    int32_t* up = region_ptr(b, o_up);
+    CullDev u{};
+    u.cells = region_ptr(b, o_cells);
+    u.listed = region_ptr(b, o_listed);
+    u.bad = region_ptr(b, o_bad);
+    u.bad_room = (int)cells;   // at most kCovisMaxKeyframes x kCovisMaxKeypoints, below 2^30
+    u.pre = region_ptr(b, o_pre);
+    u.out = region_ptr(b, o_out);
+    u.stride = stride;
+    u.n_keep = q->n_keep;
+    // one upload: the caller's list behind its length, then the kept keyframes
+    std::vector<int32_t> h;
+    h.reserve(o_up.count);
+    h.push_back(own ? 0 : q->n_cand);
+    if (!own) h.insert(h.end(), q->cand, q->cand + q->n_cand);
+    u.keep = up + h.size();
+    if (q->n_keep) h.insert(h.end(), q->keep, q->keep + q->n_keep);
+    ORBX_HIP_CHECK(hipMemcpyAsync(up, h.data(), h.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    ORBX_HIP_CHECK(hipMemsetAsync(u.out, 0, kCullHeader * sizeof(int32_t), ctx->stream));
+    timer_begin(ctx, "covis_cull_kf");
+    if (own) {
+        const int N = covis_sort_len(hi);
+        hipLaunchKernelGGL(k_covis_list, dim3(1), dim3(kCovisBlock), (size_t)N * sizeof(uint32_t), ctx->stream, m->d, hi,
+                           m->w_stride, q->cur, ORBX_COVIS_ORDERED, N, m->d.res, t.kf_capacity);
+        u.lst = m->d.res;
+    } else {
+        u.lst = up;
+    }
+    const dim3 per_cand(stride), per_row((hi + kCovisWaves - 1) / kCovisWaves), threads(kCovisThreads);
+    hipLaunchKernelGGL(k_cull_stamp, per_cand, threads, 0, ctx->stream, m->d, u, hi, P, M);
+    hipLaunchKernelGGL(k_cull_count, per_row, threads, 0, ctx->stream, m->d, hi, P, M);
+    hipLaunchKernelGGL(k_cull_offsets, per_cand, threads, 0, ctx->stream, m->d, u, hi, P, M);
+    hipLaunchKernelGGL(k_cull_fill, per_row, threads, 0, ctx->stream, m->d, u, hi, P, M);
+    hipLaunchKernelGGL(k_cull_pre, per_cand, threads, 0, ctx->stream, m->d, u, hi, P, M);
+    hipLaunchKernelGGL(k_cull_walk, dim3(1), dim3(kCovisBlock), 0, ctx->stream, m->d, u, hi, P, M, q->max_culls,
+                       q->cand_cap, q->bad_cap);
+    hipLaunchKernelGGL(k_cull_commit, dim3(1), dim3(kCovisBlock), 0, ctx->stream, m->d, u, hi, m->w_stride);
+    const int listed_blocks = std::max(1, std::min(1024, blocks_of(u.bad_room)));   // a grid-stride loop over the list
+    hipLaunchKernelGGL(k_cull_finish, dim3(listed_blocks), threads, 0, ctx->stream, m->d, u, P);
+    timer_end(ctx, "covis_cull_kf");
+    ORBX_HIP_CHECK(hipGetLastError());
+    // one read-back of the header and the per-candidate lists; the bad points, whose number the header gives,
+    // follow only when a cull took some with it
+    std::vector<int32_t> out(o_out.count);
+    ORBX_HIP_CHECK(hipMemcpyAsync(out.data(), u.out, out.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    const int n_cand = out[0], n_done = out[1], n_bad = out[2];
+    std::vector<int32_t> bad((size_t)n_bad);
+    if (n_bad > 0) {
+        ORBX_HIP_CHECK(hipMemcpyAsync(bad.data(), u.bad, bad.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    }
+    const int32_t* cand = out.data() + kCullHeader;
+    const int32_t *mps = cand + stride, *red = mps + stride, *dec = red + stride;
+    q->n_cand = n_cand;
+    q->n_done = n_done;
+    q->n_bad = n_bad;
+    for (int k = 0; k < std::min(n_cand, q->cand_cap); k++)
+        if (own) q->cand[k] = cand[k];
+    for (int k = 0; k < std::min(n_done, q->cand_cap); k++) {
+        q->n_mps[k] = mps[k];
+        q->n_redundant[k] = red[k];
+        q->decision[k] = dec[k];
+    }
+    for (int k = 0; k < std::min(n_bad, q->bad_cap); k++) q->bad_points[k] = bad[(size_t)k];
+    // the shadow follows what the device committed
+    r = t.apply_cull(n_cand, q->cand_cap, n_done, cand, dec, n_bad, q->bad_cap, bad.data());
+    if (r == ORBX_ERR_CAPACITY) return r;
+    return (r == ORBX_OK && out[3] == 1) ? ORBX_OK : ORBX_ERR_HIP;   // the two never differ
+}
+
+extern "C" int orbx_covis_cull_points(orbx_ctx* ctx, orbx_covis* m, int cur_kf, int n, const int32_t* ids,
+                                      const int32_t* found, const int32_t* visible, const int32_t* first_kf,
+                                      int32_t* action)
+{
+    if (!usable(ctx, m)) return ORBX_ERR_ARG;
+    CovisTable& t = m->tab;
+    int r = t.check_cull_points(cur_kf, n, ids, found, visible, first_kf, action);
+    if (r != ORBX_OK || n == 0) return r;
+    ctx_enter(ctx);
+    const int hi = t.hi, P = t.max_keypoints, M = t.mp_capacity;
+    Layout l;
+    const Region<int32_t> o_in = l.take<int32_t>(4 * (size_t)n), o_act = l.take<int32_t>((size_t)n);
+    if ((r = ensure_scratch(ctx, l.total)) != ORBX_OK) return r;
+    int32_t* in = region_ptr(ctx->scratch, o_in);
+    int32_t* act = region_ptr(ctx->scratch, o_act);
+    std::vector<int32_t> h;   // one upload
+    h.reserve(o_in.count);
+    for (const int32_t* a : {ids, found, visible, first_kf}) h.insert(h.end(), a, a + n);
+    ORBX_HIP_CHECK(hipMemcpyAsync(in, h.data(), h.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    const dim3 per_id(blocks_of(n)), per_row((hi + kCovisWaves - 1) / kCovisWaves), threads(kCovisThreads);
+    timer_begin(ctx, "covis_cull_mp");
+    hipLaunchKernelGGL(k_cullp_stamp, per_id, threads, 0, ctx->stream, m->d, in, n);
+    if (hi > 0) hipLaunchKernelGGL(k_cull_count, per_row, threads, 0, ctx->stream, m->d, hi, P, M);
+    hipLaunchKernelGGL(k_cullp_decide, per_id, threads, 0, ctx->stream, m->d, in, n, cur_kf, act);
+    if (hi > 0) hipLaunchKernelGGL(k_cullp_clear, per_row, threads, 0, ctx->stream, m->d, hi, P, M);
+    hipLaunchKernelGGL(k_cullp_finish, per_id, threads, 0, ctx->stream, m->d, in, n, act);
+    timer_end(ctx, "covis_cull_mp");
+    ORBX_HIP_CHECK(hipGetLastError());
+    ORBX_HIP_CHECK(hipMemcpyAsync(action, act, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    ORBX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    t.apply_cull_points(n, ids, action);
+    return ORBX_OK;
 }

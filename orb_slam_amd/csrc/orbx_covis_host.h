@@ -77,6 +77,7 @@ struct CovisTable {
         rows.assign((size_t)kf_capacity, std::vector<int32_t>());
         erased.assign((size_t)mp_capacity, 0);
         obs.assign((size_t)mp_capacity, std::vector<uint32_t>());
+        octaves_set.assign((size_t)kf_capacity, 0);
         size = 0;
         hi = 0;
     }
@@ -221,6 +222,97 @@ struct CovisTable {
         for (int i = 0; i < n; i++)
             if (!point_ok(mp[i])) return false;
         return true;
+    }
+
+    // ---- the culling walks (orbx_covis_set_octaves, _cull_keyframes, _cull_points) ----
+    // The octaves themselves live in HBM alone; the shadow knows who has them.
+    std::vector<uint8_t> octaves_set;   // [kf_capacity]
+
+    int check_octaves(int id, int n, const uint8_t* octave) const
+    {
+        if (!is_member(id) || n != (int)rows[(size_t)id].size() || (n > 0 && !octave)) return ORBX_ERR_ARG;
+        return ORBX_OK;
+    }
+    void commit_octaves(int id) { octaves_set[(size_t)id] = 1; }
+    bool has_octaves(int id) const { return octaves_set[(size_t)id] != 0; }
+    bool every_member_has_octaves() const
+    {
+        for (int id = 0; id < hi; id++)
+            if (state[(size_t)id] == kMember && !has_octaves(id)) return false;
+        return true;
+    }
+    // the cells of all member rows: what bounds the observer cells and the bad points of one cull call
+    size_t member_cells() const
+    {
+        size_t s = 0;
+        for (int id = 0; id < hi; id++)
+            if (state[(size_t)id] == kMember) s += rows[(size_t)id].size();
+        return s;
+    }
+    bool ids_in_range(int n, const int32_t* ids) const
+    {
+        if (n < 0 || (n > 0 && !ids)) return false;
+        for (int k = 0; k < n; k++)
+            if (!kf_in_range(ids[k])) return false;
+        return true;
+    }
+    // The arguments of orbx_covis_cull_keyframes, before any device work.
+    int check_cull(const orbx_covis_cull_args* q) const
+    {
+        if (!q || q->max_culls < 0 || q->cand_cap < 0 || q->bad_cap < 0 || !ids_in_range(q->n_keep, q->keep))
+            return ORBX_ERR_ARG;
+        if ((q->cand_cap > 0 && (!q->cand || !q->n_mps || !q->n_redundant || !q->decision)) ||
+            (q->bad_cap > 0 && !q->bad_points))
+            return ORBX_ERR_ARG;
+        if (q->cur == -1) {
+            if (q->n_cand > kf_capacity || !ids_in_range(q->n_cand, q->cand)) return ORBX_ERR_ARG;
+        } else if (!is_member(q->cur)) {
+            return ORBX_ERR_ARG;
+        }
+        if (!every_member_has_octaves()) return ORBX_ERR_ARG;
+        if (q->cur == -1 && q->n_cand > q->cand_cap) return ORBX_ERR_CAPACITY;
+        return ORBX_OK;
+    }
+    // What one cull call read back: all or none.  A count above its capacity
+    // changes nothing (the device left its state alone too); otherwise every
+    // culled keyframe goes as commit_erase_keyframe takes it and every bad
+    // point as erase_points takes it.  The end state does not depend on the
+    // order of the two kinds: a row that went no longer holds the point, a
+    // point that went no longer stands in the row.
+    int apply_cull(int n_cand, int cand_cap, int n_done, const int32_t* cand, const int32_t* decision, int n_bad,
+                   int bad_cap, const int32_t* bad)
+    {
+        if (n_cand > cand_cap || n_bad > bad_cap) return ORBX_ERR_CAPACITY;
+        if (n_done < 0 || n_done > n_cand || n_bad < 0 || check_points(n_bad, bad) != ORBX_OK) return ORBX_ERR_ARG;
+        for (int k = 0; k < n_done; k++)
+            if (decision[k] == 1 && !is_member(cand[k])) return ORBX_ERR_ARG;
+        for (int k = 0; k < n_done; k++)
+            if (decision[k] == 1) commit_erase_keyframe(cand[k]);
+        std::vector<uint32_t> cells;
+        erase_points(n_bad, bad, cells);
+        return ORBX_OK;
+    }
+
+    // The arguments of orbx_covis_cull_points.
+    int check_cull_points(int cur_kf, int n, const int32_t* ids, const int32_t* found, const int32_t* visible,
+                          const int32_t* first_kf, const int32_t* action) const
+    {
+        if (cur_kf < 0 || check_points(n, ids) != ORBX_OK || (n > 0 && (!found || !visible || !first_kf || !action)))
+            return ORBX_ERR_ARG;
+        for (int k = 0; k < n; k++)
+            if (found[k] < 0 || visible[k] < 0 || first_kf[k] < 0 || first_kf[k] > cur_kf) return ORBX_ERR_ARG;
+        std::vector<int32_t> s(ids, ids + n);
+        std::sort(s.begin(), s.end());
+        return std::adjacent_find(s.begin(), s.end()) == s.end() ? ORBX_OK : ORBX_ERR_ARG;
+    }
+    // the points of actions 2 and 3 go
+    void apply_cull_points(int n, const int32_t* ids, const int32_t* action)
+    {
+        std::vector<int32_t> gone;
+        for (int k = 0; k < n; k++)
+            if (action[k] == 2 || action[k] == 3) gone.push_back(ids[k]);
+        std::vector<uint32_t> cells;
+        erase_points((int)gone.size(), gone.data(), cells);
     }
 };
 
