@@ -839,7 +839,9 @@ int orbx_dev_undistort(orbx_ctx* ctx, int first, int count, const float* K, cons
  * TemplatedVocabulary.h:1338-1420) -- node 0 the root, node i (1..n-1) a
  * child of parent[i] (children in increasing id order), word ids given to
  * the nodes flagged is_leaf in id order, a 32-byte descriptor and a weight
- * (idf) per node.  Kept in HBM for the vocabulary's lifetime. */
+ * (idf) per node.  Kept in HBM for the vocabulary's lifetime.  A refused
+ * call (ORBX_ERR_ARG: a null pointer, k, L < 1, n_nodes < 2, a parent[i]
+ * outside [0, i)) leaves *out NULL. */
 typedef struct orbx_vocab orbx_vocab;
 int orbx_vocab_create(orbx_ctx* ctx, int k, int L, int n_nodes, const int32_t* parent,
                       const uint8_t* is_leaf, const uint8_t* desc, const double* weight,

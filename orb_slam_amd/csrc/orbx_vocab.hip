@@ -206,9 +206,9 @@ using namespace orbx;
 extern "C" int orbx_vocab_create(orbx_ctx* ctx, int k, int L, int n_nodes, const int32_t* parent,
                                  const uint8_t* is_leaf, const uint8_t* desc, const double* weight, orbx_vocab** out)
 {
+    if (out) *out = nullptr;   // every refusal below leaves no handle behind
     if (!ctx || !out || k < 1 || L < 1 || n_nodes < 2 || !parent || !is_leaf || !desc || !weight)
         return ORBX_ERR_ARG;
-    *out = nullptr;
     // children CSR in increasing id order; word ids for the leaf-flagged nodes
     std::vector<int32_t> cnt(n_nodes + 1, 0), word(n_nodes, 0);
     int wid = 0;
